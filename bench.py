@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: scored users/sec (1 + 100 candidates) of the CARCA eval forward on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -449,6 +449,25 @@ def measure_epoch_pipeline(c, model, device, world, fence, n_batches=256):
                     "headline" % n_batches}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, scores):
+    """--dump-outputs: the scores one timed step handed back, as out_dir/<name>.npy (float32).  Scores above DUMP_MAX_BYTES
+    are written as a fixed, seeded sample of whole users, with their row indices beside them (<name>_rows.npy, float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    if scores.nbytes > DUMP_MAX_BYTES:
+        rows2d = scores.reshape(scores.shape[0], -1)
+        keep = DUMP_MAX_BYTES // (rows2d[0].nbytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(rows2d.shape[0], size=keep, replace=False))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        scores = rows2d[rows]
+    np.save(os.path.join(out_dir, name + ".npy"), scores)
+
+
 def free_port():
     import socket
 
@@ -501,6 +520,8 @@ def main():
                     "passes of tools/profile_round.sh: their per-launch averages must cover the headline batch only)")
     ap.add_argument("--no-configs", action="store_true", help="skip the side pass over BASELINE's C3 / C5 configurations")
     ap.add_argument("--no-scoring-scaling", action="store_true", help="skip the scoring kernel's B = 1024 / 4096 side pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the scores of the last timed step to "
+                    "DIR/scores.npy (float32; rank r > 0: scores_rank<r>.npy) for comparing two builds output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -615,6 +636,7 @@ def main():
         elapsed = time.perf_counter() - t0
         gpu_span_ms = g0.elapsed_time(g1)
         host_issue_ms = 1e3 * (host_done[-1] - t0)
+        last_scores = y.float().cpu().numpy() if args.dump_outputs else None  # (behind the fence: not timed)
         for _ in range(SIDE_STEPS):  # (outside the timed region: every kernel's pair)
             step(True, every_kernel=True)
         fence()
@@ -717,6 +739,9 @@ def main():
         else:
             traffic_note = ("profiles/%s was measured on another version of csrc/gemm.hip: stale, not reported"
                             % os.path.basename(tfiles[-1]))
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "scores" if rank == 0 else "scores_rank%d" % rank, last_scores)
 
     if rank == 0:
         users = world * c["B"] * args.steps

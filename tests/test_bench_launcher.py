@@ -45,3 +45,25 @@ def test_plain_invocation_does_not_import_torch_cuda_in_the_parent():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
+
+
+def test_dump_outputs_writes_the_scores_and_a_seeded_sample_above_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: float32 scores as DIR/<name>.npy; above DUMP_MAX_BYTES a fixed sample of whole users, their rows
+    beside them, the same sample on every run."""
+    import numpy as np
+
+    bench = _bench()
+    scores = np.random.default_rng(3).standard_normal((128, 101))
+    bench.dump_outputs(str(tmp_path / "full"), "scores", scores)
+    got = np.load(tmp_path / "full" / "scores.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, scores.astype(np.float32))
+    assert not (tmp_path / "full" / "scores_rows.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), "scores", scores)
+    sample, rows = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "scores_rows.npy")
+    assert sample.nbytes + rows.nbytes <= 10_000 and len(rows) > 0 and rows.dtype == np.float64
+    assert np.array_equal(sample, scores.astype(np.float32)[rows.astype(np.int64)])
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "scores.npy"))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "scores_rows.npy"))

@@ -92,23 +92,33 @@ def test_g3_adam_three_steps():
     fx = load("g3_adam")
     cfg = oracle_config(fx.cfg)
     params = {k: v.clone().requires_grad_(True) for k, v in fx.params.items()}
-    opt = torch.optim.Adam(list(params.values()), lr=1e-3, weight_decay=0.0, betas=(0.9, 0.98))
+    lr, steps = 1e-3, 3
+    opt = torch.optim.Adam(list(params.values()), lr=lr, weight_decay=0.0, betas=(0.9, 0.98))
     profile, targets = _train_inputs(fx.ins)
     mask = O.get_mask(fx.ins["o_x"])
-    for step in range(3):
+    for step in range(steps):
         opt.zero_grad()
         y = O.carca_forward(params, cfg, profile, targets, training=True)
         loss = O.bce_loss(y, fx.ins["y_true"], mask)
         assert abs(float(loss) - float(fx.outs[f"loss{step}"])) < 2e-6
         loss.backward()
+        if step == 0:
+            first_grad = {k: v.grad.detach().abs() for k, v in params.items() if v.grad is not None}
         opt.step()
     for k, v in params.items():
         # A key bias shifts every score of a softmax row equally, so its true gradient is 0 and
         # what reaches Adam is round-off that Adam rescales to +-lr steps: not comparable.
         if k.endswith("WK.bias"):
             continue
+        got, want = v.detach(), fx.outs["final/" + k]
+        # The same holds for the few entries whose first gradient is a near-cancelling sum (feats_embed.weight[156, 8]:
+        # -1.07e-8 in fp64, -0.80e-8 in fp32): Adam's first step g / (|g| + 1e-8) is then set by the summation order of
+        # the CPU's kernels.  Such entries (0 < |g| < 1e-7, 15 of the 60k) are held to Adam's reach, lr per step per run.
+        g = first_grad.get(k)
+        noisy = (g > 0) & (g < 1e-7) if g is not None else torch.zeros_like(got, dtype=torch.bool)
+        assert torch.allclose(got[noisy], want[noisy], atol=2 * steps * lr, rtol=0), k
         # Adam's first steps are +-lr whatever the gradient size, so allow a few 1e-6
-        assert torch.allclose(v.detach(), fx.outs["final/" + k], atol=5e-5, rtol=0), k
+        assert torch.allclose(got[~noisy], want[~noisy], atol=5e-5, rtol=0), k
 
 
 def test_g4_metrics():
