@@ -5,6 +5,7 @@
 #include <mutex>
 #include <vector>
 
+#include "attn_common.h"
 #include "carca_common.h"
 #include "../../include/carca_hip.h"
 
@@ -120,6 +121,17 @@ extern "C" int carca_padded_dims(int d, int H, int* dpi, int* dhp, int* dpo) {
   if (dpo) *dpo = H * p;
   return CARCA_OK;
 }
+
+#define CARCA_ATT_BUILT_(DPI_, DHP_, H_, ...) \
+  if (dpi == DPI_ && dhp == DHP_ && H == H_) return 1;
+extern "C" int carca_attn_geometry_built(int d, int H) {
+  if (d < 1 || H < 1 || d % H != 0 || d > 128) return 0;  // (so that carca_padded_dims below sets no error)
+  int dpi = 0, dhp = 0;
+  carca_padded_dims(d, H, &dpi, &dhp, nullptr);
+  CARCA_ATT_GEOMETRIES(CARCA_ATT_BUILT_, 0)
+  return 0;
+}
+#undef CARCA_ATT_BUILT_
 
 namespace {
 constexpr int PACK_CHUNK = 48;  // descriptors per launch (3.5 KB of kernel arguments): a model's forward packs fit one

@@ -280,16 +280,25 @@ __device__ __forceinline__ void attend_head(const f32x4 (&qfrag)[DPI / 16], cons
   }
 }
 
-// (DPI, DHP, H) combinations with a kernel instantiation; anything else is CARCA_ERR_UNSUPPORTED
-#define CARCA_ATT_DISPATCH(FN, ...)                                               \
-  do {                                                                            \
-    if (dpi == 64 && dhp == 16 && H == 4) return FN<64, 16, 4>(__VA_ARGS__);      \
-    if (dpi == 64 && dhp == 32 && H == 2) return FN<64, 32, 2>(__VA_ARGS__);      \
-    if (dpi == 64 && dhp == 64 && H == 1) return FN<64, 64, 1>(__VA_ARGS__);      \
-    if (dpi == 96 && dhp == 32 && H == 3) return FN<96, 32, 3>(__VA_ARGS__);      \
-    if (dpi == 96 && dhp == 48 && H == 2) return FN<96, 48, 2>(__VA_ARGS__);      \
-    if (dpi == 96 && dhp == 96 && H == 1) return FN<96, 96, 1>(__VA_ARGS__);      \
-    if (dpi == 128 && dhp == 32 && H == 4) return FN<128, 32, 4>(__VA_ARGS__);    \
-    if (dpi == 128 && dhp == 64 && H == 2) return FN<128, 64, 2>(__VA_ARGS__);    \
-    if (dpi == 128 && dhp == 128 && H == 1) return FN<128, 128, 1>(__VA_ARGS__);  \
+// (DPI, DHP, H) combinations with a kernel instantiation: the one list behind every CARCA_ATT_DISPATCH and behind
+// carca_attn_geometry_built (api.hip), which the Python side routes on.  X(DPI, DHP, H, ...) per entry; the trailing
+// arguments are passed through to X.
+#define CARCA_ATT_GEOMETRIES(X, ...) \
+  X(64, 16, 4, __VA_ARGS__)          \
+  X(64, 32, 2, __VA_ARGS__)          \
+  X(64, 64, 1, __VA_ARGS__)          \
+  X(96, 32, 3, __VA_ARGS__)          \
+  X(96, 48, 2, __VA_ARGS__)          \
+  X(96, 96, 1, __VA_ARGS__)          \
+  X(128, 32, 4, __VA_ARGS__)         \
+  X(128, 64, 2, __VA_ARGS__)         \
+  X(128, 128, 1, __VA_ARGS__)
+
+// Calls FN<DPI, DHP, H>(...) for the caller's (dpi, dhp, H) and returns its result; falls through (the caller reports
+// CARCA_ERR_UNSUPPORTED) for a combination the list above does not hold.
+#define CARCA_ATT_TRY_(DPI_, DHP_, H_, FN, ...) \
+  if (dpi == DPI_ && dhp == DHP_ && H == H_) return FN<DPI_, DHP_, H_>(__VA_ARGS__);
+#define CARCA_ATT_DISPATCH(FN, ...)                          \
+  do {                                                       \
+    CARCA_ATT_GEOMETRIES(CARCA_ATT_TRY_, FN, __VA_ARGS__)    \
   } while (0)

@@ -7,8 +7,9 @@ buffers the kernels wrote.  Nothing in this file computes model math on the host
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -113,6 +114,22 @@ def padded_dims(d: int, H: int) -> Tuple[int, int, int]:
 
 
 FUSED_MAX_D = 128  # the per-user kernels keep rows of at most this many floats (carca_padded_dims); wider models run composed
+
+
+@functools.lru_cache(maxsize=None)
+def attn_geometry_built(d: int, H: int) -> bool:
+    """Whether the fused attention kernels are instantiated for the (DPI, DHP, H) that (d, H) pads to (CARCA_ATT_GEOMETRIES
+    in csrc/attn_common.h, through carca_attn_geometry_built)."""
+    return bool(_lib.load().carca_attn_geometry_built(int(d), int(H)))
+
+
+def use_composed(d: int, heads: Iterable[int], L: int, n_groups: int = 1) -> bool:
+    """The one routing rule of the modules' forwards: True = long_profile.py's composed row-level path, False = the fused
+    per-user kernels.  Composed when the profile is longer than their MAX_L slots, there are more target groups than one
+    fused call takes, the model is wider than FUSED_MAX_D, or some attention module's (d, H) has no kernel built."""
+    if L > _lib.MAX_L or n_groups > _lib.MAX_GROUPS or d > FUSED_MAX_D:
+        return True
+    return not all(attn_geometry_built(d, H) for H in heads)
 
 
 def row_ld(d: int) -> int:

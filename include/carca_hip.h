@@ -115,6 +115,10 @@ int carca_release_stream_scratch(void* stream);
  * Activations travel between kernels as [rows, DPI] with zeroed pad columns.
  * ---------------------------------------------------------------------------------------- */
 int carca_padded_dims(int d, int H, int* dpi, int* dhp, int* dpo);
+/* 1 if the fused per-user attention kernels (self-attention block, cross-attention scoring and their backward) are built
+ * for the (DPI, DHP, H) that (d, H) pads to, else 0; never an error (0 for d > 128 or d % H != 0).  Models whose
+ * geometry is not built run the composed row-level path instead (long_profile.py). */
+int carca_attn_geometry_built(int d, int H);
 
 /* ---- weight packing -----------------------------------------------------------------------
  * Copies parameter matrices (state_dict layout) into the zero-padded, 16-byte-aligned,

@@ -42,11 +42,12 @@ def _oracle_masks(model, cfg, p, B, L, Ns):
     return mk
 
 
-@pytest.mark.parametrize("p", [0.3, 0.5])
-def test_dropout_forward_backward_match_oracle_with_same_masks(p):
+@pytest.mark.parametrize("p,d,H", [pytest.param(0.3, 90, 3, id="0.3"), pytest.param(0.5, 90, 3, id="0.5"),
+                                   pytest.param(0.3, 128, 1, id="0.3-d128-H1"), pytest.param(0.5, 64, 4, id="0.5-d64-H4")])
+def test_dropout_forward_backward_match_oracle_with_same_masks(p, d, H):
     from carca_replication_amd import modules as M
 
-    cfg, P, profile, pos, neg, y_true, o_x, model = _setup(p)
+    cfg, P, profile, pos, neg, y_true, o_x, model = _setup(p, d=d, H=H)
     B, L = profile[0].shape
     model.train()
     model._keep_dropout_masks = True

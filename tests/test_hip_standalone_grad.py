@@ -47,7 +47,9 @@ def _P64(P):
     return {k: v.double().clone().requires_grad_(v.is_floating_point()) for k, v in P.items()}
 
 
-@pytest.mark.parametrize("d,H,L,B", [(90, 3, 50, 5), (64, 2, 20, 4), (128, 4, 33, 3)])
+# (the last five: <64,16,4> <64,64,1> <96,96,1> <128,64,2> <128,128,1>, the geometries no full-model test trains)
+@pytest.mark.parametrize("d,H,L,B", [(90, 3, 50, 5), (64, 2, 20, 4), (128, 4, 33, 3), (64, 4, 16, 4), (56, 1, 17, 4),
+                                     (96, 1, 64, 3), (100, 2, 48, 3), (128, 1, 1, 3)])
 @pytest.mark.parametrize("residual", [True, False])
 def test_self_attention_block_is_differentiable(d, H, L, B, residual):
     cfg, P, model, mask, gen = _setup(d, H, L, B)
@@ -69,7 +71,10 @@ def test_self_attention_block_is_differentiable(d, H, L, B, residual):
     _check_params("encoder.0.", blk, P64)
 
 
-@pytest.mark.parametrize("d,H,L,N,B", [(90, 3, 50, 101, 4), (64, 2, 20, 7, 5), (128, 4, 33, 1, 3)])
+# (the last five: the same five geometries, with N = 64 / 65 / 128 targets -- cross_attn_bwd stages targets in chunks of 64
+# and accumulates dK / dV over the chunks)
+@pytest.mark.parametrize("d,H,L,N,B", [(90, 3, 50, 101, 4), (64, 2, 20, 7, 5), (128, 4, 33, 1, 3), (64, 4, 16, 64, 4),
+                                       (56, 1, 17, 65, 4), (96, 1, 64, 128, 3), (100, 2, 48, 65, 3), (128, 1, 33, 128, 3)])
 @pytest.mark.parametrize("training", [True, False])
 def test_cross_attention_block_is_differentiable(d, H, L, N, B, training):
     cfg, P, model, p_mask, gen = _setup(d, H, L, B)
