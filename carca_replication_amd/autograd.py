@@ -155,6 +155,7 @@ class _Tail:
 # by the same fill) that are added at the join: the weight-gradient kernels end in a read-modify-write of dW.
 # Off: deterministic mode (its shadow buffer covers the real gradients), sharded steps (the early-gradients event sits
 # inside the one call), the re-associated embedding path, other embeddings / decoders.
+# Round 5 measured three other schedules of this step -- slower or no better -- and removed them (TUNING.md, round 5).
 SPLIT_EMBED_BWD = "graph"  # "graph": while a hipGraph is being captured (engine.GraphedTrainStep) -- an eager step is bound by
                            # its ~40 launches' host time (1.7 ms at C2), which the split's extra launches only add to (eager
                            # steps measured 1.71-2.48 ms with it, 1.79 without); True: always; False: never
@@ -167,39 +168,16 @@ SPLIT_MAIN_TARGET_USERS = 0.25  # share of the FIRST target segment's users left
                                 # -> 1.215 / 1.196 / 1.188 / 1.185 / 1.203 / 1.207 ms per graphed step; round 3: 0 / 0.04 / 0.08
                                 # -> 1.654 / 1.642 / 1.655)
 SPLIT_MIN_GFLOP = 20.0     # the split pays when d feats_embed is long against the launches it doubles (C2: 71 GFLOP per pass)
-SPLIT_TAIL_ON_SIDE = False  # round 5 (MEASURED AND OFF, see below): the weight gradients that feed nothing -- the grouped d x d products of the decoder and the
-                           # blocks, d joint_embed -- leave the FIRST stream's chain: they are issued on the second stream behind
-                           # its big kernel (which ends first), gated by an event behind the encoder's backward; the first
-                           # stream goes from the chain straight into its own rows' embedding backward.  False: round 4's order
-SPLIT_TABLE_STREAM = False  # ... and each stream's row table (wgrad_rowtab_kernel: a function of the ids) built on a third
-                            # stream beside that stream's d [z ; q] / scatter launches instead of between them and the big kernel.
-                            # OFF: with it the C2-sized capture segfaults in hipStreamEndCapture on this runtime (ROCm 7.2; the
-                            # fixture-sized one passes) -- the fork is NESTED, a third stream forked off the second one
-# Interleaved A/B of the graphed C2 step (tools/ab_train_graph.py, round 5): round 4's order 1.1929 ms; tail on the second stream
-# with the first stream's big kernel on 128 CUs and 0.35 / 0.5 / 0.15 of the first target segment's users: 1.1977 / 1.1989 /
-# 1.2109; on 192 CUs: 1.2286; on 256: 1.2193-1.2276.  Two big kernels held to half a chip each for their whole length lose more
-# (the one that ends first leaves its half idle) than the ~110 us of small products gain by leaving the first stream's chain:
-# round 4's order -- second stream's kernel on 128 CUs beside the chain, the first stream's LAST kernel on all 256 -- stays.
-SPLIT_TAIL_MAIN_CUS = 128  # CU budget of the first stream's big kernel under SPLIT_TAIL_ON_SIDE
-SPLIT_TAIL_MAIN_TARGET_USERS = 0.35  # ... and the share of the first target segment's users it takes (SPLIT_MAIN_TARGET_USERS' role)
 _SIDE_STREAMS = {}
-_TABLE_STREAMS = {}
-import os as _os0  # (A/B switches of the captured schedule from the environment: CARCA_SPLIT_TAIL / CARCA_SPLIT_TABLE = 0 | 1)
-
-SPLIT_TAIL_ON_SIDE = {"0": False, "1": True}.get(_os0.environ.get("CARCA_SPLIT_TAIL", ""), SPLIT_TAIL_ON_SIDE)
-SPLIT_TABLE_STREAM = {"0": False, "1": True}.get(_os0.environ.get("CARCA_SPLIT_TABLE", ""), SPLIT_TABLE_STREAM)
 
 
-def ensure_side_streams(device) -> None:
-    """The second / third stream of the captured schedule, created OUTSIDE a capture (engine.GraphedTrainStep calls this before
-    it captures).  Creating them lazily worked while the first use sat in the backward; with the prep fork in the FORWARD a
-    stream created by the capturing thread inside the capture crashed hipStreamEndCapture on this runtime (segfault; the same
-    schedule with the streams created by an eager warm-up step passes)."""
+def ensure_side_streams(device) -> torch.cuda.Stream:
+    """The second stream of the captured schedule, one per device.  engine.GraphedTrainStep calls this before it captures:
+    a stream created by the capturing thread inside the capture has crashed hipStreamEndCapture on this runtime."""
     key = device.index if device.index is not None else torch.cuda.current_device()
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    if key not in _TABLE_STREAMS:
-        _TABLE_STREAMS[key] = torch.cuda.Stream(device=device)
+    return _SIDE_STREAMS[key]
 
 
 class _SideEmbed:
@@ -215,13 +193,7 @@ class _SideEmbed:
             self.tmp[id(q)] = t[: q.numel()].view(q.shape)
         self.gbp = dict(gbp)
         self.gbp.update(self.tmp)
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        if key not in _SIDE_STREAMS:
-            _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-        self.stream = _SIDE_STREAMS[key]
-        if key not in _TABLE_STREAMS:
-            _TABLE_STREAMS[key] = torch.cuda.Stream(device=device)
-        self.table_stream = _TABLE_STREAMS[key].cuda_stream if SPLIT_TABLE_STREAM else None
+        self.stream = ensure_side_streams(device)
         self.cus = ops.num_cus()
 
     @staticmethod
@@ -233,21 +205,11 @@ class _SideEmbed:
         with torch.cuda.stream(self.stream):
             ops.set_tuning(10, min(SPLIT_SIDE_CUS, self.cus))
             try:
-                emb.embed_backward(des, segs, zq, self.gbp, L, dpi, wj_t=wj_t, skip_joint=True, table_stream=self.table_stream)
+                emb.embed_backward(des, segs, zq, self.gbp, L, dpi, wj_t=wj_t, skip_joint=True)
             finally:
                 ops.set_tuning(10, 0)
 
-    def tail(self, fn) -> None:
-        """fn() on the second stream once the FIRST stream has got to where it is now (the end of the encoder's backward)."""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.stream.wait_event(ev)
-        with torch.cuda.stream(self.stream):
-            fn()
-
     def main_cus(self) -> int:
-        if SPLIT_TAIL_ON_SIDE:  # (the second stream still has its tail to run when its big kernel ends: the halves stay halves)
-            return min(SPLIT_TAIL_MAIN_CUS, self.cus)
         if SPLIT_MAIN_CUS > 0:
             return min(SPLIT_MAIN_CUS, self.cus)
         return max(8, self.cus - min(SPLIT_SIDE_CUS, self.cus))
@@ -353,19 +315,6 @@ def _cross_decoder_backward(model, st, ys, dys, gbp, wg, cp, d_wpad):
         st["B"], st["L"], d, H, dec.residual, st["training"], cpd, wg)
 
 
-import os as _os
-
-# MEASURED AND OFF (round 5): graphed C2 step 1.1912 ms with it, 1.1919 without -- the fill and the pack (14 us of kernels) were
-# not on the critical path for long enough to matter, and the fork is one more thing for a capture to go wrong on.
-EARLY_PREP = {"0": False, "1": True, "graph": "graph"}.get(_os.environ.get("CARCA_EARLY_PREP", ""), False)  # the backward's zero fill (gradients + staging) and its pack launch (transposed weight copies) read nothing
-                      # the forward produces: "graph" = while a hipGraph is captured they are issued on the second stream at the
-                      # START of the forward and joined in front of the backward's first kernel (14 us off the step's critical
-                      # path); False = at the start of the backward, as eager steps always do
-
-
-GRAPH_WARMUP = [False]  # set by engine.GraphedTrainStep around its eager warm-up steps
-
-
 def _prepare_backward(model, params, st) -> dict:
     """What _CarcaFn.backward sets up before its first kernel: the pack plan (one launch), the flat gradient buffer (one
     fill), the second stream's buffers."""
@@ -444,32 +393,8 @@ class _CarcaFn(torch.autograd.Function):
             for blk in model.encoder:
                 blk._check_mode()
             dec._check_mode()
-            # EARLY_PREP: what the backward sets up before its first kernel depends on the weights and the ids alone
-            early_box: list = []
-            # ("graph": inside the capture AND in the eager warm-up steps GraphedTrainStep runs right before it -- the first
-            # pass through this fork must not be the captured one: taken for the first time inside a capture it crashed
-            # hipStreamEndCapture on this runtime, taken once eagerly before it the same capture passes)
-            want_early = (GRAPH_WARMUP[0] or torch.cuda.is_current_stream_capturing()) if EARLY_PREP == "graph" else bool(EARLY_PREP)
-
-            def fork_prep():
-                # (forked BEHIND the forward's first launch -- its pack kernel --, not at the very start of a capture: a
-                # stream that waits on an event recorded into a still EMPTY capture crashed hipStreamEndCapture here)
-                key = p_x.device.index if p_x.device.index is not None else torch.cuda.current_device()
-                if key not in _SIDE_STREAMS:
-                    _SIDE_STREAMS[key] = torch.cuda.Stream(device=p_x.device)
-                ps = _SIDE_STREAMS[key]
-                ps.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(ps):
-                    pst = dict(dpi=dpi, B=B, p_x=p_x, segs=segs, emb_saved=None, is_ca=True)
-                    prep = _prepare_backward(model, params, pst)
-                    ev = torch.cuda.Event()
-                    ev.record(ps)
-                early_box.append((prep, ev))
-
-            hook = fork_prep if (want_early and p_x.is_cuda and not ops.deterministic() and ops.early_event is None) else None
             tr: dict = {}
-            ys = model._forward_fused((p_x, p_a, p_c), [sg[:3] for sg in segs[1:]], train=tr, after_pack=hook)
-            early = early_box[0] if early_box else None
+            ys = model._forward_fused((p_x, p_a, p_c), [sg[:3] for sg in segs[1:]], train=tr)
             st = dict(p_x=p_x, segs=segs, es=tr["es"], emb_saved=tr["zq"], blocks=tr["blocks"], enc_out=tr["enc_out"],
                       training=model.training, B=B, L=L, m_embed=tr["m_embed"], p_emb=tr["p_emb"], dpi=dpi, is_ca=True,
                       p_normed=tr["p_normed"], csave=tr["csave"], cw=tr["cw"], keep=tr["keep"], ngroups=len(ys))
@@ -480,9 +405,6 @@ class _CarcaFn(torch.autograd.Function):
             ctx.model = model
             ctx.params = params
             ctx.st = st
-            ctx.prep = ctx.prep_event = None
-            if early is not None:  # (the backward's fill + pack, issued on the second stream before the forward's first kernel)
-                ctx.prep, ctx.prep_event = early
             joint = getattr(ys, "joint", None)
             if joint is not None and len(ys) > 1:
                 # one output tensor [B, sum N] whose column blocks are the groups' scores: autograd then hands the
@@ -553,11 +475,8 @@ class _CarcaFn(torch.autograd.Function):
         p_x = st["p_x"]
         dev = p_x.device
         # every transposed weight copy and every staging area of this pass: one pack launch, one zero fill (shared with
-        # the gradients), one unpack launch -- issued HERE, or already under the forward (EARLY_PREP, _prepare_backward)
-        prep = ctx.prep if getattr(ctx, "prep", None) is not None else _prepare_backward(model, params, st)
-        if getattr(ctx, "prep_event", None) is not None:
-            torch.cuda.current_stream().wait_event(ctx.prep_event)
-        ctx.prep = ctx.prep_event = None
+        # the gradients), one unpack launch
+        prep = _prepare_backward(model, params, st)
         plan, cpk, wpad_idx, bpks, emb_wt_idx = prep["plan"], prep["cpk"], prep["wpad_idx"], prep["bpks"], prep["emb_wt_idx"]
         grads, after_pass, det, gbp, side = prep["grads"], prep["after_pass"], prep["det"], prep["gbp"], prep["side"]
         ys = ctx.saved_tensors
@@ -579,8 +498,7 @@ class _CarcaFn(torch.autograd.Function):
                 segs_all, zq_all = st["segs"], st["emb_saved"]
                 rows0 = segs_all[0][0].numel()
                 side_segs, side_des, main_extra, zq_side = list(segs_all[1:]), list(des_t), None, rows0
-                nb_main = int((SPLIT_TAIL_MAIN_TARGET_USERS if SPLIT_TAIL_ON_SIDE else SPLIT_MAIN_TARGET_USERS) *
-                              segs_all[1][0].shape[0])
+                nb_main = int(SPLIT_MAIN_TARGET_USERS * segs_all[1][0].shape[0])
                 if 0 < nb_main < segs_all[1][0].shape[0] and len(segs_all) + 1 <= ops._lib.MAX_SEGS:
                     # balance: the FIRST users of the first target segment stay with the profile rows (their [z ; q] rows
                     # follow the profile's in the saved buffer: one call, two segments)
@@ -618,32 +536,6 @@ class _CarcaFn(torch.autograd.Function):
         if st["p_emb"] > 0:  # CARCA.dropout on the profile embedding (carca.py:416)
             dx = ops.mask_mul(dx, st["m_embed"], 1.0 / (1.0 - st["p_emb"]), d, dpi)
         des = [dx] + des_t                      # d e per segment, [rows, dpi]; profile rows still unmasked
-        if side is not None and SPLIT_TAIL_ON_SIDE:
-            wj_t = plan.wT.view(emb_wt_idx)
-            m_des, m_segs = [dx], list(st["segs"][:1])
-            if main_extra is not None:
-                m_segs.append(main_extra[0])
-                m_des.append(main_extra[1])
-            all_des, all_segs = m_des + side_des, m_segs + side_segs
-
-            def tail():  # (second stream, behind its big kernel: nothing downstream reads these gradients before the join)
-                wg.launch()
-                plan.unpack(gbp)
-                emb.embed_backward(all_des, all_segs, st["emb_saved"], gbp, L, dpi, wj_t=wj_t, only_joint=True)
-
-            side.tail(tail)
-            ops.set_tuning(10, side.main_cus())
-            try:  # first stream: its own rows' d [z ; q], scatter-add and d feats_embed, straight behind the chain
-                emb.embed_backward(m_des, m_segs, st["emb_saved"], gbp, L, dpi, wj_t=wj_t, skip_joint=True,
-                                   table_stream=side.table_stream)
-            finally:
-                ops.set_tuning(10, 0)
-            side.join(gbp)
-            if det is not None:
-                det.finish()
-            after_pass()
-            ctx.st = None
-            return (None, None, None) + tuple(grads)
         wg.launch()
         if det is not None:  # (the staging areas are about to be READ: their accumulated sums out of the shadow first)
             det.flush_staging()

@@ -548,72 +548,8 @@ int g_num_cus = 0;
 
 }  // namespace
 
-// The row table depends on the ids alone (which rows take part, where their operands start): a caller that has other work to
-// issue first -- carca_embed_bwd: d joint_embed, d [z ; q], the scatter-add -- FORKS a second stream off its own at entry
-// (carca_wgrad_table_fork), the next carca_wgrad_cu_try of this thread launches wgrad_rowtab_kernel THERE (17-26 us of one
-// block's latency chain beside the caller's launches instead of in front of the big kernel) and makes `stream` wait for it;
-// carca_wgrad_table_join closes a fork that no launch used.  Inside a hipGraph capture the two event edges become graph
-// edges.  The table's memory is ordered by `stream`: the fork's event sits behind every earlier launch that read it.
-namespace {
-struct TableFork {
-  hipStream_t ts = nullptr;
-  hipEvent_t ea = nullptr, eb = nullptr;
-  bool open = false;
-};
-thread_local TableFork g_fork;
-}  // namespace
-int carca_wgrad_table_fork(hipStream_t stream, hipStream_t table_stream) {
-  if (!table_stream || table_stream == stream) return CARCA_OK;
-  TableFork& f = g_fork;
-  // (a fresh pair of events per fork, destroyed at the join -- what torch's wait_stream does: an event object recorded a
-  // second time from another stream of the same capture is one more thing this runtime's capture has not been seen to survive)
-  f.ea = f.eb = nullptr;
-  if (hipEventCreateWithFlags(&f.ea, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&f.eb, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    if (f.ea) (void)hipEventDestroy(f.ea);
-    f.ea = f.eb = nullptr;
-    return CARCA_OK;  // (no events: no fork -- the table is built on `stream` as before)
-  }
-  if (hipEventRecord(f.ea, stream) != hipSuccess || hipStreamWaitEvent(table_stream, f.ea, 0) != hipSuccess) {
-    carca_set_error("wgrad_table_fork: cannot fork the row-table stream: %s", hipGetErrorString(hipGetLastError()));
-    return CARCA_ERR_BADARG;
-  }
-  f.ts = table_stream;
-  f.open = true;
-  return CARCA_OK;
-}
-namespace {
-__global__ void table_fork_noop_kernel() {}
-}  // namespace
-int carca_wgrad_table_join(hipStream_t stream, bool used) {
-  TableFork& f = g_fork;
-  if (!f.open) return CARCA_OK;
-  f.open = false;
-  // (a fork nothing was launched on: give the branch a node before it is joined -- see carca_wgrad_cu_suited)
-  if (!used) hipLaunchKernelGGL(table_fork_noop_kernel, dim3(1), dim3(64), 0, f.ts);
-  const bool ok = hipEventRecord(f.eb, f.ts) == hipSuccess && hipStreamWaitEvent(stream, f.eb, 0) == hipSuccess;
-  (void)hipEventDestroy(f.ea);
-  (void)hipEventDestroy(f.eb);
-  f.ea = f.eb = nullptr;
-  if (!ok) {
-    carca_set_error("wgrad_table_join: cannot join the row-table stream: %s", hipGetErrorString(hipGetLastError()));
-    return CARCA_ERR_BADARG;
-  }
-  return CARCA_OK;
-}
-
 // CARCA_OK: launched.  1: shape not suited / operands too large for 31-bit offsets -> caller uses the tiled kernel.
-static int wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream, bool dry);
-int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream) { return wgrad_cu_try(desc, stream, false); }
-// would carca_gemm_wgrad send this product to the persistent kernel?  (no launch, no allocation: carca_embed_bwd asks
-// before it forks a stream for the row table -- a fork that nothing is launched on is an EMPTY branch of a capture, and
-// hipStreamEndCapture of this runtime crashes on one)
-bool carca_wgrad_cu_suited(const CarcaWgradDesc* desc) {
-  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  return variant != 4 && variant != 5 && wgrad_cu_try(desc, nullptr, true) == CARCA_OK;
-}
-static int wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream, bool dry) {
+int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream) {
   WgradCuDev g{};
   g.d = *desc;
   int chunks = 0;
@@ -674,7 +610,6 @@ static int wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream, bool dry
   g.gpx = per_xcd / g.nnb;
   g.ngroups = g.nxcd * g.gpx + (g.nxcd * (per_xcd - g.gpx * g.nnb)) / g.nnb;
   if (g.ngroups < 1) return 1;  // (more n blocks than CUs: the tile kernel)
-  if (dry) return CARCA_OK;
   // (g.ngroups stays the number of groups the chip can HOST; how many of them get units, and which, is the row-table
   // kernel's decision once it has counted the rows that take part: WgPlan)
   g.slow_w = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 13 ? 256 : 264;  // (variant 13: equal item counts -- A/B switch)
@@ -705,12 +640,7 @@ static int wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream, bool dry
     g.plan = (WgPlan*)(aux + cnt_ints - plan_ints);  // (16-byte aligned: everything in front of it is whole 16-byte groups)
     g.part = (float*)(aux + cnt_ints);
   }
-  if (g_fork.open) {  // (the caller forked a stream for the table at its entry: see carca_wgrad_table_fork)
-    hipLaunchKernelGGL(wgrad_rowtab_kernel, dim3(1), dim3(1024), 0, g_fork.ts, g, tab);
-    if (int rc = carca_wgrad_table_join(stream, true)) return rc;
-  } else {
-    hipLaunchKernelGGL(wgrad_rowtab_kernel, dim3(1), dim3(1024), 0, stream, g, tab);
-  }
+  hipLaunchKernelGGL(wgrad_rowtab_kernel, dim3(1), dim3(1024), 0, stream, g, tab);
   g.dbg = carca_debug_buffer();
   if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 3 && g.dbg)
     hipLaunchKernelGGL(gemm_wgrad_cu_kernel<1>, dim3(grid), dim3(WG_NT), 0, stream, g);

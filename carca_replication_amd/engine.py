@@ -219,21 +219,15 @@ class GraphedTrainStep:
         ops.set_dropout_seed_offset(self.replays)
         ops.early_event = self.ev_early
         try:
-            if self.inputs[0].is_cuda:  # (the captured backward's side streams must exist before the capture begins)
+            if self.inputs[0].is_cuda:  # (the captured backward's side stream must exist before the capture begins)
                 from . import autograd
 
                 autograd.ensure_side_streams(self.inputs[0].device)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # lazily built state (code objects, workspaces, descriptor rings) first
-                from . import autograd as _ag
-
-                _ag.GRAPH_WARMUP[0] = True  # (the warm-up steps take the captured pass's prep fork: see autograd.EARLY_PREP)
-                try:
-                    for _ in range(warmup):
-                        _forward_backward(model, optim, self.inputs, self.denom)
-                finally:
-                    _ag.GRAPH_WARMUP[0] = False
+                for _ in range(warmup):
+                    _forward_backward(model, optim, self.inputs, self.denom)
             torch.cuda.current_stream().wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             self.scope = 0

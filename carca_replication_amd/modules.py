@@ -374,8 +374,7 @@ class AllEmbedding(Embedding):
         backward pass packs it in ITS pack launch and hands the view back as embed_backward(..., wj_t=)."""
         return [ops.PackItem(self.joint_embed.weight, self.d + self.feats_embed.weight.shape[0], dpi, transposed=True)]
 
-    def embed_backward(self, des, segs, zq, gbp, L: int, dpi: int, wj_t=None, joint_only=None, skip_joint=False,
-                       only_joint=False, table_stream=None) -> None:
+    def embed_backward(self, des, segs, zq, gbp, L: int, dpi: int, wj_t=None, joint_only=None, skip_joint=False) -> None:
         """Backward of embed_segments (carca.py:85-95): des[i] = d e of segment i, [rows, dpi], NOT yet masked;
         accumulates into the gradient buffers gbp[id(param)].  One host call (carca_embed_bwd): position-encoding
         gradient, d joint_embed, d [z ; q], item-row scatter-add, d feats_embed.  joint_only / skip_joint: see
@@ -401,9 +400,8 @@ class AllEmbedding(Embedding):
                            g_feats_b=gbp[id(self.feats_embed.bias)], g_joint_w=gbp[id(self.joint_embed.weight)],
                            g_joint_b=gbp[id(self.joint_embed.bias)]),
                       table, d, g_feats, n_attrs, n_ctx, L,
-                      # (targets carry no position term; an only_joint call leaves it to the call that owns the profile rows)
-                      gbp[id(enc_w)] if (enc_w is not None and not segs[0][3] and not only_joint) else None,
-                      joint_only=joint_only, skip_joint=skip_joint, only_joint=only_joint, table_stream=table_stream)
+                      gbp[id(enc_w)] if (enc_w is not None and not segs[0][3]) else None,  # (targets carry no position term)
+                      joint_only=joint_only, skip_joint=skip_joint)
 
     def _embed_unmasked(self, x: Tensor, a: Optional[Tensor], c: Tensor, target: bool) -> Tensor:
         """carca.py:86-92 WITHOUT line 94: W_j [sqrt(d) E[x] ; W_f [a;c] + b_f] + b_j (+ position term) for every slot, id 0
@@ -1084,7 +1082,7 @@ class CARCA(_PackedModule, Model):
             return False
         return True
 
-    def _forward_fused(self, profile, targets, events=None, train: Optional[dict] = None, after_pack=None) -> List[Tensor]:
+    def _forward_fused(self, profile, targets, events=None, train: Optional[dict] = None) -> List[Tensor]:
         """One host call for the whole forward (carca_forward).  train: None = inference (workspaces cached per shape);
         a dict = the TRAINING forward: fresh buffers, the backward's saved tensors and the dropout sites, all handed back
         through that dict (the keys autograd._CarcaFn keeps in its state)."""
@@ -1174,8 +1172,6 @@ class CARCA(_PackedModule, Model):
             D.sa_residual[i] = int(bool(blk.residual))
         D.ca = dec.weights_struct(dev, self.norm, repack)
         ops.pack_many(repack)
-        if after_pack is not None:  # (the training forward: a point BEHIND its first launch, ahead of everything else --
-            after_pack()            # where autograd forks the backward's fill + pack onto a second stream)
         D.ca_residual, D.training = int(bool(dec.residual)), int(bool(self.training))
         # the groups' scores are written as column blocks of ONE [B, sum N] tensor: what carca.py:431's torch.cat builds,
         # without the copy (and without the split / re-gather of its gradient in the backward pass)
