@@ -18,7 +18,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
-SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip"]
 HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h"]
 
 MAX_SEGS = 4
@@ -229,6 +229,18 @@ class ForwardDesc(C.Structure):
 
 # name -> (restype, argtypes); every symbol include/carca_hip.h declares
 _i, _f = C.c_int, C.c_float
+class RecommendDesc(C.Structure):
+    """CarcaRecommendDesc (carca_recommend)."""
+    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("H", C.c_int32),
+                ("k", C.c_int32), ("decoder", C.c_int32), ("p_ids", _fp), ("ld_p_ids", C.c_int32), ("item_q", _fp),
+                ("ld_item_q", C.c_int32), ("item_w", _fp), ("ld_item_w", C.c_int32), ("user_k", _fp),
+                ("ld_user_k", C.c_int32), ("user_u", _fp), ("ld_user_u", C.c_int32), ("user_q", _fp),
+                ("ld_user_q", C.c_int32), ("user_m", _fp), ("ld_user_m", C.c_int32), ("user_off", _fp),
+                ("ld_user_off", C.c_int32), ("ffn_b", _fp), ("exclude", _fp), ("n_exclude", C.c_int32),
+                ("ld_exclude", C.c_int32), ("scores", _fp), ("ld_scores", C.c_int32), ("ids_out", _fp),
+                ("ld_ids_out", C.c_int32)]
+
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -305,6 +317,7 @@ SIGNATURES = {
     "carca_concat_ids": (_i, [C.POINTER(_fp), C.POINTER(C.c_int64), _i, _fp, _fp]),
     "carca_build_eval_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                     _fp]),
+    "carca_recommend": (_i, [C.POINTER(RecommendDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

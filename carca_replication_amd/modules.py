@@ -20,6 +20,7 @@ DotProduct / WeightedDotProduct  carca.py:352-399  ops.dot_score_fwd (+ layernor
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from abc import ABC, abstractmethod
 from typing import Iterable, List, Optional, Tuple
@@ -181,6 +182,49 @@ def _rows(x: Tensor) -> int:
     return x.numel()
 
 
+# ---- item-side tables of full-catalogue recommendation (CARCA.recommend) ----------------------
+# In eval mode every embedding is affine in the context: e(i, c) = T[i] + M c for i != 0 (targets carry no position term,
+# carca.py:91).  T = the class's own embed_segments over one target segment ids = arange(n_items) with zero context, M
+# composed from its weights with carca_gemm_rows.  Cached per weight version like every other derived copy (the key of
+# _PackedModule._packed plus the identity of the registered attribute table); kept out of pickles.
+_TABLE_KEYS = ("_item_table_cache", "_ctx_matrix_cache", "_reco_cache")
+
+
+def _cached_table(module: nn.Module, slot: str, params, extra: tuple, build, keep=None):
+    """keep: an object whose id() is part of `extra` (the attribute table): referenced by the cache, so that the id
+    cannot be reused by another tensor while the entry lives."""
+    key = (_WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params) + extra
+    cache = module.__dict__.get(slot)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    value = build()
+    module.__dict__[slot] = (key, value, keep)
+    return value
+
+
+def _need_attr_table(module: nn.Module, what: str) -> Tensor:
+    table = module.attr_table()
+    if table is None:
+        raise CarcaHipError(f"{type(module).__name__}.{what}: no attribute table registered -- call "
+                            "register_attr_table(attrs) with the [n_items, n_attrs] item-attribute matrix first")
+    return table
+
+
+def _target_table(module: nn.Module, n_items: int, a: Optional[Tensor], n_ctx: int, dev) -> Tensor:
+    """T [n_items, row_ld(d)]: embed_segments over ids = arange(n_items) as one target segment, zero context."""
+    x = torch.arange(n_items, dtype=torch.int32, device=dev).view(1, n_items)
+    c = torch.zeros(1, n_items, n_ctx, dtype=torch.float32, device=dev)
+    ld = ops.row_ld(module.d)
+    es, _ = module.embed_segments([(x, a, c, True)], ld_e=ld)
+    return es[0].reshape(n_items, ld)
+
+
+def _drop_tables(state: dict) -> dict:
+    for k in _TABLE_KEYS:
+        state.pop(k, None)
+    return state
+
+
 class AllEmbedding(Embedding):
     def __init__(self, n_items: int, d: int, g: int, n_ctx: int, n_attrs: int, enc: Encoding):
         super().__init__()
@@ -205,7 +249,7 @@ class AllEmbedding(Embedding):
         state.pop("_fold_train", None)
         state.pop("_wf_t", None)
         state.pop("_ztab_cache", None)
-        return state
+        return _drop_tables(state)
 
     def register_attr_table(self, attrs: Optional[Tensor]) -> None:
         """API-compatible extension: keep the item-attribute matrix [n_items, n_attrs] (row 0 = pad,
@@ -261,6 +305,22 @@ class AllEmbedding(Embedding):
 
     def _pos(self, T: int) -> Optional[Tensor]:
         return _position_table(self.enc, T)
+
+    def item_table(self) -> Tensor:
+        """T [n_items, row_ld(d)] = e(i, c = 0) for every item (row 0 = 0): the forward's own embedding of a target row."""
+        table = _need_attr_table(self, "item_table")
+        prm = cached_parameters(self)
+        n_ctx = self.feats_embed.in_features - table.shape[1]
+        return _cached_table(self, "_item_table_cache", prm, (id(table),), lambda: _target_table(
+            self, self.items_embed.num_embeddings, None, n_ctx, self.items_embed.weight.device), keep=table)
+
+    def context_matrix(self, n_ctx: int) -> Optional[Tensor]:
+        """M [d, n_ctx] = W_jq W_f[:, n_attrs:] (e(i, c) = T[i] + M c), or None without context."""
+        if n_ctx == 0:
+            return None
+        F = self.feats_embed.in_features
+        wc, _ = self.folded_weights()
+        return wc[:, F - n_ctx: F]
 
     def bind_split_weights(self, n_attrs: int) -> None:
         """Opt-in split-precision feature GEMM (ops.set_feature_gemm_precision): hand the library the packed 16-bit planes
@@ -490,6 +550,45 @@ class _FeatsEmbedding(Embedding):
         for m in (self.feats_embed, self.joint_embed):
             nn.init.zeros_(m.bias)
 
+    def __getstate__(self):
+        state = dict(super().__getstate__())
+        state.pop("_attr_table", None)
+        return _drop_tables(state)
+
+    def register_attr_table(self, attrs: Optional[Tensor]) -> None:
+        """As AllEmbedding.register_attr_table: the [n_items, n_attrs] item-attribute matrix on the device; afterwards
+        `a` may be None (rows gathered by id).  Pass None to unregister."""
+        if attrs is None:
+            self.__dict__.pop("_attr_table", None)
+            return
+        n_ctx_max = self.feats_embed.in_features
+        if attrs.dim() != 2 or attrs.shape[1] > n_ctx_max:
+            raise CarcaHipError("register_attr_table: expected [n_items, n_attrs] with n_attrs <= feats_embed.in_features")
+        self.__dict__["_attr_table"] = attrs.detach().to(self.feats_embed.weight.device, torch.float32).contiguous()
+
+    def attr_table(self) -> Optional[Tensor]:
+        return self.__dict__.get("_attr_table")
+
+    def item_table(self) -> Tensor:
+        """T [n_items, row_ld(d)] = e(i, c = 0) for every item of the registered attribute table."""
+        table = _need_attr_table(self, "item_table")
+        n_ctx = self.feats_embed.in_features - table.shape[1] if self._use_ctx else 0
+        return _cached_table(self, "_item_table_cache", cached_parameters(self), (id(table),), lambda: _target_table(
+            self, table.shape[0], table.view(1, table.shape[0], table.shape[1]), n_ctx, table.device), keep=table)
+
+    def context_matrix(self, n_ctx: int) -> Optional[Tensor]:
+        """M [d, n_ctx] = W_j W_f[:, n_attrs:] for AttrCtxEmbedding (carca.py:113-114); None for AttrEmbedding."""
+        if n_ctx == 0 or not self._use_ctx:
+            return None
+        Wf, Wj = self.feats_embed.weight, self.joint_embed.weight
+
+        def build():
+            F, g = Wf.shape[1], Wf.shape[0]
+            wf_ctx_t = Wf.detach()[:, F - n_ctx:].t().contiguous()  # [n_ctx, g] (data movement)
+            (m,) = ops.gemm_rows([dict(a0=Wj.detach())], wf_ctx_t, n_ctx, g, (n_ctx + 3) // 4 * 4)
+            return m[:, :n_ctx]
+        return _cached_table(self, "_ctx_matrix_cache", (Wf, Wj), (n_ctx,), build)
+
     def _split(self, segs):
         n_ctx = segs[0][2].shape[-1] if self._use_ctx else 0
         n_attrs = self.feats_embed.in_features - n_ctx
@@ -501,8 +600,17 @@ class _FeatsEmbedding(Embedding):
         n_attrs, n_ctx = self._split(segs)
         g_ld = (g + 3) // 4 * 4
         pos = _segs_pos(self.enc, segs)
-        qs = ops.gemm_rows([dict(a0=a, a1=c if n_ctx else None) for (_, a, c, _) in segs], Wf[:, :n_attrs], g, n_attrs,
-                           g_ld, bt1=Wf[:, n_attrs:] if n_ctx else None, K1=n_ctx, bias=self.feats_embed.bias)
+        table = self.attr_table()
+
+        def src(x, a):  # a None: the rows of the registered attribute table, gathered by id inside the product
+            if a is not None:
+                return dict(a0=a)
+            if table is None:
+                raise CarcaHipError(f"{type(self).__name__}: attrs is None and no attribute table is registered "
+                                    "(register_attr_table)")
+            return dict(a0=table, a0_gather=True, ids=x)
+        qs = ops.gemm_rows([dict(a1=c if n_ctx else None, **src(x, a)) for (x, a, c, _) in segs], Wf[:, :n_attrs], g,
+                           n_attrs, g_ld, bt1=Wf[:, n_attrs:] if n_ctx else None, K1=n_ctx, bias=self.feats_embed.bias)
         es = ops.gemm_rows([dict(a0=qs[i], ids=x, T=x.shape[1], add_pos=(not tgt) and pos is not None)
                             for i, (x, _, _, tgt) in enumerate(segs)], Wj, d, g, ld_e, bias=self.joint_embed.bias,
                            pos=pos, mask_rows=True)
@@ -565,7 +673,15 @@ class IdEmbedding(Embedding):
     def __getstate__(self):
         state = dict(super().__getstate__())
         state.pop("_eye", None)
-        return state
+        return _drop_tables(state)
+
+    def item_table(self) -> Tensor:
+        """T [n_items, row_ld(d)] = sqrt(d) E (row 0 = 0); the embedding ignores context."""
+        E = self.items_embed.weight
+        return _cached_table(self, "_item_table_cache", (E,), (), lambda: _target_table(self, E.shape[0], None, 0, E.device))
+
+    def context_matrix(self, n_ctx: int) -> Optional[Tensor]:
+        return None
 
     def embed_segments(self, segs, ld_e: int):
         d, E = self.d, self.items_embed.weight
@@ -600,6 +716,18 @@ class MLPIdEmbedding(Embedding):
         nn.init.zeros_(self.feats_embed.bias)
         with torch.no_grad():
             self.items_embed.weight[0].zero_()
+
+    def __getstate__(self):
+        return _drop_tables(dict(super().__getstate__()))
+
+    def item_table(self) -> Tensor:
+        """T [n_items, row_ld(d)] = W sqrt(d) E[i] + b for i != 0, row 0 = 0; the embedding ignores context."""
+        E = self.items_embed.weight
+        return _cached_table(self, "_item_table_cache", cached_parameters(self), (),
+                             lambda: _target_table(self, E.shape[0], None, 0, E.device))
+
+    def context_matrix(self, n_ctx: int) -> Optional[Tensor]:
+        return None
 
     def embed_segments(self, segs, ld_e: int):
         d, E, W = self.d, self.items_embed.weight, self.feats_embed.weight
@@ -827,7 +955,7 @@ class _PackedModule:
         state = dict(super().__getstate__())
         for k in ("_pack_cache", "_final_norm_params", "_plan", "_fold_cache", "_param_cache", "_split_cache"):
             state.pop(k, None)
-        return state
+        return _drop_tables(state)
 
 
 class SelfAttentionBlock(_PackedModule, Encoder):
@@ -954,6 +1082,25 @@ class CrossAttentionBlock(_PackedModule, Decoder):
     def drop_p(self) -> float:
         return float(self.attn.dropout.p) if self.training else 0.0
 
+    def recommend_tables(self, T: Tensor):
+        """The scorer's per-item tables over an embedding's item table T (CARCA.recommend): QT = T W_Q^T + b_Q
+        [n_items, row_ld(d)], wT [n_items, 4] with column 0 = w_ffn . T[i] (the residual's item term, carca.py:344-345),
+        and the block-diagonal [H, d] matrix of w_ffn that folds the value projection per head (u_h = w_h . V_h, as
+        CarcaCaWeights.wu / cu).  Composed with carca_gemm_rows, cached per weight version and item table."""
+        a = self.attn
+
+        def build():
+            d, H = a.d, a.H
+            dh = d // H
+            (qt,) = ops.gemm_rows([dict(a0=T)], a.WQ.weight.detach(), d, d, ops.row_ld(d), bias=a.WQ.bias.detach())
+            (wt,) = ops.gemm_rows([dict(a0=T)], self.ffn.weight.detach(), 1, d, 4)
+            wd = torch.zeros(H, d, dtype=torch.float32, device=T.device)
+            w = self.ffn.weight.detach().view(H, dh)
+            for h in range(H):  # (data movement)
+                wd[h, h * dh:(h + 1) * dh] = w[h]
+            return qt, wt, wd
+        return _cached_table(self, "_reco_cache", (a.WQ.weight, a.WQ.bias, self.ffn.weight), (id(T),), build, keep=T)
+
     def forward(self, o: Tensor, o_mask: Tensor, p: Tensor, p_mask: Tensor) -> Tensor:
         """Standalone decoder call: p is already final-normed (as in carca.py:421-428)."""
         self._check_mode()
@@ -1072,6 +1219,118 @@ class CARCA(_PackedModule, Model):
         if isinstance(self.embeds, AllEmbedding):
             self.embeds.__dict__["_fold_train"] = bool(on) and bool(training)
         return self
+
+    # ---- full-catalogue top-k (include/carca_hip.h: carca_recommend) ------------------------
+    def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
+                  exclude="profile") -> Tuple[Tensor, Tensor]:
+        """The k best items of the whole catalogue per user: (scores [B, k] float32, ids [B, k] int64), best first.
+
+        Scores equal what forward(profile, [(ids, attrs, context broadcast)]) returns for those items (eval mode: the
+        candidates do not interact, carca.py:339).  profile = (p_x, p_a, p_c) as for forward (p_a may be None with an
+        attribute table registered); context [B, n_ctx] is the context every candidate carries (data.py:180-185).
+        exclude: "profile" (the profile's items), None, or an int [B, E] tensor of ids (0 = no entry).  Ties go to the
+        smaller id; fewer than k eligible items pad with id 0 and score 0.  Needs model.eval(); L <= 64, a (d, H) with
+        fused kernels built and 1 <= k <= 128.  The item-side tables are built on the first call and cached per weight
+        version (item_table / context_matrix / recommend_tables)."""
+        if self.training:
+            raise CarcaHipError("recommend: the model is in training mode; recommendation scores with eval semantics "
+                                "(call model.eval() first)")
+        self._check_built()
+        if not 1 <= int(k) <= 128:
+            raise CarcaHipError(f"recommend: k = {k} outside 1..128 (the largest k the selection keeps is 128)")
+        p_x, p_a, p_c = profile
+        ops._need_cuda(p_x, p_a, p_c, context)
+        B, L = p_x.shape
+        if L > _lib.MAX_L:
+            raise CarcaHipError(f"recommend: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}")
+        emb, dec = self.embeds, self.decoder
+        d = emb.d
+        bad = [H for H in self._attn_heads() if d > ops.FUSED_MAX_D or not ops.attn_geometry_built(d, H)]
+        if bad:
+            raise CarcaHipError(f"recommend: (d, H) = ({d}, {bad[0]}) has no fused attention kernel built "
+                                "(CARCA_ATT_GEOMETRIES in csrc/attn_common.h)")
+        ca = isinstance(dec, CrossAttentionBlock)
+        if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
+            raise CarcaHipError(f"recommend: decoder {type(dec).__name__} is not covered")
+        n_ctx = context.shape[-1] if context is not None else 0
+        if context is not None and tuple(context.shape) != (B, n_ctx):
+            raise CarcaHipError(f"recommend: context must be [B, n_ctx], got {tuple(context.shape)}")
+        with torch.no_grad():
+            T = emb.item_table()
+            n_items = T.shape[0]
+            M = emb.context_matrix(n_ctx)
+            H = dec.attn.H if ca else self._heads()
+            dpi, _, _ = ops.padded_dims(d, H)
+            ld = ops.row_ld(d)
+            # profile side: the encoder path of forward (embed_segments + the fused blocks + the final LayerNorm)
+            es, _ = emb.embed_segments([(p_x, p_a, p_c, False)], ld_e=dpi)
+            x = es[0]
+            for blk in self.encoder:
+                blk._check_mode()
+                x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
+            p_n = ops.layernorm_fwd(x.reshape(B * L, -1), self.norm.weight, self.norm.bias, d, dpi)
+            mc = None
+            if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
+                (mc,) = ops.gemm_rows([dict(a0=ops._f32(context))], M, d, n_ctx, ld)
+            p_ids = ops._ids32(p_x)
+            D = _lib.RecommendDesc()
+            keep = [T, p_ids, p_n, mc]
+            D.B, D.L, D.n_items, D.d, D.H, D.k = B, L, n_items, d, H, int(k)
+            D.p_ids, D.ld_p_ids = p_ids.data_ptr(), L
+            if ca:
+                qt, wt, wd = dec.recommend_tables(T)
+                a = dec.attn
+                (kk,) = ops.gemm_rows([dict(a0=p_n)], a.WK.weight.detach(), d, d, ld, bias=a.WK.bias.detach())
+                (vv,) = ops.gemm_rows([dict(a0=p_n)], a.WV.weight.detach(), d, d, ld, bias=a.WV.bias.detach())
+                (uu,) = ops.gemm_rows([dict(a0=vv)], wd, H, d, 4)  # u_lh = w_h . V_lh (the decoder FFN folded in)
+                keep += [qt, wt, kk, uu]
+                D.decoder = 0
+                D.item_q, D.ld_item_q = qt.data_ptr(), qt.stride(0)
+                D.user_k, D.ld_user_k, D.user_u, D.ld_user_u = kk.data_ptr(), kk.stride(0), uu.data_ptr(), uu.stride(0)
+                D.ffn_b = dec.ffn.bias.data_ptr()
+                if dec.residual:
+                    D.item_w, D.ld_item_w = wt.data_ptr(), wt.stride(0)
+                if mc is not None:
+                    (dq,) = ops.gemm_rows([dict(a0=mc)], a.WQ.weight.detach(), d, d, ld)  # (M c_u) W_Q^T
+                    keep.append(dq)
+                    D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
+                    if dec.residual:
+                        (off,) = ops.gemm_rows([dict(a0=mc)], dec.ffn.weight.detach(), 1, d, 4)  # w_ffn . M c_u
+                        keep.append(off)
+                        D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
+            else:
+                rows = p_n
+                D.decoder = 1
+                if isinstance(dec, WeightedDotProduct):  # carca.py:385-389
+                    rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi)
+                    if dec.norm:
+                        rows = ops.l2norm_fwd(rows, d, dpi)
+                        D.decoder = 2
+                keep.append(rows)
+                last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
+                D.item_q, D.ld_item_q = T.data_ptr(), T.stride(0)
+                D.user_q, D.ld_user_q = last.data_ptr(), last.stride(0)
+                if mc is not None:
+                    D.user_m, D.ld_user_m = mc.data_ptr(), mc.stride(0)
+            if isinstance(exclude, str):
+                if exclude != "profile":
+                    raise CarcaHipError('recommend: exclude must be "profile", None or an int [B, E] tensor')
+                excl = p_ids
+            elif exclude is None:
+                excl = None
+            else:
+                ops._need_cuda(exclude)
+                if exclude.dim() != 2 or exclude.shape[0] != B or exclude.is_floating_point():
+                    raise CarcaHipError("recommend: exclude must be an int [B, E] tensor")
+                excl = ops._ids32(exclude)
+            if excl is not None and excl.shape[1] > 0:
+                keep.append(excl)
+                D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
+            scores = torch.empty(B, int(k), dtype=torch.float32, device=p_x.device)
+            ids = torch.empty(B, int(k), dtype=torch.int64, device=p_x.device)
+            D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), int(k), ids.data_ptr(), int(k)
+            _lib.check(_lib.load().carca_recommend(C.byref(D), ops._stream()), "recommend")
+        return scores, ids
 
     # ---- inference: one host call per forward (include/carca_hip.h: carca_forward) -----------------------------
     def _fused_ok(self, trace) -> bool:

@@ -101,6 +101,30 @@ def evaluate(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[flo
     return hr / users, ndcg / users, loss_sum / max(n_batches, 1)
 
 
+def evaluate_full(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[float, float]:
+    """(HR@k, NDCG@k) with the positive o_x[:, 0] ranked against EVERY item of the catalogue instead of the loader's
+    sampled negatives (full-ranking protocol; Krichene & Rendle, KDD 2020).  Per batch: CARCA.recommend with the positive's
+    context o_c[:, 0] (data.py:185) and the profile's items minus the positive excluded; the positive's rank is its
+    position in the top-k list (ties: the smaller id first).  Same loaders as evaluate(); one host sync at the end."""
+    model = model.eval().to(device)
+    sums = torch.zeros(3, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for batch in loader:
+            p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
+            pos = o_x[:, :1].to(torch.int64)
+            excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
+            _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl)
+            hit = ids == pos
+            rank = torch.arange(k, device=ids.device, dtype=torch.float32).expand_as(ids)
+            sums[0] += hit.sum()
+            sums[1] += (hit.to(torch.float32) / torch.log2(rank + 2.0)).sum()
+            sums[2] += ids.shape[0]
+    hr, ndcg, users = (float(v) for v in sums.cpu())
+    if torch.device(device).type == "cuda":
+        ops.poll_errors()
+    return hr / max(users, 1.0), ndcg / max(users, 1.0)
+
+
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,

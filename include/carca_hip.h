@@ -748,6 +748,54 @@ int carca_eval_metrics(const float* y /*[B,N]*/, const int32_t* y_true, const in
 int carca_rank_metrics(const float* y /*[B,N]*/, int B, int N, int k, const int32_t* pos /*[B] or NULL*/,
                        int32_t* rank /*[B] or NULL*/, float* sums /*[3]*/, void* stream);
 
+/* ---- full-catalogue top-k (replaces scoring every item as a target group: carca.py:338-349, 352-399 over the candidate
+ * lists of data.py:180-185, ranked as train.py:15-32 does) ------------------------------------------------------------
+ * Eval mode only.  Each embedding is affine in the context, e(i, c) = T[i] + M c for i != 0, so the item side is a table
+ * built once per weight version and the user side a few rows per user.  For user u, item i >= 1:
+ *   decoder 0 (CrossAttentionBlock): logit = sum_h softmax_l((item_q[i]_h . K_ulh + user_q[u]_h . K_ulh) / sqrt(dh)) u_ulh
+ *            + item_w[i] + user_off[u] + ffn_b[0]  over the profile slots l with p_ids != 0 (no slot: attention term 0);
+ *            item_q = QT [n_items, d] (T W_Q^T + b_Q), user_k = K [B*L, d], user_u = folded values [B*L, H]
+ *            (p_l . wu_h + cu_h), user_q = (M c_u) W_Q^T [B, d] or NULL, item_w = w_ffn . T[i] or NULL (no residual),
+ *            user_off [B] or NULL, ffn_b device float[1] or NULL;
+ *   decoder 1 (DotProduct / WeightedDotProduct): logit = user_q[u] . (item_q[i] + user_m[u]), item_q = T, user_q = the
+ *            scored profile row, user_m = M c_u [B, d] or NULL;
+ *   decoder 2 (WeightedDotProduct(normalize=True)): decoder 1's logit / max(||item_q[i] + user_m[u]||, 1e-12).
+ * Writes the k best items per user, best first: ids_out [B, k] int64 and scores = sigmoid(logit) ((logit + 1) / 2 for
+ * decoder 2) -- what the model's forward returns for that item.  Ties go to the smaller id; id 0 and the nonzero entries of
+ * exclude [B, n_exclude] (int32, 0 = no entry, duplicates allowed) are never selected; fewer than k eligible items pad
+ * with id 0 and score 0.  Bit-identical run to run (no float atomics).  Logits of the B x n_items pairs live in stream
+ * scratch.  CARCA_ERR_UNSUPPORTED: L > CARCA_MAX_L, k > 128, d > 128 or d % H != 0, a cross-attention (d, H) with no
+ * kernel built.  CARCA_ERR_BADARG: null pointers, strides shorter than a row, ld_item_q / ld_user_k / ld_user_q /
+ * ld_user_m not multiples of 4. */
+typedef struct CarcaRecommendDesc {
+  int B, L, n_items, d, H, k;
+  int decoder;          /* 0 cross-attention, 1 dot, 2 normalised dot */
+  const int32_t* p_ids; /* [B, ld_p_ids] profile ids */
+  int ld_p_ids;
+  const float* item_q; /* [n_items, ld_item_q] */
+  int ld_item_q;
+  const float* item_w; /* [n_items] with stride ld_item_w, or NULL */
+  int ld_item_w;
+  const float* user_k; /* [B*L, ld_user_k] */
+  int ld_user_k;
+  const float* user_u; /* [B*L, ld_user_u] */
+  int ld_user_u;
+  const float* user_q; /* [B, ld_user_q] (decoder 0: may be NULL) */
+  int ld_user_q;
+  const float* user_m; /* [B, ld_user_m] or NULL */
+  int ld_user_m;
+  const float* user_off; /* [B] with stride ld_user_off, or NULL */
+  int ld_user_off;
+  const float* ffn_b; /* float[1] or NULL */
+  const int32_t* exclude; /* [B, ld_exclude], first n_exclude columns read */
+  int n_exclude, ld_exclude;
+  float* scores; /* [B, ld_scores] */
+  int ld_scores;
+  int64_t* ids_out; /* [B, ld_ids_out] */
+  int ld_ids_out;
+} CarcaRecommendDesc;
+int carca_recommend(const CarcaRecommendDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
