@@ -18,8 +18,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
-SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip"]
-HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip"]
+HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -241,6 +241,18 @@ class RecommendDesc(C.Structure):
                 ("ld_ids_out", C.c_int32)]
 
 
+class RankDesc(C.Structure):
+    """CarcaRankDesc (carca_rank_items)."""
+    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("H", C.c_int32),
+                ("decoder", C.c_int32), ("p_ids", _fp), ("ld_p_ids", C.c_int32), ("item_q", _fp),
+                ("ld_item_q", C.c_int32), ("item_w", _fp), ("ld_item_w", C.c_int32), ("user_k", _fp),
+                ("ld_user_k", C.c_int32), ("user_u", _fp), ("ld_user_u", C.c_int32), ("user_q", _fp),
+                ("ld_user_q", C.c_int32), ("user_m", _fp), ("ld_user_m", C.c_int32), ("user_off", _fp),
+                ("ld_user_off", C.c_int32), ("ffn_b", _fp), ("exclude", _fp), ("n_exclude", C.c_int32),
+                ("ld_exclude", C.c_int32), ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32),
+                ("scores", _fp), ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)]
+
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -318,6 +330,7 @@ SIGNATURES = {
     "carca_build_eval_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                     _fp]),
     "carca_recommend": (_i, [C.POINTER(RecommendDesc), _fp]),
+    "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

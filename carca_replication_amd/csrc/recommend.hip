@@ -14,97 +14,32 @@
 //      then the complemented item id, so ties go to the smaller id), a bitonic sort of the k survivors, and the link
 //      (sigmoid, or (y + 1) / 2) applied to the k selected logits only.
 // Integer LDS atomics only (histograms, slot counters); the result does not depend on scheduling.
-#include "attn_common.h"
+#include "recommend_common.h"
 #include "../../include/carca_hip.h"
 
 namespace {
 
-constexpr int RC_TILE = 256;          // items per scoring workgroup (one per lane)
+constexpr int RC_TILE = rc::TILE;     // items per scoring workgroup (one per lane)
 constexpr int RC_SEL_THREADS = 256;   // selection workgroup
 constexpr int RC_KMAX = 128;          // largest k
 constexpr unsigned RC_SENTINEL = 0xFFFFFFFFu;  // a negative NaN pattern no arithmetic here produces; order key 0
 
-// ---- 1a. cross-attention scoring ----------------------------------------------------------------------------
+// ---- 1a. cross-attention scoring (per-(user, item) arithmetic: recommend_common.h) -------------------------------
 template <int DPI, int DHP, int H>
 __global__ __launch_bounds__(RC_TILE) void rc_score_ca_kernel(CarcaRecommendDesc D, float* __restrict__ logits, int ld_s,
                                                               int users_per_block) {
-  constexpr int DPO = DHP * H;
-  __shared__ float4 Ks4[CARCA_MAX_L * DPO / 4];  // compacted valid profile slots, head-padded
-  __shared__ float Us[CARCA_MAX_L][H];
-  __shared__ float Bs[H][CARCA_MAX_L];
-  __shared__ int slot[CARCA_MAX_L];
-  __shared__ int nvalid;
-  float* Ks = reinterpret_cast<float*>(Ks4);
-  const int tid = threadIdx.x;
-  const int dh = D.d / H;
-  const float sc = 1.4426950408889634f / sqrtf((float)dh);  // log2(e) / sqrt(dh): the softmax runs on exp2
-  const int item = blockIdx.x * RC_TILE + tid;
+  __shared__ rc::CaUser<DHP, H> S;
+  const float sc = rc::ca_scale<H>(D);
+  const int item = blockIdx.x * RC_TILE + threadIdx.x;
   const bool live = item >= 1 && item < D.n_items;
   float q[H][DHP];
-#pragma unroll
-  for (int h = 0; h < H; ++h)
-#pragma unroll
-    for (int c = 0; c < DHP; ++c) q[h][c] = (live && c < dh) ? D.item_q[(size_t)item * D.ld_item_q + h * dh + c] : 0.f;
-  float item_off = 0.f;
-  if (live && D.item_w) item_off = D.item_w[(size_t)item * D.ld_item_w];
+  float item_off;
+  rc::ca_load_item(D, item, live, q, item_off);
   const int u0 = blockIdx.y * users_per_block, u1 = min(D.B, u0 + users_per_block);
   for (int u = u0; u < u1; ++u) {
     __syncthreads();  // the previous user's LDS is read out
-    if (tid < 64) {  // compact the valid slots (leading pad slots and any interior id 0 are skipped)
-      const bool v = tid < D.L && D.p_ids[(size_t)u * D.ld_p_ids + tid] != 0;
-      const unsigned long long m = __ballot(v);
-      if (v) slot[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-      if (tid == 0) nvalid = __popcll(m);
-    }
-    __syncthreads();
-    const int nv = nvalid;
-    for (int idx = tid; idx < nv * DPO; idx += RC_TILE) {
-      const int j = idx / DPO, col = idx % DPO, h = col / DHP, c = col % DHP;
-      Ks[idx] = c < dh ? D.user_k[((size_t)u * D.L + slot[j]) * D.ld_user_k + h * dh + c] : 0.f;
-    }
-    for (int idx = tid; idx < nv * H; idx += RC_TILE) {
-      const int j = idx / H, h = idx % H;
-      Us[j][h] = D.user_u[((size_t)u * D.L + slot[j]) * D.ld_user_u + h];
-    }
-    __syncthreads();
-    for (int idx = tid; idx < nv * H; idx += RC_TILE) {  // beta_hl = (M c_u W_Q^T)_h . K_hl, pre-scaled
-      const int j = idx / H, h = idx % H;
-      float b = 0.f;
-      if (D.user_q) {
-        const float* dq = D.user_q + (size_t)u * D.ld_user_q + h * dh;
-        for (int c = 0; c < dh; ++c) b = fmaf(dq[c], Ks[j * DPO + h * DHP + c], b);
-      }
-      Bs[h][j] = b * sc;
-    }
-    __syncthreads();
-    float logit = item_off;
-    if (D.user_off) logit += D.user_off[(size_t)u * D.ld_user_off];
-    if (D.ffn_b) logit += D.ffn_b[0];
-    if (nv > 0) {  // (a fully masked profile: attention term 0, carca.py:256)
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        float m = -INFINITY, den = 0.f, num = 0.f;
-        for (int j = 0; j < nv; ++j) {
-          const float4* kr = Ks4 + (j * DPO + h * DHP) / 4;
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int c4 = 0; c4 < DHP / 4; ++c4) {
-            const float4 k4 = kr[c4];
-            s0 = fmaf(q[h][4 * c4], k4.x, s0);
-            s1 = fmaf(q[h][4 * c4 + 1], k4.y, s1);
-            s0 = fmaf(q[h][4 * c4 + 2], k4.z, s0);
-            s1 = fmaf(q[h][4 * c4 + 3], k4.w, s1);
-          }
-          const float s = fmaf(s0 + s1, sc, Bs[h][j]);
-          const float mn = fmaxf(m, s);
-          const float a = exp2f(m - mn), e = exp2f(s - mn);
-          den = fmaf(den, a, e);
-          num = fmaf(num, a, e * Us[j][h]);
-          m = mn;
-        }
-        logit += num / den;
-      }
-    }
+    const int nv = rc::ca_stage_user(D, u, sc, S);
+    const float logit = rc::ca_logit(D, u, q, item_off, nv, sc, S);
     if (live) logits[(size_t)u * ld_s + item] = logit;
   }
 }
@@ -120,65 +55,17 @@ int rc_launch_ca(const CarcaRecommendDesc& D, float* logits, int ld_s, dim3 grid
 template <int DPI>
 __global__ __launch_bounds__(RC_TILE) void rc_score_dot_kernel(CarcaRecommendDesc D, float* __restrict__ logits, int ld_s,
                                                                int users_per_block) {
-  __shared__ float4 As4[DPI / 4], Ms4[DPI / 4];
-  __shared__ float am_mm[2];
-  const int tid = threadIdx.x;
-  const int item = blockIdx.x * RC_TILE + tid;
+  __shared__ rc::DotUser<DPI> S;
+  const int item = blockIdx.x * RC_TILE + threadIdx.x;
   const bool live = item >= 1 && item < D.n_items;
-  const bool norm = D.decoder == 2, has_m = D.user_m != nullptr;
   float t[DPI];
-  float tn = 0.f;
-#pragma unroll
-  for (int c = 0; c < DPI; ++c) {
-    t[c] = (live && c < D.d) ? D.item_q[(size_t)item * D.ld_item_q + c] : 0.f;
-    tn = fmaf(t[c], t[c], tn);
-  }
+  float tn;
+  rc::dot_load_item(D, item, live, t, tn);
   const int u0 = blockIdx.y * users_per_block, u1 = min(D.B, u0 + users_per_block);
-  float* As = reinterpret_cast<float*>(As4);
-  float* Ms = reinterpret_cast<float*>(Ms4);
   for (int u = u0; u < u1; ++u) {
     __syncthreads();
-    if (tid < DPI) {
-      As[tid] = tid < D.d ? D.user_q[(size_t)u * D.ld_user_q + tid] : 0.f;
-      Ms[tid] = (has_m && tid < D.d) ? D.user_m[(size_t)u * D.ld_user_m + tid] : 0.f;
-    }
-    if (tid < 64) {  // a_u . m_u and m_u . m_u, once per user
-      float a0 = 0.f, m0 = 0.f;
-      for (int c = tid; c < D.d; c += 64) {
-        const float a = D.user_q[(size_t)u * D.ld_user_q + c];
-        const float mv = has_m ? D.user_m[(size_t)u * D.ld_user_m + c] : 0.f;
-        a0 = fmaf(a, mv, a0);
-        m0 = fmaf(mv, mv, m0);
-      }
-      a0 = wave_sum(a0);
-      m0 = wave_sum(m0);
-      if (tid == 0) am_mm[0] = a0, am_mm[1] = m0;
-    }
-    __syncthreads();
-    float dot0 = 0.f, dot1 = 0.f, tm0 = 0.f, tm1 = 0.f;
-#pragma unroll
-    for (int c4 = 0; c4 < DPI / 4; ++c4) {
-      const float4 a4 = As4[c4];
-      dot0 = fmaf(t[4 * c4], a4.x, dot0);
-      dot1 = fmaf(t[4 * c4 + 1], a4.y, dot1);
-      dot0 = fmaf(t[4 * c4 + 2], a4.z, dot0);
-      dot1 = fmaf(t[4 * c4 + 3], a4.w, dot1);
-    }
-    float y = dot0 + dot1 + am_mm[0];
-    if (norm) {
-      if (has_m) {
-#pragma unroll
-        for (int c4 = 0; c4 < DPI / 4; ++c4) {
-          const float4 m4 = Ms4[c4];
-          tm0 = fmaf(t[4 * c4], m4.x, tm0);
-          tm1 = fmaf(t[4 * c4 + 1], m4.y, tm1);
-          tm0 = fmaf(t[4 * c4 + 2], m4.z, tm0);
-          tm1 = fmaf(t[4 * c4 + 3], m4.w, tm1);
-        }
-      }
-      const float n2 = fmaxf(tn + 2.f * (tm0 + tm1) + am_mm[1], 0.f);
-      y = y / fmaxf(sqrtf(n2), 1e-12f);  // F.normalize(o): o / max(||o||, eps) (carca.py:388-389)
-    }
+    rc::dot_stage_user(D, u, S);
+    const float y = rc::dot_logit(D, t, tn, S);
     if (live) logits[(size_t)u * ld_s + item] = y;
   }
 }
@@ -203,13 +90,6 @@ __global__ __launch_bounds__(64) void rc_exclude_kernel(CarcaRecommendDesc D, fl
 }
 
 // ---- 3. selection ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned rc_order(unsigned bits) {  // float bits -> unsigned with the same order
-  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
-__device__ __forceinline__ float rc_unorder(unsigned o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
 __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(CarcaRecommendDesc D, const float* __restrict__ logits,
                                                                    int ld_s) {
   __shared__ int hist[256];
@@ -226,7 +106,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(CarcaRecommen
     const unsigned long long prefix = s_prefix;
     const int pbits = s_pbits;
     for (int i = tid; i < n; i += RC_SEL_THREADS) {
-      const unsigned o = rc_order(row[i]);
+      const unsigned o = rc::order_bits(row[i]);
       if (o == 0u) continue;  // sentinel: excluded
       const unsigned long long key = ((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
       if (pbits > 0 && (key >> (64 - pbits)) != prefix) continue;
@@ -269,7 +149,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(CarcaRecommen
     const unsigned long long prefix = s_prefix;
     const int pbits = s_pbits;
     for (int i = tid; i < n; i += RC_SEL_THREADS) {
-      const unsigned o = rc_order(row[i]);
+      const unsigned o = rc::order_bits(row[i]);
       if (o == 0u) continue;
       const unsigned long long key = ((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
       if ((key >> (64 - pbits)) >= prefix) {
@@ -298,8 +178,8 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(CarcaRecommen
     if (tid < keff) {
       const unsigned long long key = skey[tid];
       id = (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-      const float y = rc_unorder((unsigned)(key >> 32));
-      score = D.decoder == 2 ? (y + 1.f) * 0.5f : 1.f / (1.f + expf(-y));  // carca.py:346, 367, 395-399
+      const float y = rc::unorder_bits((unsigned)(key >> 32));
+      score = rc::link(y, D.decoder);
     }
     D.scores[(size_t)u * D.ld_scores + tid] = score;
     D.ids_out[(size_t)u * D.ld_ids_out + tid] = id;

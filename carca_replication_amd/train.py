@@ -125,6 +125,67 @@ def evaluate_full(model: Model, loader: DataLoader, device: str, k: int) -> Tupl
     return hr / max(users, 1.0), ndcg / max(users, 1.0)
 
 
+def _rank_sums(ranks: torch.Tensor, ks) -> torch.Tensor:
+    """[hits@k for k in ks, dcg@k for k in ks, sum 1/(rank+1), sum rank, users] (float64, on ranks' device) over the
+    entries of ranks >= 0 (rank -1 marks an id outside the catalogue and counts nowhere)."""
+    r = ranks.reshape(-1).to(torch.float64)
+    valid = r >= 0
+    r = torch.where(valid, r, torch.zeros_like(r))
+    v = valid.to(torch.float64)
+    gain = v / torch.log2(r + 2.0)
+    parts = [(v * (r < k)).sum() for k in ks] + [(gain * (r < k)).sum() for k in ks]
+    parts += [(v / (r + 1.0)).sum(), (v * r).sum(), v.sum()]
+    return torch.stack(parts)
+
+
+def _metrics_from_sums(sums, ks) -> dict:
+    vals = [float(x) for x in sums.cpu()]
+    n = len(ks)
+    users = vals[-1]
+    den = max(users, 1.0)
+    out = {f"HR@{k}": vals[i] / den for i, k in enumerate(ks)}
+    out.update({f"NDCG@{k}": vals[n + i] / den for i, k in enumerate(ks)})
+    out.update(MRR=vals[2 * n] / den, mean_rank=vals[2 * n + 1] / den, users=int(users))
+    return out
+
+
+def full_rank_metrics(ranks: torch.Tensor, ks=(1, 5, 10, 20, 50)) -> dict:
+    """Full-ranking metrics from 0-based ranks (pure torch, any device): HR@k = share of ranks < k, NDCG@k = mean of
+    [rank < k] / log2(rank + 2) (train.py:15-32 with the positive's rank taken over the whole catalogue), MRR = mean of
+    1 / (rank + 1), mean_rank, and users; any k >= 1.  Ranks < 0 (ids outside the catalogue) are left out."""
+    ks = _check_ks(ks)
+    return _metrics_from_sums(_rank_sums(ranks, ks), ks)
+
+
+def _check_ks(ks):
+    ks = tuple(int(k) for k in ks)
+    if not ks or min(ks) < 1:
+        raise ValueError(f"cutoffs must be integers >= 1, got {ks}")
+    return ks
+
+
+def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5, 10, 20, 50)) -> dict:
+    """evaluate_full's protocol -- the positive o_x[:, 0] with its context o_c[:, 0] against every item, the profile's
+    items other than the positive excluded -- in one pass for every cutoff: the positive's exact rank comes from
+    CARCA.rank_items (a count over the catalogue, no top-k list), so any k >= 1 is allowed.  Returns {"HR@k", "NDCG@k"
+    for k in ks, "MRR", "mean_rank", "users"} (full_rank_metrics).  Same loaders as evaluate(); sums stay on the device,
+    one host sync at the end."""
+    ks = _check_ks(ks)
+    model = model.eval().to(device)
+    sums = torch.zeros(2 * len(ks) + 3, dtype=torch.float64, device=device)
+    with torch.no_grad():
+        for batch in loader:
+            p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
+            pos = o_x[:, :1].to(torch.int64)
+            excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
+            _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl)
+            sums += _rank_sums(ranks, ks)
+    out = _metrics_from_sums(sums, ks)
+    if torch.device(device).type == "cuda":
+        ops.poll_errors()
+    return out
+
+
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,

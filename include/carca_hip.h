@@ -796,6 +796,51 @@ typedef struct CarcaRecommendDesc {
 } CarcaRecommendDesc;
 int carca_recommend(const CarcaRecommendDesc* desc, void* stream);
 
+/* ---- exact full-catalogue ranks of listed items (the full-ranking protocol's question, "where does the held-out item
+ * land among all items", without a top-k list) ---------------------------------------------------------------------
+ * The model-side fields (B .. ffn_b) and the exclusion list mean exactly what they mean in CarcaRecommendDesc, and the
+ * logit of a (user, item) pair is bit-identical to carca_recommend's, so the two calls order items identically: logit
+ * descending, ties to the smaller id.  For user u and list entry j, with id = items[u][j]:
+ *   ranks[u][j]  = number of ELIGIBLE items (id != 0, not excluded) that order strictly before id -- the position
+ *                  carca_recommend would give it; an excluded or repeated id still gets the position it would take;
+ *   scores[u][j] = sigmoid(logit) ((logit + 1) / 2 for decoder 2), as carca_recommend's scores;
+ *   id 0 or an id outside [0, n_items): rank -1 and score 0 (never read out of bounds).
+ * Three launches, no host wait, nothing retained: the listed and excluded items are scored; a sweep over the catalogue
+ * counts per (user, target) the items ordering before the target with integer atomics into a zeroed counter (no
+ * [B, n_items] buffer); a correction subtracts the distinct excluded ids that order before it.  Bit-identical run to
+ * run.  Scratch: stream scratch, or the capture's memory.  CARCA_ERR_UNSUPPORTED as carca_recommend, and n_list outside
+ * 1..128.  CARCA_ERR_BADARG as carca_recommend, and null items / scores / ranks or strides shorter than n_list. */
+typedef struct CarcaRankDesc {
+  int B, L, n_items, d, H;
+  int decoder;          /* 0 cross-attention, 1 dot, 2 normalised dot */
+  const int32_t* p_ids; /* [B, ld_p_ids] profile ids */
+  int ld_p_ids;
+  const float* item_q; /* [n_items, ld_item_q] */
+  int ld_item_q;
+  const float* item_w; /* [n_items] with stride ld_item_w, or NULL */
+  int ld_item_w;
+  const float* user_k; /* [B*L, ld_user_k] */
+  int ld_user_k;
+  const float* user_u; /* [B*L, ld_user_u] */
+  int ld_user_u;
+  const float* user_q; /* [B, ld_user_q] (decoder 0: may be NULL) */
+  int ld_user_q;
+  const float* user_m; /* [B, ld_user_m] or NULL */
+  int ld_user_m;
+  const float* user_off; /* [B] with stride ld_user_off, or NULL */
+  int ld_user_off;
+  const float* ffn_b; /* float[1] or NULL */
+  const int32_t* exclude; /* [B, ld_exclude], first n_exclude columns read */
+  int n_exclude, ld_exclude;
+  const int32_t* items; /* [B, ld_items], first n_list columns: the items to rank */
+  int n_list, ld_items;
+  float* scores; /* [B, ld_scores] */
+  int ld_scores;
+  int64_t* ranks; /* [B, ld_ranks] */
+  int ld_ranks;
+} CarcaRankDesc;
+int carca_rank_items(const CarcaRankDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
