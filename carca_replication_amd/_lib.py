@@ -18,8 +18,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
-SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip"]
-HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip"]
+HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -253,6 +253,23 @@ class RankDesc(C.Structure):
                 ("scores", _fp), ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)]
 
 
+_KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_user_a", C.c_int64), ("table", _fp),
+              ("ld_table", C.c_int32), ("table_i8", _fp), ("ld_table_i8", C.c_int32), ("exclude", _fp),
+              ("n_exclude", C.c_int32), ("ld_exclude", C.c_int32)]
+
+
+class KnnRecommendDesc(C.Structure):
+    """CarcaKnnRecommendDesc (carca_knn_recommend)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "n_items", "F", "k")] + _KNN_MODEL +
+                [("scores", _fp), ("ld_scores", C.c_int32), ("ids_out", _fp), ("ld_ids_out", C.c_int32)])
+
+
+class KnnRankDesc(C.Structure):
+    """CarcaKnnRankDesc (carca_knn_rank_items)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "n_items", "F")] + _KNN_MODEL +
+                [("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("scores", _fp),
+                 ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)])
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -331,6 +348,8 @@ SIGNATURES = {
                                     _fp]),
     "carca_recommend": (_i, [C.POINTER(RecommendDesc), _fp]),
     "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
+    "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
+    "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

@@ -1602,7 +1602,8 @@ class CARCA(_PackedModule, Model):
 class KNN(Model):
     """The reference's attribute-similarity baseline: score = attrs(last profile item) . attrs(target), no parameters.
     Extension: register_attr_table(attrs) lets profile/target attribute tensors be None (rows gathered by id on the
-    device), as for AllEmbedding."""
+    device), as for AllEmbedding; with it registered, recommend / rank_items rank the whole catalogue (its rows) as
+    CARCA's methods do."""
 
     def __init__(self):
         super().__init__()
@@ -1610,6 +1611,80 @@ class KNN(Model):
 
     def register_attr_table(self, attrs: Optional[Tensor]) -> None:
         self._attr_table = None if attrs is None else attrs.detach().to(torch.float32).contiguous()
+        self.__dict__.pop("_i8_cache", None)
+
+    def __getstate__(self):
+        state = dict(super().__getstate__())
+        state.pop("_i8_cache", None)
+        return state
+
+    def int8_table(self) -> Optional[Tensor]:
+        """The int8 copy of the registered table that the catalogue scoring runs on (ops.knn_int8_table), or None when
+        the table does not qualify.  Built on first use -- the only host sync -- and cached with the table, keyed on
+        its identity and _version."""
+        table = self._attr_table
+        c = self.__dict__.get("_i8_cache")
+        if c is None or c[0] is not table or c[1] != table._version:
+            c = (table, table._version, ops.knn_int8_table(table))
+            self.__dict__["_i8_cache"] = c
+        return c[2]
+
+    def _catalogue(self, what: str, profile, D, exclude, keep: list, clamp: Optional[int] = None) -> None:
+        if self._attr_table is None:
+            raise CarcaHipError(f"KNN.{what}: no attribute table registered -- call register_attr_table(attrs) with the "
+                                "[n_items, n_attrs] item-attribute matrix first (the catalogue is its rows)")
+        p_x, p_a, _ = profile
+        table = self._attr_table
+        p_ids = ops.knn_catalogue(D, table, None if p_a is not None else self.int8_table(), p_x, p_a, keep)
+        CARCA._catalogue_exclusion(what, exclude, p_ids, D.B, D, keep, clamp=clamp)
+
+    def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None, k: int = 10,
+                  exclude="profile") -> Tuple[Tensor, Tensor]:
+        """The k best items of the catalogue (the rows of the registered attribute table) per user: (scores [B, k]
+        float32, ids [B, k] int64), best first.  The score of item i is forward's, attrs(last profile slot) . table[i]:
+        the last slot's row of p_a when given, else table[p_x[:, -1]] (an id outside the table reads as a zero row).
+        context is ignored (knn.py ignores it).  Order, exclusion ("profile", None or an int [B, E] tensor, 0 = no
+        entry) and padding are CARCA.recommend's: ties go to the smaller id, id 0 is never listed, fewer than k
+        eligible items pad with id 0 and score 0.  1 <= k <= 128; any L; train and eval mode alike."""
+        if not 1 <= int(k) <= 128:
+            raise CarcaHipError(f"recommend: k = {k} outside 1..128 (the largest k the selection keeps is 128)")
+        with torch.no_grad():
+            D, keep = _lib.KnnRecommendDesc(), []
+            self._catalogue("recommend", profile, D, exclude, keep)
+            B, device = D.B, profile[0].device
+            scores = torch.empty(B, int(k), dtype=torch.float32, device=device)
+            ids = torch.empty(B, int(k), dtype=torch.int64, device=device)
+            D.k = int(k)
+            D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), int(k), ids.data_ptr(), int(k)
+            _lib.check(_lib.load().carca_knn_recommend(C.byref(D), ops._stream()), "KNN.recommend")
+        return scores, ids
+
+    def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
+                   exclude="profile") -> Tuple[Tensor, Tensor]:
+        """Exact catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64), as CARCA.rank_items.
+        items: an int32 / int64 [B, N] tensor, 1 <= N <= 128.  ranks[u, j] is the number of eligible items (id != 0,
+        not excluded) before items[u, j] in recommend's order; an excluded or repeated item keeps its position.  Id 0
+        or an id outside [0, n_items) gives rank -1 and score 0.  Scores and the order are bit-identical to
+        recommend's; profile, context and exclude are recommend's."""
+        ops._need_cuda(items)
+        if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
+            raise CarcaHipError("rank_items: items must be an int [B, N] tensor")
+        N = items.shape[1]
+        if not 1 <= N <= 128:
+            raise CarcaHipError(f"rank_items: N = {N} items per user outside 1..128")
+        with torch.no_grad():
+            D, keep = _lib.KnnRankDesc(), []
+            n_items = 0 if self._attr_table is None else self._attr_table.shape[0]
+            self._catalogue("rank_items", profile, D, exclude, keep, clamp=n_items)
+            B, device = D.B, profile[0].device
+            lst = ops._ids32(items if items.dtype == torch.int32 else items.clamp(-1, n_items))
+            keep.append(lst)
+            scores = torch.empty(B, N, dtype=torch.float32, device=device)
+            ranks = torch.empty(B, N, dtype=torch.int64, device=device)
+            D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
+            D.scores, D.ld_scores, D.ranks, D.ld_ranks = scores.data_ptr(), N, ranks.data_ptr(), N
+            _lib.check(_lib.load().carca_knn_rank_items(C.byref(D), ops._stream()), "KNN.rank_items")
+        return scores, ranks
 
     def forward(self, profile: Tuple[Tensor, Tensor, Tensor], targets: List[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
         p_x, p_a, p_c = profile

@@ -103,9 +103,10 @@ def evaluate(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[flo
 
 def evaluate_full(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[float, float]:
     """(HR@k, NDCG@k) with the positive o_x[:, 0] ranked against EVERY item of the catalogue instead of the loader's
-    sampled negatives (full-ranking protocol; Krichene & Rendle, KDD 2020).  Per batch: CARCA.recommend with the positive's
-    context o_c[:, 0] (data.py:185) and the profile's items minus the positive excluded; the positive's rank is its
-    position in the top-k list (ties: the smaller id first).  Same loaders as evaluate(); one host sync at the end."""
+    sampled negatives (full-ranking protocol; Krichene & Rendle, KDD 2020).  Per batch: model.recommend (CARCA.recommend or
+    KNN.recommend) with the positive's context o_c[:, 0] (data.py:185) and the profile's items minus the positive
+    excluded; the positive's rank is its position in the top-k list (ties: the smaller id first).  Same loaders as
+    evaluate(); one host sync at the end."""
     model = model.eval().to(device)
     sums = torch.zeros(3, dtype=torch.float32, device=device)
     with torch.no_grad():
@@ -167,9 +168,9 @@ def _check_ks(ks):
 def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5, 10, 20, 50)) -> dict:
     """evaluate_full's protocol -- the positive o_x[:, 0] with its context o_c[:, 0] against every item, the profile's
     items other than the positive excluded -- in one pass for every cutoff: the positive's exact rank comes from
-    CARCA.rank_items (a count over the catalogue, no top-k list), so any k >= 1 is allowed.  Returns {"HR@k", "NDCG@k"
-    for k in ks, "MRR", "mean_rank", "users"} (full_rank_metrics).  Same loaders as evaluate(); sums stay on the device,
-    one host sync at the end."""
+    model.rank_items (CARCA.rank_items or KNN.rank_items: a count over the catalogue, no top-k list), so any k >= 1 is
+    allowed.  Returns {"HR@k", "NDCG@k" for k in ks, "MRR", "mean_rank", "users"} (full_rank_metrics).  Same loaders as
+    evaluate(); sums stay on the device, one host sync at the end."""
     ks = _check_ks(ks)
     model = model.eval().to(device)
     sums = torch.zeros(2 * len(ks) + 3, dtype=torch.float64, device=device)

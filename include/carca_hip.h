@@ -841,6 +841,72 @@ typedef struct CarcaRankDesc {
 } CarcaRankDesc;
 int carca_rank_items(const CarcaRankDesc* desc, void* stream);
 
+/* ---- KNN baseline: full-catalogue top-k and exact ranks (replace KNN.forward over the catalogue as target groups:
+ * knn.py:13-19 over the candidate lists of data.py:180-185, ranked as train.py:15-32 does) ------
+ * The catalogue is the rows of the attribute table [n_items, ld_table] (fp32, F features).  For user u and item i >= 1:
+ *   logit = q_u . table[i] over the F features, no link (KNN.forward's raw score);
+ *   q_u   = user_a[u] (dense mode: the last profile slot's attribute row, [B, ld_user_a]) when user_a is given, else
+ *           table[p_ids[u][L-1]] (table mode), a zero row when that id is outside [0, n_items).
+ * Scoring is one users x items GEMM in fp32 MFMA (exact fp32 products, fp32 sums).  With table_i8 (table mode only) it
+ * runs in i8 MFMA with i32 sums over that int8 copy of the table, [n_items, ld_table_i8], ld_table_i8 a multiple of 64.
+ * The caller passes it only for a table whose entries are all integers with max|x| <= 127 and max|x|^2 * F < 2^24:
+ * every partial sum is then an exact integer, so both variants give the same bits.  Logits of the B x n_items pairs live
+ * in stream scratch (or the capture's memory); no host wait, nothing retained; bit-identical run to run.
+ * CARCA_ERR_UNSUPPORTED: B > 65535, F > 2^22, k or n_list outside 1..128.  CARCA_ERR_BADARG: null pointers, strides
+ * shorter than a row, ld_table > 2^24, table_i8 with user_a or with a bad ld_table_i8.
+ *
+ * carca_knn_recommend: the k best items per user, best first, in carca_recommend's order (logit descending, ties to the
+ * smaller id): ids_out [B, k] int64 and scores = the logits.  Id 0 and the nonzero entries of exclude [B, n_exclude]
+ * (int32, 0 = no entry, duplicates allowed) are never selected; fewer than k eligible items pad with id 0 and score 0.
+ * Shares carca_recommend's exclusion and selection launches. */
+typedef struct CarcaKnnRecommendDesc {
+  int B, L, n_items, F, k;
+  const int32_t* p_ids; /* [B, ld_p_ids] profile ids (table mode) */
+  int ld_p_ids;
+  const float* user_a; /* [B, ld_user_a] query rows, or NULL (table mode) */
+  int64_t ld_user_a;
+  const float* table; /* [n_items, ld_table] */
+  int ld_table;
+  const int8_t* table_i8; /* [n_items, ld_table_i8] or NULL */
+  int ld_table_i8;
+  const int32_t* exclude; /* [B, ld_exclude], first n_exclude columns read */
+  int n_exclude, ld_exclude;
+  float* scores; /* [B, ld_scores] */
+  int ld_scores;
+  int64_t* ids_out; /* [B, ld_ids_out] */
+  int ld_ids_out;
+} CarcaKnnRecommendDesc;
+int carca_knn_recommend(const CarcaKnnRecommendDesc* desc, void* stream);
+
+/* carca_knn_rank_items: for user u and list entry j, with id = items[u][j]:
+ *   ranks[u][j]  = number of ELIGIBLE items (id != 0, not excluded) that order strictly before id in
+ *                  carca_knn_recommend's order; an excluded or repeated id still gets the position it would take;
+ *   scores[u][j] = the logit, bit-identical to carca_knn_recommend's;
+ *   id 0 or an id outside [0, n_items): rank -1 and score 0 (never read out of bounds).
+ * The model-side fields and the exclusion list are carca_knn_recommend's, and so is the scoring launch; the listed
+ * items' keys are read from its logits, then a sweep counts per (user, target) the items ordering before the target
+ * with integer atomics. */
+typedef struct CarcaKnnRankDesc {
+  int B, L, n_items, F;
+  const int32_t* p_ids;
+  int ld_p_ids;
+  const float* user_a;
+  int64_t ld_user_a;
+  const float* table;
+  int ld_table;
+  const int8_t* table_i8;
+  int ld_table_i8;
+  const int32_t* exclude;
+  int n_exclude, ld_exclude;
+  const int32_t* items; /* [B, ld_items], first n_list columns: the items to rank */
+  int n_list, ld_items;
+  float* scores; /* [B, ld_scores] */
+  int ld_scores;
+  int64_t* ranks; /* [B, ld_ranks] */
+  int ld_ranks;
+} CarcaKnnRankDesc;
+int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
