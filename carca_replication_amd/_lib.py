@@ -18,7 +18,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
-SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
+           "catalogue_xent.hip"]
 HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h"]
 
 MAX_SEGS = 4
@@ -270,6 +271,14 @@ class KnnRankDesc(C.Structure):
                 [("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("scores", _fp),
                  ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)])
 
+class CatalogueXentDesc(C.Structure):
+    """CarcaCatalogueXentDesc (carca_catalogue_xent_fwd / _bwd)."""
+    _fields_ = [("R", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp), ("ld_p", C.c_int32), ("T", _fp),
+                ("ld_t", C.c_int32), ("pos", _fp), ("splits_items", C.c_int32), ("items_per_split", C.c_int32),
+                ("splits_rows", C.c_int32), ("scratch", _fp), ("scratch_floats", C.c_int64), ("lse", _fp),
+                ("row_loss", _fp), ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dT", _fp)]
+
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -350,6 +359,8 @@ SIGNATURES = {
     "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
     "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
+    "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
+    "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

@@ -370,6 +370,24 @@ def _prepare_backward(model, params, st) -> dict:
                 det=det, gbp=gbp, side=side)
 
 
+def _encoder_backward(model, st, dx, gbp, bpks, wg):
+    """The SelfAttentionBlocks' backward, last to first (carca.py:297-318): d of the encoder output -> d of its input."""
+    d, dpi, B, L, p_x = model.embeds.d, st["dpi"], st["B"], st["L"], st["p_x"]
+    for blk, sv, bp in zip(reversed(list(model.encoder)), reversed(st["blocks"]), reversed(bpks)):
+        # one host call per block (carca_sa_block_bwd): seven launches + five products appended to wg
+        x_in = sv["x_in"].view(-1, dpi)
+        g = lambda p: gbp[id(p)]  # noqa: E731
+        dx = ops.sa_block_bwd(
+            dx, p_x, sv, x_in, (bp.wT(0), bp.wT(1), bp.wT(2), bp.wT(3), bp.wT(4)),
+            (blk.norm1.weight.detach(), blk.norm2.weight.detach()),
+            dict(g_w1=g(blk.ffn_1.weight), g_b1=g(blk.ffn_1.bias), g_w2=g(blk.ffn_2.weight), g_b2=g(blk.ffn_2.bias),
+                 g_wq=bp.g(0), g_wk=bp.g(1), g_wv=bp.g(2), g_bq=bp.g(3), g_bk=bp.g(4), g_bv=bp.g(5),
+                 g_ln1_w=g(blk.norm1.weight), g_ln1_b=g(blk.norm1.bias), g_ln2_w=g(blk.norm2.weight),
+                 g_ln2_b=g(blk.norm2.bias)),
+            B, L, d, blk.attn.H, blk.residual, sv["p"], wg)
+    return dx
+
+
 class _CarcaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, profile, targets, *params):
@@ -519,18 +537,7 @@ class _CarcaFn(torch.autograd.Function):
                                    dbeta=gbp[id(model.norm.bias)])
 
         # ---------------- encoder blocks, last to first (carca.py:297-318) --------------------------------
-        for blk, sv, bp in zip(reversed(list(model.encoder)), reversed(st["blocks"]), reversed(bpks)):
-            # one host call per block (carca_sa_block_bwd): seven launches + five products appended to wg
-            x_in = sv["x_in"].view(-1, dpi)
-            g = lambda p: gbp[id(p)]  # noqa: E731
-            dx = ops.sa_block_bwd(
-                dx, p_x, sv, x_in, (bp.wT(0), bp.wT(1), bp.wT(2), bp.wT(3), bp.wT(4)),
-                (blk.norm1.weight.detach(), blk.norm2.weight.detach()),
-                dict(g_w1=g(blk.ffn_1.weight), g_b1=g(blk.ffn_1.bias), g_w2=g(blk.ffn_2.weight), g_b2=g(blk.ffn_2.bias),
-                     g_wq=bp.g(0), g_wk=bp.g(1), g_wv=bp.g(2), g_bq=bp.g(3), g_bk=bp.g(4), g_bv=bp.g(5),
-                     g_ln1_w=g(blk.norm1.weight), g_ln1_b=g(blk.norm1.bias), g_ln2_w=g(blk.norm2.weight),
-                     g_ln2_b=g(blk.norm2.bias)),
-                B, L, d, blk.attn.H, blk.residual, sv["p"], wg)
+        dx = _encoder_backward(model, st, dx, gbp, bpks, wg)
 
         # ---------------- embedding (carca.py:85-95 and its ablations) -------------------------------------
         if st["p_emb"] > 0:  # CARCA.dropout on the profile embedding (carca.py:416)

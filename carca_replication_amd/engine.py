@@ -11,6 +11,7 @@ import torch
 
 from . import dist as cdist
 from . import ops
+from ._lib import CarcaHipError
 from .modules import BinaryCrossEntropy, get_mask, note_training_forward
 
 _loss_fn = BinaryCrossEntropy()
@@ -54,8 +55,17 @@ def _row_exchange_len(p_x, o_x, global_batch: Optional[int]) -> Optional[int]:
     return per_rank * (p_x.shape[1] + o_x.shape[1])
 
 
-def train_step(model, optim, batch, sharded: bool = False, global_batch: Optional[int] = None) -> torch.Tensor:
+LOSSES = ("bce", "softmax")
+
+
+def train_step(model, optim, batch, sharded: bool = False, global_batch: Optional[int] = None,
+               loss: str = "bce") -> torch.Tensor:
     """batch = (p_x, p_a, p_c, o_x, o_a, o_c, y_true) as the reference's DataLoader yields (train.py:84).
+
+    loss: "bce" = the reference's objective (carca.py:441-444, one sampled negative per position); "softmax" = full-
+    catalogue softmax cross-entropy of the positive half (CARCA.catalogue_softmax_loss): the
+    negatives and y_true are not read, and every item row gets a gradient, so the optimizer is not told the batch's rows
+    (a touched-row Adam table then steps densely).  Not built for sharded steps.
 
     With sharded=True the batch holds THIS rank's users; the loss is normalised by the global mask
     count and gradients are summed over ranks, which reproduces the single-process step exactly.
@@ -63,7 +73,13 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
     big item table size its row exchange without a host sync (dist.allgather_row_gradients).
     Returns the (device) loss: the global batch loss's local share when sharded.
     """
+    if loss not in LOSSES:
+        raise ValueError(f"train_step: loss must be one of {LOSSES}, got {loss!r}")
     batch = as_batch7(batch)
+    if loss == "softmax":
+        if sharded:
+            raise CarcaHipError('train_step: loss="softmax" is not built for sharded steps')
+        return _softmax_step(model, optim, batch)
     p_x, o_x = batch[0], batch[3]
     gathered = None
     if not (sharded and cdist._active()):
@@ -148,6 +164,16 @@ def _mark_touched_rows(model, optim, p_x, o_x, gathered: Optional[dict] = None) 
         if gathered and gathered.get(id(w)) is not None:
             ids = gathered[id(w)]
         optim.mark_rows(w, ids)
+
+
+def _softmax_step(model, optim, batch) -> torch.Tensor:
+    p_x, p_a, p_c, o_x = batch[:4]
+    pos = o_x[:, : o_x.shape[1] // 2]  # train.py:86-88: the positive half
+    optim.zero_grad(set_to_none=True)
+    loss = model.catalogue_softmax_loss((p_x, p_a, p_c), pos)
+    loss.backward()
+    optim.step()  # (no mark_rows: every row of the item table has a gradient)
+    return loss.detach()
 
 
 def _forward_backward(model, optim, batch, denom: Optional[torch.Tensor]) -> torch.Tensor:

@@ -1220,6 +1220,16 @@ class CARCA(_PackedModule, Model):
             self.embeds.__dict__["_fold_train"] = bool(on) and bool(training)
         return self
 
+    def catalogue_softmax_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor) -> Tensor:
+        """Full-catalogue softmax cross-entropy of a training batch: profile = (p_x, p_a, p_c) as
+        forward takes it, pos = o_x[:, :L] (the positive half of the batch).  Scalar mean over the valid slots (pos in
+        [1, n_items)) of logsumexp over every item i >= 1 of the dot decoder's logit minus the positive's logit;
+        differentiable in every parameter.  Dot decoders only (WeightedDotProduct without normalisation); attribute-reading
+        embeddings need register_attr_table.  Dropout follows self.training, at the sites and with the masks of forward."""
+        from .catalogue_xent import catalogue_softmax_loss
+
+        return catalogue_softmax_loss(self, profile, pos)
+
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items; DESIGN.md 10, 11) -
     def _catalogue_user_side(self, what: str, profile, context: Optional[Tensor], D) -> list:
         """Checks the envelope of recommend / rank_items and fills the model-side fields of D (RecommendDesc or RankDesc:

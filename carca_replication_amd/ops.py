@@ -1345,3 +1345,124 @@ def split_bind(w: Optional[Tensor], planes: Optional[Tensor], mode: int = 0, K0:
         _lib.check(lib.carca_split_bind(None, None, 0, 0, 0), "split_bind")
     else:
         _lib.check(lib.carca_split_bind(w.data_ptr(), planes.data_ptr(), int(mode), w.shape[0], int(K0)), "split_bind")
+
+
+# --------------------------------------------------------------------------------------------------
+# full-catalogue softmax cross-entropy (carca_catalogue_xent_fwd / _bwd)
+# --------------------------------------------------------------------------------------------------
+CX_TILE = 64        # rows of a workgroup's own tile and of each streamed tile (csrc/catalogue_xent.hip)
+CX_MAX_SPLITS = 256
+CX_WAVES_PER_CU = 4  # the split counts aim at this many workgroups per CU
+
+
+def catalogue_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_catalogue_xent_fwd / _bwd (pure: no device).  The item range is split so that the
+    forward's and dP's (row block x item split) grid has about CX_WAVES_PER_CU workgroups per CU, the rows of dT's
+    (item block x row split) grid likewise.  Returns the split counts and the scratch each call needs, in 4-byte words
+    (the layout csrc/catalogue_xent.hip checks): 2 ceil64(R) + 64 words of row lists, then the forward's (max, sum-exp)
+    partials, or the backward's dP partials [splits_items, R, ld] and, with more than one row split, dT partials
+    [splits_rows, n_items, ld], ld = round_up(d, 4)."""
+    if R < 1 or n_items < 1 or d < 1:
+        raise CarcaHipError("catalogue_xent_plan: R, n_items and d must be positive")
+    r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
+    ldo = (d + 3) // 4 * 4
+    target = CX_WAVES_PER_CU * max(1, int(n_cus))
+    n_row_blocks = -(-R // CX_TILE)
+    n_item_blocks = -(-n_items // CX_TILE)
+    s_i = max(1, min(n_item_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
+    per = -(-n_item_blocks // s_i) * CX_TILE
+    s_i = -(-n_items // per)  # (no empty split)
+    s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_item_blocks)))
+    head = 2 * r64(R) + 64
+    fwd = head + 2 * r64(s_i * R)
+    bwd = head + r64(s_i * R * ldo) + (r64(s_r * n_items * ldo) if s_r > 1 else 0)
+    return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+
+
+def _xent_operand(x: Tensor, d: int) -> Tensor:
+    """x [rows, >= d] fp32 as the kernels take it: unit column stride, row stride a multiple of 4, 16-byte aligned;
+    anything else is copied into [rows, round_up(d, 4)] with zeros past d."""
+    if x.dtype != torch.float32:
+        raise CarcaHipError(f"catalogue_xent: expected float32, got {x.dtype}")
+    if x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= d and x.data_ptr() % 16 == 0:
+        return x
+    out = x.new_zeros(x.shape[0], (d + 3) // 4 * 4)
+    out[:, :d] = x[:, :d]
+    return out
+
+
+def _xent_desc(P: Tensor, T: Tensor, pos: Tensor, d: int, scratch_key: str, plan: dict, keep: list):
+    D = _lib.CatalogueXentDesc()
+    D.R, D.n_items, D.d = P.shape[0], T.shape[0], d
+    D.P, D.ld_p, D.T, D.ld_t, D.pos = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0), pos.data_ptr()
+    D.splits_items, D.items_per_split, D.splits_rows = plan["splits_items"], plan["items_per_split"], plan["splits_rows"]
+    # scratch through torch's caching allocator (max_memory_allocated sees it); freed when the call returns
+    scratch = torch.empty(plan[scratch_key], dtype=torch.float32, device=P.device)
+    keep.append(scratch)
+    D.scratch, D.scratch_floats = scratch.data_ptr(), scratch.numel()
+    return D
+
+
+def catalogue_xent_fwd(P: Tensor, T: Tensor, pos: Tensor, d: int) -> Tuple[Tensor, Tensor]:
+    """Mean full-catalogue softmax cross-entropy of rows P [R, ld_p] against items T [n_items, ld_t] (first d columns,
+    strides multiples of 4), targets pos [R] int32 (rows whose pos is outside [1, n_items) are padding).
+    Returns (loss [1], lse [R]); no host wait."""
+    _need_cuda(P, T, pos)
+    plan = catalogue_xent_plan(P.shape[0], T.shape[0], d, num_cus())
+    keep: list = []
+    D = _xent_desc(P, T, pos, d, "scratch_fwd", plan, keep)
+    lse = torch.empty(P.shape[0], dtype=torch.float32, device=P.device)
+    row_loss = torch.empty_like(lse)
+    loss = torch.empty(1, dtype=torch.float32, device=P.device)
+    D.lse, D.row_loss, D.loss = lse.data_ptr(), row_loss.data_ptr(), loss.data_ptr()
+    _lib.check(_lib.load().carca_catalogue_xent_fwd(C.byref(D), _stream()), "catalogue_xent_fwd")
+    return loss, lse
+
+
+def catalogue_xent_bwd(P: Tensor, T: Tensor, pos: Tensor, lse: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor]:
+    """(dP [R, ld_p], dT [n_items, ld_t]) of catalogue_xent_fwd's loss scaled by grad [1] (device); zeros past d."""
+    _need_cuda(P, T, pos, lse, grad)
+    plan = catalogue_xent_plan(P.shape[0], T.shape[0], d, num_cus())
+    keep: list = []
+    D = _xent_desc(P, T, pos, d, "scratch_bwd", plan, keep)
+    g = _f32(grad.reshape(1))
+    dP = torch.empty(P.shape[0], P.stride(0), dtype=torch.float32, device=P.device)
+    dT = torch.empty(T.shape[0], T.stride(0), dtype=torch.float32, device=P.device)
+    D.lse, D.grad, D.dP, D.dT = lse.data_ptr(), g.data_ptr(), dP.data_ptr(), dT.data_ptr()
+    _lib.check(_lib.load().carca_catalogue_xent_bwd(C.byref(D), _stream()), "catalogue_xent_bwd")
+    return dP, dT
+
+
+class _CatalogueXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, T, pos):
+        d = P.shape[1]
+        P2, T2 = _xent_operand(P.detach(), d), _xent_operand(T.detach(), d)
+        pos32 = _ids32(pos.reshape(-1))
+        loss, lse = catalogue_xent_fwd(P2, T2, pos32, d)
+        ctx.save_for_backward(P2, T2, pos32, lse)
+        ctx.d = d
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        P2, T2, pos32, lse = ctx.saved_tensors
+        d = ctx.d
+        dP, dT = catalogue_xent_bwd(P2, T2, pos32, lse, g.detach(), d)
+        return dP[:, :d], dT[:, :d], None
+
+
+def catalogue_xent(P: Tensor, T: Tensor, pos: Tensor) -> Tensor:
+    """Mean softmax cross-entropy over the whole catalogue, differentiable in P and T:
+
+        sum over valid r of ( logsumexp_{i = 1 .. n_items-1} P[r] . T[i] - P[r] . T[pos[r]] ) / n_valid
+
+    P [R, d] fp32, T [n_items, d] fp32, pos [R] integer; row r is valid iff pos[r] lies in [1, n_items), id 0 is never a
+    class, a batch without a valid row gives 0.  Fused HIP kernels: no [R, n_items] logit buffer in either pass."""
+    _need_cuda(P, T, pos)
+    if P.dim() != 2 or T.dim() != 2 or P.shape[1] != T.shape[1] or pos.numel() != P.shape[0]:
+        raise CarcaHipError(f"catalogue_xent: expected P [R, d], T [n_items, d], pos [R]; got {tuple(P.shape)}, "
+                            f"{tuple(T.shape)}, {tuple(pos.shape)}")
+    if pos.is_floating_point():
+        raise CarcaHipError("catalogue_xent: pos must be an integer tensor")
+    return _CatalogueXentFn.apply(P, T, pos)

@@ -907,6 +907,42 @@ typedef struct CarcaKnnRankDesc {
 } CarcaKnnRankDesc;
 int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream);
 
+/* ---- full-catalogue softmax cross-entropy for the dot decoders ------------------------------
+ * P [R, ld_p] profile rows, T [n_items, ld_t] catalogue rows (d features; ld_p, ld_t multiples of 4, bases 16-byte
+ * aligned), pos [R] int32.  Row r is VALID iff pos[r] lies in [1, n_items); id 0 is never a class.
+ *   carca_catalogue_xent_fwd: lse[r] = log sum_{i=1..n_items-1} exp(P[r] . T[i]), row_loss[r] = lse[r] - P[r] . T[pos[r]]
+ *     (both 0 for a row that is not valid), loss[0] = sum of row_loss / n_valid (0 when no row is valid);
+ *   carca_catalogue_xent_bwd: with lse from the forward and the upstream scale grad[0], G = softmax - onehot(pos):
+ *     dP = grad / n_valid * G T  (0 for rows that are not valid and for the columns past d),
+ *     dT = grad / n_valid * G^T P (row 0 and the columns past d: 0).
+ * Products in exact-fp32 MFMA; the logit tiles are recomputed, never stored.  n_valid and the list of valid rows are
+ * found on the device (no host wait).  The item range is split over splits_items workgroup columns of items_per_split
+ * items (a multiple of 64); the backward's dT splits the valid rows over splits_rows.  Scratch (scratch_floats 4-byte
+ * words, caller-allocated; ops.catalogue_xent_plan gives the size): 2 ceil64(R) + 64 words of row lists, then the
+ * forward's 2 ceil64(splits_items R) (max, sum-exp) partials, or the backward's ceil64(splits_items R ld) dP partials and,
+ * with splits_rows > 1, ceil64(splits_rows n_items ld) dT partials, ld = round_up(d, 4).  No float atomics: the same call
+ * gives the same bits.  CARCA_ERR_UNSUPPORTED: d > 256.  CARCA_ERR_BADARG: null pointers, strides, split counts outside
+ * 1..256, items_per_split * splits_items < n_items, scratch too small. */
+typedef struct CarcaCatalogueXentDesc {
+  int R, n_items, d;
+  const float* P;
+  int ld_p;
+  const float* T;
+  int ld_t;
+  const int32_t* pos;
+  int splits_items, items_per_split, splits_rows;
+  float* scratch;
+  int64_t scratch_floats;
+  float* lse;      /* [R]: forward output, backward input */
+  float* row_loss; /* [R] forward */
+  float* loss;     /* [1] forward */
+  const float* grad; /* [1] backward: upstream scale of loss */
+  float* dP;       /* [R, ld_p] backward */
+  float* dT;       /* [n_items, ld_t] backward */
+} CarcaCatalogueXentDesc;
+int carca_catalogue_xent_fwd(const CarcaCatalogueXentDesc* desc, void* stream);
+int carca_catalogue_xent_bwd(const CarcaCatalogueXentDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
