@@ -487,9 +487,12 @@ extern "C" int carca_forward(const CarcaForwardDesc* D, void* const* ev, void* s
     if (ev && ev[0] && ev[1]) carca_arm_launch_events(ev[0], ev[1]);
     // (z_table: the item term comes out of the projected table in the joint product's epilogue -- no gather at all)
     const bool ztab = D->z_table != nullptr && !D->save_blocks && !D->save_cross;
+    // (evaluation -- nothing saved for a backward pass, no dropout: the feature product over distinct attribute rows)
+    const bool eval = !D->training && !D->save_blocks && !D->save_cross && !(D->p_embed > 0.f);
     rc = carca_embed_fwd(D->segs, nseg, D->n_attrs, D->n_ctx, D->d, D->g, D->items_w, D->feats_w, D->feats_b,
                          D->joint_w, D->joint_b, D->pos, D->zq, D->ld_e,
-                         ztab ? CARCA_EMBED_FEAT : (CARCA_EMBED_GATHER | CARCA_EMBED_FEAT), stream_);
+                         (ztab ? CARCA_EMBED_FEAT : (CARCA_EMBED_GATHER | CARCA_EMBED_FEAT)) | (eval ? CARCA_EMBED_DEDUP : 0),
+                         stream_);
     hipEvent_t left0, left1;
     if (carca_take_launch_events(&left0, &left1) && rc == CARCA_OK) {
       carca_set_error("forward: the feature GEMM's launch did not take the timing events");

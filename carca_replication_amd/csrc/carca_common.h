@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/carca_hip.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 // 16-byte vector with 4-byte alignment: hipcc still emits global_load_dwordx4 for it
@@ -220,7 +222,7 @@ __device__ __forceinline__ void carca_warm_kernargs() {
 enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRAD_SLOTS = 2, CARCA_TUNE_DETERMINISTIC = 8,
        CARCA_TUNE_STAMPS = 9, CARCA_TUNE_CU_CAP = 10, CARCA_TUNE_SK_DON = 11, CARCA_TUNE_SK_SPIN_LOG2 = 12,
        CARCA_TUNE_SK_WITHHOLD = 13, CARCA_TUNE_XS_OPT = 14, CARCA_TUNE_DIAG = 15, CARCA_TUNE_SPLIT_GEMM = 16,
-       CARCA_TUNE_COUNT = 24 };
+       CARCA_TUNE_FEAT_DEDUP = 20, CARCA_TUNE_COUNT = 24 };
 int carca_tuning(int key);
 int carca_num_cus();  // compute units of the current device (cached)
 // True while `stream` is being captured into a hipGraph.
@@ -236,7 +238,7 @@ bool carca_stream_capturing(hipStream_t stream);
 void* carca_stream_scratch(hipStream_t stream, int tag, size_t bytes, size_t zero_bytes = 0, bool* fresh = nullptr);
 enum { CARCA_SCRATCH_SK = 1, CARCA_SCRATCH_WPART = 2, CARCA_SCRATCH_WTAB = 3, CARCA_SCRATCH_SPLITW = 4, CARCA_SCRATCH_SKC = 5,
        CARCA_SCRATCH_SKC_PART = 6, CARCA_SCRATCH_RECOMMEND = 7, CARCA_SCRATCH_RANK = 8,
-       CARCA_SCRATCH_KNN = 9 };
+       CARCA_SCRATCH_KNN = 9, CARCA_SCRATCH_DEDUP_HASH = 10, CARCA_SCRATCH_DEDUP = 11 };
 void* carca_capture_alloc(hipStream_t stream, size_t bytes, bool host_mapped, void** device_view, size_t zero_bytes = 0);
 // Timing events for this thread's NEXT row-GEMM launch (the roofline hooks of carca_forward): the launch binds them to
 // its own dispatch packet (hipExtLaunchKernel), so elapsed(start, stop) is the kernel's duration and no barrier packet
@@ -256,6 +258,27 @@ int carca_gemm_rows_n96s_try(const CarcaGemmDesc* desc, bool fits32, hipStream_t
 // carca_gemm_rows with the item-row gather riding along where the kernel choice leaves a CU idle; *rode tells whether
 // it did (otherwise the caller launches the gather itself)
 int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* ga, int* rode, void* stream);
+// The evaluation feature product over distinct attribute rows (feat_dedup.hip, gemm.hip: carca_gemm_rows_feat_dedup).
+// One launch's state: the product's descriptor, the rows of all segments laid end to end (segment s from row0[s]), the
+// id table (key / val: 2^hbits slots, zero between launches), per row its slot (the table slot it owns, else -1), its
+// representative row (-1: id 0) and its flag (1: a representative -- what gemm_rows_skc_kernel plans from), and P
+// [R, ldp] (written at the representatives' rows).
+struct CarcaDedupRun {
+  CarcaGemmDesc d;
+  int nseg, R, vec, hbits;
+  int row0[CARCA_MAX_SEGS + 1];
+  unsigned hmask;
+  int* key;
+  unsigned* val;
+  int *slot, *rep, *flag;
+  float* P;
+  int ldp;
+};
+// 1 = not this product's path (nothing launched), CARCA_OK with *run filled, or an error
+int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, CarcaDedupRun* run);
+int carca_feat_dedup_plan(const CarcaDedupRun* run, hipStream_t stream, hipEvent_t start);
+int carca_feat_dedup_expand(const CarcaDedupRun* run, hipStream_t stream, hipEvent_t stop);
+int carca_gemm_rows_feat_dedup(const CarcaGemmDesc* desc, void* stream);
 // host-visible word a kernel sets when it meets something no launch status can carry (1: a stream-K taker gave up waiting,
 // 2: gemm_rows_skc_kernel's row-block lists too short, 3: gemm_wgrad_cu_kernel's partial-tile slots too few); reported and
 // cleared by carca_poll_errors and by the next stream-K launch (gemm.hip).  Device view, or null.

@@ -82,7 +82,14 @@ extern "C" int carca_embed_fwd(const CarcaRowSeg* segs, int nseg, int n_attrs, i
   // q of a padding slot (id 0) is never used -- e is masked (carca.py:92-94), the backward sees de = 0 there --, so the
   // product may leave those rows out (gemm_rows_skc_kernel) and write zeros instead
   fa.mask_rows = 1;
-  if ((stages & CARCA_EMBED_GATHER) && (stages & CARCA_EMBED_FEAT)) {
+  if ((stages & CARCA_EMBED_FEAT) && (stages & CARCA_EMBED_DEDUP)) {
+    // evaluation: the product over one representative per group of equal attribute rows (feat_dedup.hip); the gather
+    // keeps its own launch
+    const int rc = carca_gemm_rows_feat_dedup(&fa, stream_);
+    if (rc != CARCA_OK) return rc;
+    if (stages & CARCA_EMBED_GATHER)
+      if (int rc2 = launch_gather()) return rc2;
+  } else if ((stages & CARCA_EMBED_GATHER) && (stages & CARCA_EMBED_FEAT)) {
     // both asked for in one call: the gather rides in the feature GEMM's launch when that leaves a CU idle
     int rode = 0;
     const int rc = carca_gemm_rows_passenger(&fa, &ga, &rode, stream_);  // q = [attrs ; ctx] W_f^T + b_f  (carca.py:86)

@@ -75,6 +75,10 @@ struct GemmDev {
   int skc_cheap;     // gemm_rows_skc_kernel: cost of a K step of the narrow column block's tile in 1/100 of a full tile's step
   int skc_ov, skc_ov_lone;  // ... and what OWNING a row block costs (tail tile, partials taken, epilogue) in K steps of the
                             // workgroup's kind: the stretches are cut equal in steps + that overhead (step 3 of the kernel)
+  // gemm_rows_skc_kernel over the representatives of an evaluation batch (carca_gemm_rows_feat_dedup): the rows multiplied
+  // are those with keep[s][row] != 0 instead of ids != 0, and the rows left out are not cleared (nothing reads them)
+  int keep_on;
+  const int32_t* keep[CARCA_MAX_SEGS];
 };
 
 
@@ -1170,7 +1174,7 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
 #pragma unroll
   for (int i = 0; i < CARCA_MAX_SEGS; ++i) {
     nrows_[i] = D.seg[i].rows;
-    ids_[i] = D.seg[i].ids;
+    ids_[i] = args.keep_on ? args.keep[i] : D.seg[i].ids;  // (what decides which rows are multiplied)
   }
   auto seg_cbase = [&](int s) {  // (s = 0 .. CARCA_MAX_SEGS: the entries in front of segment s, all of them for s = nseg)
     int v = 0;
@@ -1347,7 +1351,7 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
   const int xcd = id & 7, nw = x * nfull + y, q8 = nw >> 3, r8 = nw & 7;
   const int cnt = xcd < r8 ? q8 + 1 : q8;
   if (nrb == 0 || (id >> 3) >= cnt) {
-    clear_left_out();
+    if (!args.keep_on) clear_left_out();
     return;
   }
   const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
@@ -1387,6 +1391,10 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
     const CarcaGemmSeg sg = D.seg[s];
     const int p0 = (rb - rbs[s]) * 384, p1 = min(p0 + 384, live[s]);
     const int nch = (sg.rows + 63) / 64, cb0 = seg_cbase(s);
+    const int32_t* kid = ids_[0];
+#pragma unroll
+    for (int i = 1; i < CARCA_MAX_SEGS; ++i)
+      if (i == s) kid = ids_[i];
     // the chunks that hold the block's rows: a contiguous run (the running sums are monotone); every wave finds its ends
     // by itself (two searches over <= 2304 sums in LDS), then the run's chunks go round the waves, four requested together
     int cl = 0, ch = nch;  // first chunk whose end is past p0; first chunk that starts at or after p1
@@ -1420,7 +1428,7 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int row = (c0 + u) * 64 + lane;
-        const int v = sg.ids[min(row, sg.rows - 1)];
+        const int v = kid[min(row, sg.rows - 1)];
         idv[u] = (c0 + u < ch && row < sg.rows) ? v : 0;
       }
 #pragma unroll
@@ -1504,7 +1512,7 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
       cu_tile<2, XC, SK_DYN>(args, As, Bs, rb, nfull_ * 96, s0, s1, !give, part, flag, dyn);
     SKC_STAMP(5 + 2 * p);
   }
-  clear_left_out();
+  if (!args.keep_on) clear_left_out();
 #undef SKC_STAMP
 }
 
@@ -2236,7 +2244,10 @@ static int launch_gemm_rows_sk(const CarcaGemmDesc* desc, hipStream_t stream, co
 }
 
 // gemm_rows_skc_kernel: the stream-K kernel over the rows with id != 0.  1 = not this product's kernel.
-static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, const CarcaGatherArgs* pas, int* rode) {
+// dedup: over one representative row per group of equal attribute rows instead, between the plan and expand launches of
+// feat_dedup.hip (carca_gemm_rows_feat_dedup); the timing events then span all four launches.
+static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, const CarcaGatherArgs* pas, int* rode,
+                                bool dedup = false) {
   const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
   if (variant == 15 || variant == 158 || variant == 23) return 1;  // (23: gemm_rows_sk_kernel, every row -- A/B switch)
   if (!desc->mask_rows) return 1;  // (rows with id 0 may be left out only where the product masks them)
@@ -2294,6 +2305,24 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
     g.sk_spin = 1u << (lg > 0 && lg < 31 ? lg : 23);
     g.sk_withhold = carca_tuning(CARCA_TUNE_SK_WITHHOLD);
   }
+  CarcaDedupRun dd;
+  if (dedup) {
+    if (int rc = carca_feat_dedup_prepare(desc, stream, &dd)) return rc;
+    // the product of the representatives' attribute columns alone, into P (the expand launch adds context and bias)
+    pas = nullptr;
+    g.d.K1 = 0;
+    g.d.bt1 = nullptr;
+    g.d.bias = nullptr;
+    g.d.alpha = 0.f;
+    g.d.ldc = dd.ldp;
+    g.keep_on = 1;
+    for (int s = 0; s < desc->nseg; ++s) {
+      g.d.seg[s].c = dd.P + (size_t)dd.row0[s] * dd.ldp;
+      g.d.seg[s].a1 = nullptr;
+      g.d.seg[s].a1_bstride = 0;
+      g.keep[s] = dd.flag + dd.row0[s];
+    }
+  }
   int grid = ncu;
   // The gather rides (last workgroup: gather_rows_dma, ~20 ns per row measured beside the tiles: 392 us for C2's 19 k rows)
   // only under a product that lasts well beyond it even with half of its rows left out -- not at C2 (the kernel is ~480 us in
@@ -2314,9 +2343,14 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
   g.dbg = carca_debug_buffer();
   g.diag = carca_tuning(CARCA_TUNE_DIAG);  // (bit 0: the prologue's id loads read nothing -- timing experiment, wrong results)
   if (g_rows_log_on)
-    carca_rows_log(xc == 0 ? "gemm_rows_skc_kernel<0>" : (xc == 1 ? "gemm_rows_skc_kernel<1>" : "gemm_rows_skc_kernel<2>"), desc, grid);
+    carca_rows_log(dedup ? (xc == 0 ? "gemm_rows_skc_kernel<0>+dedup" : (xc == 1 ? "gemm_rows_skc_kernel<1>+dedup" : "gemm_rows_skc_kernel<2>+dedup"))
+                         : (xc == 0 ? "gemm_rows_skc_kernel<0>" : (xc == 1 ? "gemm_rows_skc_kernel<1>" : "gemm_rows_skc_kernel<2>")),
+                   desc, grid);
   hipEvent_t e0, e1;
-  const bool ev = carca_take_launch_events(&e0, &e1);
+  const bool ev_all = carca_take_launch_events(&e0, &e1);
+  if (dedup)
+    if (int rc = carca_feat_dedup_plan(&dd, stream, ev_all ? e0 : nullptr)) return rc;
+  const bool ev = ev_all && !dedup;
   if (xc == 0) {
     if (ev) hipExtLaunchKernelGGL((gemm_rows_skc_kernel<0>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
     else hipLaunchKernelGGL((gemm_rows_skc_kernel<0>), dim3(grid), dim3(768), 0, stream, g);
@@ -2328,6 +2362,7 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
     else hipLaunchKernelGGL((gemm_rows_skc_kernel<2>), dim3(grid), dim3(768), 0, stream, g);
   }
   CARCA_LAUNCH_CHECK();
+  if (dedup) return carca_feat_dedup_expand(&dd, stream, ev_all ? e1 : nullptr);
   return CARCA_OK;
 }
 
@@ -2498,6 +2533,22 @@ extern "C" int carca_gemm_rows(const CarcaGemmDesc* desc, void* stream_) {
     case GEMM_TILED_BUF: return launch_gemm_rows<128, 96, 32, 1, true>(desc, stream);
     default: return launch_gemm_rows<128, 96, 32, 1>(desc, stream);
   }
+}
+
+// The feature product of an EVALUATION forward (no gradient): over one representative row per group of equal attribute
+// rows where it runs on gemm_rows_skc_kernel (feat_dedup.hip), else carca_gemm_rows.  Tuning key 20 = 1 switches it off;
+// deterministic mode and the split-precision kernel keep their own paths.
+int carca_gemm_rows_feat_dedup(const CarcaGemmDesc* desc, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  GemmChoice c;
+  bool fits = false;
+  if (int rc = gemm_rows_choose(desc, &c, &fits)) return rc;
+  if ((c == GEMM_CU || c == GEMM_CU128) && carca_tuning(CARCA_TUNE_FEAT_DEDUP) != 1 &&
+      carca_tuning(CARCA_TUNE_DETERMINISTIC) == 0 && carca_tuning(CARCA_TUNE_SPLIT_GEMM) == 0) {
+    const int rc = launch_gemm_rows_skc(desc, stream, nullptr, nullptr, true);
+    if (rc != 1) return rc;
+  }
+  return carca_gemm_rows(desc, stream_);
 }
 
 int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* ga, int* rode, void* stream_) {

@@ -40,6 +40,9 @@ extern "C" {
 #define CARCA_EMBED_FEAT 2
 #define CARCA_EMBED_JOINT 4
 #define CARCA_EMBED_ALL 7
+/* with CARCA_EMBED_FEAT, evaluation only: the feature product over one representative per group of equal attribute rows
+ * (rows of equal id whose attribute bytes are equal; tuning key 20) */
+#define CARCA_EMBED_DEDUP 8
 
 int carca_abi_version(void);
 /* Kernel-variant knobs for tuning runs and A/B tests (tools/, tests/); 0 = the shipped choice everywhere.
@@ -79,7 +82,9 @@ int carca_abi_version(void);
  *          fp32 accumulation (fp32-class accuracy on the 16x faster pipe); 2 = two fp16 parts (the second scaled by
  *          2^11), three products, two fp32 accumulators -- |operands| < 65504 required.  Only where the one-workgroup-per-CU
  *          kernel would run; anything else keeps the fp32 kernels.  + 16: wherever the kernel's own conditions hold
- *          (K0 % 4 == 0, K1 <= 8, plain epilogue), whatever the grid -- for parity tests at fixture sizes. */
+ *          (K0 % 4 == 0, K1 <= 8, plain epilogue), whatever the grid -- for parity tests at fixture sizes.
+ *   key 20 feature product of an evaluation forward (carca_forward without a backward's saves): 0 = over one representative
+ *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests) */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
