@@ -19,8 +19,9 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip"]
-HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip"]
+HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
+           "catalogue_xent_common.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -279,6 +280,16 @@ class CatalogueXentDesc(C.Structure):
                 ("row_loss", _fp), ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dT", _fp)]
 
 
+class SampledXentDesc(C.Structure):
+    """CarcaSampledXentDesc (carca_sampled_xent_fwd / _bwd)."""
+    _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp),
+                ("ld_p", C.c_int32), ("Tp", _fp), ("ld_tp", C.c_int32), ("bp", _fp), ("pos", _fp), ("S", _fp),
+                ("ld_s", C.c_int32), ("s_ids", _fp), ("bs", _fp), ("splits_samples", C.c_int32),
+                ("samples_per_split", C.c_int32), ("splits_rows", C.c_int32), ("scratch", _fp),
+                ("scratch_floats", C.c_int64), ("lse", _fp), ("row_loss", _fp), ("loss", _fp), ("grad", _fp),
+                ("dP", _fp), ("dTp", _fp), ("dS", _fp)]
+
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -361,6 +372,8 @@ SIGNATURES = {
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
     "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
+    "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
+    "carca_sampled_xent_bwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

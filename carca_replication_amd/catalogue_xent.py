@@ -23,26 +23,26 @@ from . import ops
 from ._lib import CarcaHipError
 
 
-def _check(model, profile, pos) -> None:
+def _check(model, profile, pos, what: str = "catalogue_softmax_loss") -> None:
     from .modules import CrossAttentionBlock, DotProduct, WeightedDotProduct, _need_attr_table
 
     dec, emb = model.decoder, model.embeds
     if isinstance(dec, CrossAttentionBlock):
-        raise CarcaHipError("catalogue_softmax_loss: the CrossAttentionBlock decoder is not covered (the dot decoders "
+        raise CarcaHipError(f"{what}: the CrossAttentionBlock decoder is not covered (the dot decoders "
                             "DotProduct / WeightedDotProduct(normalize=False) are)")
     if not isinstance(dec, (DotProduct, WeightedDotProduct)):
-        raise CarcaHipError(f"catalogue_softmax_loss: decoder {type(dec).__name__} is not covered")
+        raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
     if isinstance(dec, WeightedDotProduct) and dec.norm:
-        raise CarcaHipError("catalogue_softmax_loss: WeightedDotProduct(normalize=True) divides by ||T[i] + M c||, which "
+        raise CarcaHipError(f"{what}: WeightedDotProduct(normalize=True) divides by ||T[i] + M c||, which "
                             "depends on the context: the full-catalogue softmax does not reduce to the item table")
     model._check_built()
     p_x = profile[0]
     ops._need_cuda(p_x, profile[1], profile[2], pos)
     if tuple(pos.shape) != tuple(p_x.shape):
-        raise CarcaHipError(f"catalogue_softmax_loss: pos must have the shape of p_x {tuple(p_x.shape)}, got "
+        raise CarcaHipError(f"{what}: pos must have the shape of p_x {tuple(p_x.shape)}, got "
                             f"{tuple(pos.shape)}")
     if hasattr(emb, "attr_table"):
-        _need_attr_table(emb, "catalogue_softmax_loss")
+        _need_attr_table(emb, what)
     if any(t is not None and t.requires_grad for t in profile):
         raise CarcaHipError("gradients with respect to the input tensors (ids/attrs/ctx) are not produced")
 
@@ -66,88 +66,109 @@ def _segments(model, profile):
     return [(c_(p_x), p_a, p_c, False), (x, cat_a, c, True)], n_items
 
 
+def _profile_forward(model, segs):
+    """The dot-decoder branch of autograd._CarcaFn over segs (the profile first, then target segments): the embedding of
+    every segment, dropout, the encoder blocks (saved for the backward), the final LayerNorm and the slot decay.
+    Returns (the final profile rows [B L, dpi], the embedded target segments, the state the backward reads)."""
+    from .modules import WeightedDotProduct
+
+    emb, dec = model.embeds, model.decoder
+    d = emb.d
+    dpi, _, _ = ops.padded_dims(d, model._heads())
+    p_x = segs[0][0]
+    B, L = p_x.shape
+    if emb.__dict__.get("_fold_train"):  # CARCA.fold_embedding(True, training=True)
+        es, emb_saved = emb._embed_segments_folded(segs, ld_e=dpi), "folded"
+    else:
+        es, emb_saved = emb.embed_segments(segs, ld_e=dpi)
+    x = es[0]
+    seed = ops.new_dropout_seed() if model.training else 0
+    p_emb = float(model.dropout.p) if model.training else 0.0
+    m_embed = ops.dropout_fwd(x, d, p_emb, seed, 1000) if p_emb > 0 else None  # carca.py:416
+    repack: list = []
+    sws = [blk.weights_struct(x.device, repack) for blk in model.encoder]
+    ops.pack_many(repack)
+    blocks = []
+    for i, blk in enumerate(model.encoder):
+        blk._check_mode()
+        bp = blk.drop_p()
+        y, saved = ops.sa_block_fwd(x, p_x, sws[i], d, blk.attn.H, blk.residual, save=True,
+                                    drop=(bp, seed, 4 * i) if bp > 0 else None)
+        saved["x_in"] = x
+        saved["p"] = bp
+        blocks.append(saved)
+        x = y
+    p_n = ops.layernorm_fwd(x.view(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)  # carca.py:421
+    rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi) if isinstance(dec, WeightedDotProduct) else p_n
+    if getattr(model, "_keep_dropout_masks", False):  # test hook: the fused path's layout (autograd._CarcaFn)
+        model._last_dropout_masks = dict(embed=m_embed, blocks=[{k: v for k, v in b.items() if k.startswith("m_")}
+                                                                for b in blocks], cross=None)
+    st = dict(p_x=p_x, segs=segs, es=es, emb_saved=emb_saved, blocks=blocks, enc_out=x, training=model.training,
+              B=B, L=L, m_embed=m_embed, p_emb=p_emb, dpi=dpi, is_ca=False, rows=rows)
+    return rows, es[1:], st
+
+
+def _profile_backward(model, params, st, loss_bwd) -> tuple:
+    """_profile_forward's backward -> the gradient of every parameter, as autograd._CarcaFn.backward computes it.
+    loss_bwd() runs the loss's backward once the pass is set up and returns (dP [B L, dpi] of the final profile rows,
+    [d e of every target segment, [rows, dpi] each])."""
+    from .autograd import _encoder_backward, _prepare_backward
+    from .modules import WeightedDotProduct
+
+    emb, dec = model.embeds, model.decoder
+    d, dpi, B, L = emb.d, st["dpi"], st["B"], st["L"]
+    prep = _prepare_backward(model, params, st)
+    plan, bpks, emb_wt_idx = prep["plan"], prep["bpks"], prep["emb_wt_idx"]
+    grads, after_pass, det, gbp = prep["grads"], prep["after_pass"], prep["det"], prep["gbp"]
+    dP, d_targets = loss_bwd()
+    if isinstance(dec, WeightedDotProduct):  # the slot weights are diagonal: their own transpose
+        dP = ops.slot_decay_scale(dP, B, L, d, dec.gamma, dpi)
+    dx = ops.layernorm_bwd(dP, st["enc_out"].view(-1, dpi), model.norm.weight.detach(), d, dpi,
+                           dgamma=gbp[id(model.norm.weight)], dbeta=gbp[id(model.norm.bias)])
+    wg = ops.WgradGroup()
+    dx = _encoder_backward(model, st, dx, gbp, bpks, wg)
+    if st["p_emb"] > 0:  # CARCA.dropout on the profile embedding (carca.py:416)
+        dx = ops.mask_mul(dx, st["m_embed"], 1.0 / (1.0 - st["p_emb"]), d, dpi)
+    wg.launch()
+    if det is not None:
+        det.flush_staging()
+    plan.unpack(gbp)
+    des = [dx] + list(d_targets)
+    if emb_wt_idx is not None:
+        emb.embed_backward(des, st["segs"], st["emb_saved"], gbp, L, dpi, wj_t=plan.wT.view(emb_wt_idx))
+    else:
+        emb.embed_backward(des, st["segs"], st["emb_saved"], gbp, L, dpi)
+    if det is not None:
+        det.finish()
+    after_pass()
+    return tuple(grads)
+
+
 class _CatalogueFn(torch.autograd.Function):
     """The fused route: one forward over the profile and the catalogue segment, one backward of fixed launches."""
 
     @staticmethod
     def forward(ctx, model, profile, pos, *params):
-        from .modules import WeightedDotProduct
-
-        emb, dec = model.embeds, model.decoder
-        d = emb.d
-        dpi, _, _ = ops.padded_dims(d, model._heads())
-        p_x = profile[0]
-        B, L = p_x.shape
         segs, n_items = _segments(model, profile)
-        p_x = segs[0][0]
-        if emb.__dict__.get("_fold_train"):  # CARCA.fold_embedding(True, training=True)
-            es, emb_saved = emb._embed_segments_folded(segs, ld_e=dpi), "folded"
-        else:
-            es, emb_saved = emb.embed_segments(segs, ld_e=dpi)
-        x = es[0]
-        seed = ops.new_dropout_seed() if model.training else 0
-        p_emb = float(model.dropout.p) if model.training else 0.0
-        m_embed = ops.dropout_fwd(x, d, p_emb, seed, 1000) if p_emb > 0 else None  # carca.py:416
-        repack: list = []
-        sws = [blk.weights_struct(x.device, repack) for blk in model.encoder]
-        ops.pack_many(repack)
-        blocks = []
-        for i, blk in enumerate(model.encoder):
-            blk._check_mode()
-            bp = blk.drop_p()
-            y, saved = ops.sa_block_fwd(x, p_x, sws[i], d, blk.attn.H, blk.residual, save=True,
-                                        drop=(bp, seed, 4 * i) if bp > 0 else None)
-            saved["x_in"] = x
-            saved["p"] = bp
-            blocks.append(saved)
-            x = y
-        p_n = ops.layernorm_fwd(x.view(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)  # carca.py:421
-        rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi) if isinstance(dec, WeightedDotProduct) else p_n
-        T = es[1].view(n_items, dpi)
+        rows, (cat,), st = _profile_forward(model, segs)
+        T = cat.view(n_items, st["dpi"])
         pos32 = ops._ids32(pos.reshape(-1))
-        loss, lse = ops.catalogue_xent_fwd(rows, T, pos32, d)
-        if getattr(model, "_keep_dropout_masks", False):  # test hook: the fused path's layout (autograd._CarcaFn)
-            model._last_dropout_masks = dict(embed=m_embed, blocks=[{k: v for k, v in b.items() if k.startswith("m_")}
-                                                                    for b in blocks], cross=None)
+        loss, lse = ops.catalogue_xent_fwd(rows, T, pos32, model.embeds.d)
         ctx.model, ctx.params = model, params
-        ctx.st = dict(p_x=p_x, segs=segs, es=es, emb_saved=emb_saved, blocks=blocks, enc_out=x, training=model.training,
-                      B=B, L=L, m_embed=m_embed, p_emb=p_emb, dpi=dpi, is_ca=False, rows=rows, T=T, pos=pos32, lse=lse)
+        ctx.st = dict(st, T=T, pos=pos32, lse=lse)
         return loss.view(())
 
     @staticmethod
     def backward(ctx, g):
-        from .autograd import _encoder_backward, _prepare_backward
-        from .modules import WeightedDotProduct
+        st, d = ctx.st, ctx.model.embeds.d
 
-        model, params, st = ctx.model, ctx.params, ctx.st
-        emb, dec = model.embeds, model.decoder
-        d, dpi, B, L = emb.d, st["dpi"], st["B"], st["L"]
-        prep = _prepare_backward(model, params, st)
-        plan, bpks, emb_wt_idx = prep["plan"], prep["bpks"], prep["emb_wt_idx"]
-        grads, after_pass, det, gbp = prep["grads"], prep["after_pass"], prep["det"], prep["gbp"]
-        dP, dT = ops.catalogue_xent_bwd(st["rows"], st["T"], st["pos"], st["lse"], g.detach(), d)
-        if isinstance(dec, WeightedDotProduct):  # the slot weights are diagonal: their own transpose
-            dP = ops.slot_decay_scale(dP, B, L, d, dec.gamma, dpi)
-        dx = ops.layernorm_bwd(dP, st["enc_out"].view(-1, dpi), model.norm.weight.detach(), d, dpi,
-                               dgamma=gbp[id(model.norm.weight)], dbeta=gbp[id(model.norm.bias)])
-        wg = ops.WgradGroup()
-        dx = _encoder_backward(model, st, dx, gbp, bpks, wg)
-        if st["p_emb"] > 0:  # CARCA.dropout on the profile embedding (carca.py:416)
-            dx = ops.mask_mul(dx, st["m_embed"], 1.0 / (1.0 - st["p_emb"]), d, dpi)
-        wg.launch()
-        if det is not None:
-            det.flush_staging()
-        plan.unpack(gbp)
-        des = [dx, dT]
-        if emb_wt_idx is not None:
-            emb.embed_backward(des, st["segs"], st["emb_saved"], gbp, L, dpi, wj_t=plan.wT.view(emb_wt_idx))
-        else:
-            emb.embed_backward(des, st["segs"], st["emb_saved"], gbp, L, dpi)
-        if det is not None:
-            det.finish()
-        after_pass()
+        def loss_bwd():
+            dP, dT = ops.catalogue_xent_bwd(st["rows"], st["T"], st["pos"], st["lse"], g.detach(), d)
+            return dP, [dT]
+
+        grads = _profile_backward(ctx.model, ctx.params, st, loss_bwd)
         ctx.st = None
-        return (None, None, None) + tuple(grads)
+        return (None, None, None) + grads
 
 
 def _composed_loss(model, profile, pos) -> Tensor:
@@ -188,3 +209,114 @@ def catalogue_softmax_loss(model, profile, pos: Tensor) -> Tensor:
     if model._composed(profile, [profile]):
         return _composed_loss(model, profile, pos)
     return _CatalogueFn.apply(model, tuple(profile), pos, *cached_parameters(model))
+
+
+# ---- sampled softmax with the logQ correction (DESIGN.md section 14) ------------------------------------------------
+def _sampled_segments(model, profile, pos, samples):
+    """[(profile segment), (samples [1, K], zero context), (positives [B, L], zero context)]; sample and positive ids
+    outside [1, n_items) become 0 on the device (the embedding's padding row, never a class)."""
+    emb = model.embeds
+    p_x, p_a, p_c = profile
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    dev = p_x.device
+
+    def fix(ids):
+        ids = ids.to(torch.int32)
+        return torch.where((ids >= 1) & (ids < n_items), ids, torch.zeros_like(ids))
+
+    s = fix(samples.reshape(1, -1))
+    tp = fix(pos)
+    K = s.shape[1]
+    c_s = torch.zeros(1, K, p_c.shape[-1], dtype=torch.float32, device=dev)
+    c_p = torch.zeros(*tp.shape, p_c.shape[-1], dtype=torch.float32, device=dev)
+    c_ = lambda t: t if t.is_contiguous() else t.contiguous()  # noqa: E731
+    a_s = a_p = None  # AllEmbedding gathers the table's rows by id inside its products, forward and backward
+    table = emb.attr_table() if hasattr(emb, "attr_table") else None
+    if table is not None and not hasattr(emb, "items_embed"):
+        # AttrCtx / Attr: their weight gradient reads dense attribute rows (modules._FeatsEmbedding.embed_backward)
+        a_s, a_p = table[s.long()], table[tp.long()]
+        if p_a is None:
+            p_a = table[p_x.long()]
+    return [(c_(p_x), p_a, p_c, False), (s, a_s, c_s, True), (tp, a_p, c_p, True)], n_items
+
+
+class _SampledFn(torch.autograd.Function):
+    """The fused route of the sampled loss: _CatalogueFn's, with the samples and the positives as the target segments."""
+
+    @staticmethod
+    def forward(ctx, model, profile, pos, samples, log_q, *params):
+        segs, n_items = _sampled_segments(model, profile, pos, samples)
+        rows, (es_s, es_p), st = _profile_forward(model, segs)
+        dpi, K = st["dpi"], segs[1][0].shape[1]
+        S, Tp = es_s.view(K, dpi), es_p.view(-1, dpi)
+        pos32, s32, bp, bs = ops.sampled_xent_corrections(pos, samples, log_q)
+        d = model.embeds.d
+        loss, lse, row_loss = ops.sampled_xent_fwd(rows, Tp, bp, pos32, S, s32, bs, n_items, d)
+        ctx.model, ctx.params = model, params
+        ctx.st = dict(st, S=S, Tp=Tp, sx=(bp, pos32, s32, bs, n_items), lse=lse, row_loss=row_loss)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        st, d = ctx.st, ctx.model.embeds.d
+
+        def loss_bwd():
+            bp, pos32, s32, bs, n_items = st["sx"]
+            dP, dTp, dS = ops.sampled_xent_bwd(st["rows"], st["Tp"], bp, pos32, st["S"], s32, bs, n_items, st["lse"],
+                                               st["row_loss"], g.detach(), d)
+            return dP, [dS, dTp]
+
+        grads = _profile_backward(ctx.model, ctx.params, st, loss_bwd)
+        ctx.st = None
+        return (None, None, None, None, None) + grads
+
+
+def _sampled_composed_loss(model, profile, pos, samples, log_q) -> Tensor:
+    """long_profile.py's differentiable pieces: L > 64, d > 128 or an unbuilt (d, H)."""
+    from . import long_profile as lp
+    from .modules import WeightedDotProduct, cached_parameters
+
+    emb, dec = model.embeds, model.decoder
+    d = emb.d
+    p_x = profile[0]
+    B, L = p_x.shape
+    if L > 1024:
+        raise CarcaHipError(f"sampled_softmax_loss: L={L} > 1024 profile slots")
+    segs, n_items = _sampled_segments(model, profile, pos, samples)
+    training = model.training
+    seed = ops.new_dropout_seed() if training else 0
+    sink = lp._Sink(len(model.encoder), 0) if getattr(model, "_keep_dropout_masks", False) else None
+    x, S, Tp = lp._EmbedSegsFn.apply(emb, tuple(segs), *cached_parameters(emb))
+    if training and model.dropout.p > 0:  # carca.py:416
+        x = lp._DropoutFn.apply(x, float(model.dropout.p), seed, 1000, sink, ("embed",))
+    for i, blk in enumerate(model.encoder):
+        blk._check_mode()
+        x = lp.sa_block(blk, x, segs[0][0], seed, 4 * i, sink, i)
+    p_n = lp._norm(x, model.norm)  # carca.py:421
+    if isinstance(dec, WeightedDotProduct):  # p[t] * sum_{j<=t} gamma^j (carca.py:385-386)
+        w = torch.cumsum(dec.gamma ** torch.arange(L, dtype=torch.float64, device=p_n.device), 0).to(torch.float32)
+        p_n = p_n * w.view(1, L, 1)
+    if sink is not None:
+        model._last_dropout_masks = sink.masks
+    K = S.shape[1]
+    return ops.sampled_xent(p_n.reshape(B * L, d), Tp.reshape(B * L, d), pos.reshape(-1), S.reshape(K, d),
+                            samples.reshape(-1), log_q)
+
+
+def sampled_softmax_loss(model, profile, pos: Tensor, samples: Tensor, log_q: Tensor) -> Tensor:
+    from .modules import cached_parameters, note_training_forward
+
+    what = "sampled_softmax_loss"
+    _check(model, profile, pos, what)
+    ops._need_cuda(samples, log_q)
+    if samples.is_floating_point() or samples.numel() < 1:
+        raise CarcaHipError(f"{what}: samples must be a non-empty integer tensor of item ids")
+    emb = model.embeds
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    if log_q.dim() != 1 or log_q.numel() != n_items or not log_q.is_floating_point():
+        raise CarcaHipError(f"{what}: log_q must be a float tensor [n_items = {n_items}], got {tuple(log_q.shape)} "
+                            f"{log_q.dtype}")
+    note_training_forward()  # packed-weight caches: see modules._WEIGHT_EPOCH
+    if model._composed(profile, [profile]):
+        return _sampled_composed_loss(model, profile, pos, samples, log_q)
+    return _SampledFn.apply(model, tuple(profile), pos, samples, log_q, *cached_parameters(model))

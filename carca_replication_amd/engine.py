@@ -55,17 +55,22 @@ def _row_exchange_len(p_x, o_x, global_batch: Optional[int]) -> Optional[int]:
     return per_rank * (p_x.shape[1] + o_x.shape[1])
 
 
-LOSSES = ("bce", "softmax")
+LOSSES = ("bce", "softmax", "sampled_softmax")
+SAMPLED_DEFAULT_K = 8192  # samples per step of the default (uniform) proposal
 
 
 def train_step(model, optim, batch, sharded: bool = False, global_batch: Optional[int] = None,
-               loss: str = "bce") -> torch.Tensor:
+               loss: str = "bce", sampler=None) -> torch.Tensor:
     """batch = (p_x, p_a, p_c, o_x, o_a, o_c, y_true) as the reference's DataLoader yields (train.py:84).
 
     loss: "bce" = the reference's objective (carca.py:441-444, one sampled negative per position); "softmax" = full-
     catalogue softmax cross-entropy of the positive half (CARCA.catalogue_softmax_loss): the
     negatives and y_true are not read, and every item row gets a gradient, so the optimizer is not told the batch's rows
     (a touched-row Adam table then steps densely).  Not built for sharded steps.
+    "sampled_softmax" = the same objective over K negatives shared by the batch (CARCA.sampled_softmax_loss, DESIGN.md
+    section 14), drawn by the step from `sampler` (sampling.ItemSampler; None = uniform with K = min(8192, n_items - 1));
+    the optimizer is told the rows p_x, the positives and the samples, so a touched-row Adam table stays sparse.  Not
+    built for sharded steps.
 
     With sharded=True the batch holds THIS rank's users; the loss is normalised by the global mask
     count and gradients are summed over ranks, which reproduces the single-process step exactly.
@@ -75,11 +80,17 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
     """
     if loss not in LOSSES:
         raise ValueError(f"train_step: loss must be one of {LOSSES}, got {loss!r}")
+    if sampler is not None and loss != "sampled_softmax":
+        raise ValueError(f'train_step: a sampler is only read by loss="sampled_softmax", got loss={loss!r}')
     batch = as_batch7(batch)
     if loss == "softmax":
         if sharded:
             raise CarcaHipError('train_step: loss="softmax" is not built for sharded steps')
         return _softmax_step(model, optim, batch)
+    if loss == "sampled_softmax":
+        if sharded:
+            raise CarcaHipError('train_step: loss="sampled_softmax" is not built for sharded steps')
+        return _sampled_softmax_step(model, optim, batch, sampler)
     p_x, o_x = batch[0], batch[3]
     gathered = None
     if not (sharded and cdist._active()):
@@ -173,6 +184,43 @@ def _softmax_step(model, optim, batch) -> torch.Tensor:
     loss = model.catalogue_softmax_loss((p_x, p_a, p_c), pos)
     loss.backward()
     optim.step()  # (no mark_rows: every row of the item table has a gradient)
+    return loss.detach()
+
+
+_SAMPLERS: dict = {}
+
+
+def default_sampler(model, device) -> "ItemSampler":
+    """The uniform proposal over the model's catalogue with K = min(SAMPLED_DEFAULT_K, n_items - 1) (one per catalogue
+    size and device)."""
+    from .sampling import ItemSampler
+
+    emb = model.embeds
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    key = (n_items, str(device))
+    if key not in _SAMPLERS:
+        _SAMPLERS[key] = ItemSampler(n_items, min(SAMPLED_DEFAULT_K, n_items - 1), device=device)
+    return _SAMPLERS[key]
+
+
+def _sampled_softmax_step(model, optim, batch, sampler) -> torch.Tensor:
+    p_x, p_a, p_c, o_x = batch[:4]
+    pos = o_x[:, : o_x.shape[1] // 2]  # train.py:86-88: the positive half
+    if sampler is None:
+        sampler = default_sampler(model, p_x.device)
+    samples = sampler.sample()
+    optim.zero_grad(set_to_none=True)
+    loss = model.sampled_softmax_loss((p_x, p_a, p_c), pos, samples, sampler.log_q())
+    loss.backward()
+    # the item table's gradient lives in the rows of the profile, the positives and the samples
+    tables = _sparse_tables(model, p_x, pos)
+    if tables and hasattr(optim, "mark_rows"):
+        n_items = model.embeds.items_embed.num_embeddings
+        s = samples.reshape(-1)
+        s = torch.where((s >= 1) & (s < n_items), s, torch.zeros_like(s))  # (as the loss embeds them)
+        for w, ids in tables.items():
+            optim.mark_rows(w, torch.cat([ids, s.to(ids.dtype)]))
+    optim.step()
     return loss.detach()
 
 

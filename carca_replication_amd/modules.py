@@ -1230,6 +1230,18 @@ class CARCA(_PackedModule, Model):
 
         return catalogue_softmax_loss(self, profile, pos)
 
+    def sampled_softmax_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor, samples: Tensor,
+                             log_q: Tensor) -> Tensor:
+        """Sampled softmax cross-entropy with the logQ correction: catalogue_softmax_loss with the
+        catalogue replaced by K ids `samples` shared by every slot, drawn from a proposal Q with log_q [n_items] = log Q
+        (sampling.ItemSampler).  Each valid slot's logsumexp runs over its positive and the samples that are not its
+        positive (accidental hits removed; duplicates each count), every logit corrected by -log(K Q(i)).  Sample ids
+        outside [1, n_items) contribute nothing.  With samples = arange(1, n_items) and uniform Q it equals
+        catalogue_softmax_loss.  Same decoders, embeddings, dropout and errors as catalogue_softmax_loss."""
+        from .catalogue_xent import sampled_softmax_loss
+
+        return sampled_softmax_loss(self, profile, pos, samples, log_q)
+
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items; DESIGN.md 10, 11) -
     def _catalogue_user_side(self, what: str, profile, context: Optional[Tensor], D) -> list:
         """Checks the envelope of recommend / rank_items and fills the model-side fields of D (RecommendDesc or RankDesc:

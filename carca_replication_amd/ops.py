@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -1379,11 +1380,11 @@ def catalogue_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
     return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
 
 
-def _xent_operand(x: Tensor, d: int) -> Tensor:
+def _xent_operand(x: Tensor, d: int, what: str = "catalogue_xent") -> Tensor:
     """x [rows, >= d] fp32 as the kernels take it: unit column stride, row stride a multiple of 4, 16-byte aligned;
     anything else is copied into [rows, round_up(d, 4)] with zeros past d."""
     if x.dtype != torch.float32:
-        raise CarcaHipError(f"catalogue_xent: expected float32, got {x.dtype}")
+        raise CarcaHipError(f"{what}: expected float32, got {x.dtype}")
     if x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= d and x.data_ptr() % 16 == 0:
         return x
     out = x.new_zeros(x.shape[0], (d + 3) // 4 * 4)
@@ -1466,3 +1467,162 @@ def catalogue_xent(P: Tensor, T: Tensor, pos: Tensor) -> Tensor:
     if pos.is_floating_point():
         raise CarcaHipError("catalogue_xent: pos must be an integer tensor")
     return _CatalogueXentFn.apply(P, T, pos)
+
+
+# --------------------------------------------------------------------------------------------------
+# sampled softmax cross-entropy with the logQ correction (carca_sampled_xent_fwd / _bwd)
+# --------------------------------------------------------------------------------------------------
+SX_TILE = 64  # rows of a workgroup's own tile and of each streamed tile (csrc/sampled_xent.hip)
+
+
+def sampled_xent_plan(R: int, K: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_sampled_xent_fwd / _bwd (pure: no device), catalogue_xent_plan's with the K samples in
+    place of the catalogue: the samples are split so that the forward's and dP's (row block x sample split) grid has about
+    CX_WAVES_PER_CU workgroups per CU, the rows of dS's (sample block x row split) grid likewise.  Returns the split counts
+    and the scratch each call needs, in 4-byte words (the layout csrc/sampled_xent.hip checks): 2 ceil64(R) + 64 words of
+    row lists, then the forward's (max, sum-exp) partials, or the backward's dP partials [splits_samples + 1, R, ld] (the
+    last: the positive term) and, with more than one row split, dS partials [splits_rows, K, ld], ld = round_up(d, 4)."""
+    if R < 1 or K < 1 or d < 1:
+        raise CarcaHipError("sampled_xent_plan: R, K and d must be positive")
+    r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
+    ldo = (d + 3) // 4 * 4
+    target = CX_WAVES_PER_CU * max(1, int(n_cus))
+    n_row_blocks = -(-R // SX_TILE)
+    n_sample_blocks = -(-K // SX_TILE)
+    s_s = max(1, min(n_sample_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
+    per = -(-n_sample_blocks // s_s) * SX_TILE
+    s_s = -(-K // per)  # (no empty split)
+    s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_sample_blocks)))
+    head = 2 * r64(R) + 64
+    fwd = head + 2 * r64(s_s * R)
+    bwd = head + r64((s_s + 1) * R * ldo) + (r64(s_r * K * ldo) if s_r > 1 else 0)
+    return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+
+
+def _sx_desc(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int, d: int,
+             scratch_key: str, keep: list):
+    R, K = P.shape[0], S.shape[0]
+    plan = sampled_xent_plan(R, K, d, num_cus())
+    D = _lib.SampledXentDesc()
+    D.R, D.K, D.n_items, D.d = R, K, int(n_items), d
+    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
+    D.bp, D.pos, D.s_ids, D.bs = bp.data_ptr(), pos.data_ptr(), s_ids.data_ptr(), bs.data_ptr()
+    D.splits_samples, D.samples_per_split = plan["splits_samples"], plan["samples_per_split"]
+    D.splits_rows = plan["splits_rows"]
+    # scratch through torch's caching allocator (max_memory_allocated sees it); freed when the call returns
+    scratch = torch.empty(plan[scratch_key], dtype=torch.float32, device=P.device)
+    keep.append(scratch)
+    D.scratch, D.scratch_floats = scratch.data_ptr(), scratch.numel()
+    return D
+
+
+def _sx_vec(t: Tensor, n: int, name: str, ids: bool) -> Tensor:
+    t = t.reshape(-1)
+    if t.numel() != n:
+        raise CarcaHipError(f"sampled_xent: {name} must have {n} entries, got {t.numel()}")
+    return _ids32(t) if ids else _f32(t)
+
+
+def sampled_xent_fwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int,
+                     d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Mean sampled softmax cross-entropy (include/carca_hip.h: carca_sampled_xent_fwd) of rows P [R, ld_p] with positives
+    Tp [R, ld_tp] against the shared samples S [K, ld_s] (first d columns, strides multiples of 4): pos [R] and
+    s_ids [K] int32, bp [R] and bs [K] the logQ corrections.  Returns (loss [1], lse [R], row_loss [R]); no host wait."""
+    _need_cuda(P, Tp, bp, pos, S, s_ids, bs)
+    R, K = P.shape[0], S.shape[0]
+    bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
+    pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
+    keep: list = [bp, bs, pos, s_ids]
+    D = _sx_desc(P, Tp, bp, pos, S, s_ids, bs, n_items, d, "scratch_fwd", keep)
+    lse = torch.empty(R, dtype=torch.float32, device=P.device)
+    row_loss = torch.empty_like(lse)
+    loss = torch.empty(1, dtype=torch.float32, device=P.device)
+    D.lse, D.row_loss, D.loss = lse.data_ptr(), row_loss.data_ptr(), loss.data_ptr()
+    _lib.check(_lib.load().carca_sampled_xent_fwd(C.byref(D), _stream()), "sampled_xent_fwd")
+    return loss, lse, row_loss
+
+
+def sampled_xent_bwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int,
+                     lse: Tensor, row_loss: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dP [R, ld_p], dTp [R, ld_tp], dS [K, ld_s]) of sampled_xent_fwd's loss scaled by grad [1] (device); zeros past d."""
+    _need_cuda(P, Tp, bp, pos, S, s_ids, bs, lse, row_loss, grad)
+    R, K = P.shape[0], S.shape[0]
+    bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
+    pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
+    keep: list = [bp, bs, pos, s_ids]
+    D = _sx_desc(P, Tp, bp, pos, S, s_ids, bs, n_items, d, "scratch_bwd", keep)
+    g = _f32(grad.reshape(1))
+    dP = torch.empty(R, P.stride(0), dtype=torch.float32, device=P.device)
+    dTp = torch.empty(R, Tp.stride(0), dtype=torch.float32, device=P.device)
+    dS = torch.empty(K, S.stride(0), dtype=torch.float32, device=P.device)
+    D.lse, D.row_loss, D.grad = lse.data_ptr(), row_loss.data_ptr(), g.data_ptr()
+    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
+    _lib.check(_lib.load().carca_sampled_xent_bwd(C.byref(D), _stream()), "sampled_xent_bwd")
+    return dP, dTp, dS
+
+
+def sampled_xent_corrections(pos: Tensor, s_ids: Tensor, log_q: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(pos32 [R], s_ids32 [K], bp [R], bs [K]) for the kernels from log_q [n_items] = log Q(i): ids outside [1, n_items)
+    become 0 (never a class), bp = -(log Q(pos) + log K), bs = -(log Q(s) + log K), 0 at ids outside the range.  On the
+    device; no host check of the ids."""
+    n_items, K = log_q.numel(), s_ids.numel()
+    lq = log_q.reshape(-1).to(torch.float32)
+
+    def fix(ids):
+        ids = ids.reshape(-1).long()
+        ok = (ids >= 1) & (ids < n_items)
+        safe = torch.where(ok, ids, torch.zeros_like(ids))
+        b = torch.where(ok, -(lq[safe] + math.log(K)), torch.zeros((), dtype=torch.float32, device=lq.device))
+        return safe.to(torch.int32), b.contiguous()
+
+    pos32, bp = fix(pos)
+    s32, bs = fix(s_ids)
+    return pos32, s32, bp, bs
+
+
+class _SampledXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, Tp, S, pos32, s32, bp, bs, n_items):
+        d = P.shape[1]
+        P2, Tp2, S2 = (_xent_operand(x.detach(), d, "sampled_xent") for x in (P, Tp, S))
+        loss, lse, row_loss = sampled_xent_fwd(P2, Tp2, bp, pos32, S2, s32, bs, n_items, d)
+        ctx.save_for_backward(P2, Tp2, S2, pos32, s32, bp, bs, lse, row_loss)
+        ctx.d, ctx.n_items = d, n_items
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        P2, Tp2, S2, pos32, s32, bp, bs, lse, row_loss = ctx.saved_tensors
+        d = ctx.d
+        dP, dTp, dS = sampled_xent_bwd(P2, Tp2, bp, pos32, S2, s32, bs, ctx.n_items, lse, row_loss, g.detach(), d)
+        return dP[:, :d], dTp[:, :d], dS[:, :d], None, None, None, None, None
+
+
+def sampled_xent(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, log_q: Tensor) -> Tensor:
+    """Mean sampled softmax cross-entropy with the logQ correction, differentiable in P, Tp and S:
+
+        sum over valid r of ( logsumexp( {z'(r, pos[r])} U {z'(r, s_k) : k in N_r} ) - z'(r, pos[r]) ) / n_valid
+        z'(r, i) = P[r] . e_i - log(K Q(i)),  e_pos[r] = Tp[r],  e_s_k = S[k],  N_r = {k : s_k in [1, n_items), s_k != pos[r]}
+
+    P [R, d], Tp [R, d] (the rows of the positives), S [K, d] (the rows of the K samples) fp32; pos [R], s_ids [K] integer;
+    log_q [n_items] = log Q(i) of the proposal the samples were drawn from (n_items = log_q.numel()).  Row r is valid iff
+    pos[r] lies in [1, n_items); a sample id outside [1, n_items) contributes nothing; a batch without a valid row gives 0.
+    With s_ids = arange(1, n_items) and uniform Q this is catalogue_xent.  Fused HIP kernels: no [R, K] buffer."""
+    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
+        raise CarcaHipError(f"sampled_xent: expected P [R, d], Tp [R, d], S [K, d]; got {tuple(P.shape)}, "
+                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
+    if pos.numel() != P.shape[0] or s_ids.numel() != S.shape[0]:
+        raise CarcaHipError(f"sampled_xent: pos must have R = {P.shape[0]} entries and s_ids K = {S.shape[0]}; got "
+                            f"{pos.numel()} and {s_ids.numel()}")
+    if S.shape[0] < 1:
+        raise CarcaHipError("sampled_xent: at least one sample is needed")
+    if pos.is_floating_point() or s_ids.is_floating_point():
+        raise CarcaHipError("sampled_xent: pos and s_ids must be integer tensors")
+    if any(x.dtype != torch.float32 for x in (P, Tp, S)):
+        raise CarcaHipError(f"sampled_xent: P, Tp and S must be float32, got {P.dtype}, {Tp.dtype}, {S.dtype}")
+    if log_q.dim() != 1 or log_q.numel() < 1 or not log_q.is_floating_point():
+        raise CarcaHipError(f"sampled_xent: log_q must be a 1-d float tensor [n_items], got {tuple(log_q.shape)} "
+                            f"{log_q.dtype}")
+    _need_cuda(P, Tp, pos, S, s_ids, log_q)
+    pos32, s32, bp, bs = sampled_xent_corrections(pos, s_ids, log_q)
+    return _SampledXentFn.apply(P, Tp, S, pos32, s32, bp, bs, log_q.numel())

@@ -191,7 +191,7 @@ def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5,
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,
-          resume: Union[str, None] = None, resume_trusted: bool = False, loss: str = "bce") -> Model:
+          resume: Union[str, None] = None, resume_trusted: bool = False, loss: str = "bce", sampler=None) -> Model:
     """src/train.py:56-152.  Extensions, off by default:
     graphed: batches of the first batch's shape replay their forward + backward from one hipGraph
       (engine.GraphedTrainStep); any other shape (a short last batch) takes the eager step;
@@ -199,13 +199,19 @@ def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_l
       restored and the epoch count continues after the stored one, with the stored best NDCG as the bar to beat;
     resume_trusted: the file named by `resume` may be a whole-module pickle as the reference writes them (train.py:124):
       load_checkpoint(allow_pickle=True) -- unpickling executes code from the file, so only for files the caller trusts;
-    loss: "bce" (the reference's objective) or "softmax" (full-catalogue softmax cross-entropy, engine.train_step; not with
-      graphed=True).  Validation and test stay the reference's sampled HR / NDCG either way."""
+    loss: "bce" (the reference's objective), "softmax" (full-catalogue softmax cross-entropy, engine.train_step) or
+      "sampled_softmax" (softmax over K shared samples with the logQ correction); the softmax losses not with
+      graphed=True.  Validation and test stay the reference's sampled HR / NDCG either way;
+    sampler: loss="sampled_softmax" only: the proposal the samples are drawn from (sampling.ItemSampler; None = uniform,
+      K = min(8192, n_items - 1))."""
     objective = loss  # (`loss` names the validation loss below, as in the reference's loop)
     if objective not in engine.LOSSES:
         raise ValueError(f"train: loss must be one of {engine.LOSSES}, got {objective!r}")
+    if sampler is not None and objective != "sampled_softmax":
+        raise ValueError(f'train: a sampler is only read by loss="sampled_softmax", got loss={objective!r}')
     if graphed and objective != "bce":
-        raise CarcaHipError('train: graphed=True captures the BCE step only; loss="softmax" runs eagerly (graphed=False)')
+        raise CarcaHipError(f'train: graphed=True captures the BCE step only; loss="{objective}" runs eagerly '
+                           '(graphed=False)')
     os.makedirs(datadir, exist_ok=True)
     model = model.train().to(device)
     best, stale, first_epoch = 0.0, 0, 1
@@ -230,7 +236,7 @@ def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_l
             if graphed and captured[0] == sig:
                 loss_sum += captured[1](dev_batch)
             else:
-                loss_sum += engine.train_step(model, optim, dev_batch, loss=objective)
+                loss_sum += engine.train_step(model, optim, dev_batch, loss=objective, sampler=sampler)
             if verbose == 2:  # the reference prints a running mean per batch; that costs a sync per batch here too
                 print(f"{now()} - Batch {i:03d}: Loss = {(float(loss_sum) / i):.4f}")
         mean_loss = float(loss_sum) / len(train_loader)

@@ -948,6 +948,52 @@ typedef struct CarcaCatalogueXentDesc {
 int carca_catalogue_xent_fwd(const CarcaCatalogueXentDesc* desc, void* stream);
 int carca_catalogue_xent_bwd(const CarcaCatalogueXentDesc* desc, void* stream);
 
+/* ---- sampled softmax cross-entropy with the logQ correction for the dot decoders ------------
+ * P [R, ld_p] profile rows, Tp [R, ld_tp] the rows of their positives, S [K, ld_s] the rows of K samples shared by every
+ * row (d features; ld_p, ld_tp, ld_s multiples of 4; P and S 16-byte aligned), pos [R] and s_ids [K] int32, bp [R] and
+ * bs [K] the logQ corrections -log(K Q(id)).  Row r is VALID iff pos[r] lies in [1, n_items).  Sample k is a negative of
+ * row r iff s_ids[k] lies in [1, n_items) and differs from pos[r] (accidental hits removed; duplicates each count).
+ *   carca_sampled_xent_fwd: with z'(r, +) = P[r] . Tp[r] + bp[r] and z'(r, k) = P[r] . S[k] + bs[k],
+ *     lse[r] = log( exp z'(r, +) + sum over the negatives k of r of exp z'(r, k) ), row_loss[r] = lse[r] - z'(r, +)
+ *     (both 0 for a row that is not valid), loss[0] = sum of row_loss / n_valid (0 when no row is valid);
+ *   carca_sampled_xent_bwd: with lse and row_loss from the forward and the upstream scale grad[0],
+ *     G[r, k] = exp(z'(r, k) - lse[r]) on the negatives (else 0), p_pos = exp(-row_loss[r]):
+ *     dP  = grad / n_valid (G S + (p_pos - 1) Tp), dTp = grad / n_valid (p_pos - 1) P  (0 for rows that are not valid),
+ *     dS  = grad / n_valid G^T P (0 for samples that are no class); every output 0 past d.
+ * Products in exact-fp32 MFMA; the logit tiles are recomputed, never stored.  The samples are split over
+ * splits_samples workgroup columns of samples_per_split (a multiple of 64); the backward's dS splits the valid rows over
+ * splits_rows.  Scratch (scratch_floats 4-byte words, caller-allocated; ops.sampled_xent_plan gives the size):
+ * 2 ceil64(R) + 64 words of row lists, then the forward's 2 ceil64(splits_samples R) (max, sum-exp) partials, or the
+ * backward's ceil64((splits_samples + 1) R ld) dP partials and, with splits_rows > 1, ceil64(splits_rows K ld) dS
+ * partials, ld = round_up(d, 4).  No float atomics: the same call gives the same bits.  CARCA_ERR_UNSUPPORTED: d > 256.
+ * CARCA_ERR_BADARG: null pointers, strides, split counts outside 1..256, samples_per_split * splits_samples < K,
+ * scratch too small. */
+typedef struct CarcaSampledXentDesc {
+  int R, K, n_items, d;
+  const float* P;
+  int ld_p;
+  const float* Tp;
+  int ld_tp;
+  const float* bp;       /* [R] */
+  const int32_t* pos;    /* [R] */
+  const float* S;
+  int ld_s;
+  const int32_t* s_ids;  /* [K] */
+  const float* bs;       /* [K] */
+  int splits_samples, samples_per_split, splits_rows;
+  float* scratch;
+  int64_t scratch_floats;
+  float* lse;        /* [R]: forward output, backward input */
+  float* row_loss;   /* [R]: forward output, backward input */
+  float* loss;       /* [1] forward */
+  const float* grad; /* [1] backward: upstream scale of loss */
+  float* dP;         /* [R, ld_p] backward */
+  float* dTp;        /* [R, ld_tp] backward */
+  float* dS;         /* [K, ld_s] backward */
+} CarcaSampledXentDesc;
+int carca_sampled_xent_fwd(const CarcaSampledXentDesc* desc, void* stream);
+int carca_sampled_xent_bwd(const CarcaSampledXentDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
