@@ -171,22 +171,20 @@ class _CatalogueFn(torch.autograd.Function):
         return (None, None, None) + grads
 
 
-def _composed_loss(model, profile, pos) -> Tensor:
-    """long_profile.py's differentiable pieces: L > 64, d > 128 or an unbuilt (d, H)."""
+def _composed_rows(model, profile, segs, what: str):
+    """long_profile.py's differentiable pieces (L > 64, d > 128 or an unbuilt (d, H)) over segs, the profile first:
+    (the normalised profile rows [B, L, d] with the decoder's weights, the target segments' embeddings)."""
     from . import long_profile as lp
     from .modules import WeightedDotProduct, cached_parameters
 
     emb, dec = model.embeds, model.decoder
-    d = emb.d
-    p_x = profile[0]
-    B, L = p_x.shape
+    L = profile[0].shape[1]
     if L > 1024:
-        raise CarcaHipError(f"catalogue_softmax_loss: L={L} > 1024 profile slots")
-    segs, n_items = _segments(model, profile)
+        raise CarcaHipError(f"{what}: L={L} > 1024 profile slots")
     training = model.training
     seed = ops.new_dropout_seed() if training else 0
     sink = lp._Sink(len(model.encoder), 0) if getattr(model, "_keep_dropout_masks", False) else None
-    x, T = lp._EmbedSegsFn.apply(emb, tuple(segs), *cached_parameters(emb))
+    x, *targets = lp._EmbedSegsFn.apply(emb, tuple(segs), *cached_parameters(emb))
     if training and model.dropout.p > 0:  # carca.py:416
         x = lp._DropoutFn.apply(x, float(model.dropout.p), seed, 1000, sink, ("embed",))
     for i, blk in enumerate(model.encoder):
@@ -198,7 +196,14 @@ def _composed_loss(model, profile, pos) -> Tensor:
         p_n = p_n * w.view(1, L, 1)
     if sink is not None:
         model._last_dropout_masks = sink.masks
-    return ops.catalogue_xent(p_n.reshape(B * L, d), T.reshape(n_items, d), pos.reshape(-1))
+    return p_n, targets
+
+
+def _composed_loss(model, profile, pos) -> Tensor:
+    segs, n_items = _segments(model, profile)
+    p_n, (T,) = _composed_rows(model, profile, segs, "catalogue_softmax_loss")
+    d = model.embeds.d
+    return ops.catalogue_xent(p_n.reshape(-1, d), T.reshape(n_items, d), pos.reshape(-1))
 
 
 def catalogue_softmax_loss(model, profile, pos: Tensor) -> Tensor:
@@ -272,34 +277,10 @@ class _SampledFn(torch.autograd.Function):
 
 
 def _sampled_composed_loss(model, profile, pos, samples, log_q) -> Tensor:
-    """long_profile.py's differentiable pieces: L > 64, d > 128 or an unbuilt (d, H)."""
-    from . import long_profile as lp
-    from .modules import WeightedDotProduct, cached_parameters
-
-    emb, dec = model.embeds, model.decoder
-    d = emb.d
-    p_x = profile[0]
-    B, L = p_x.shape
-    if L > 1024:
-        raise CarcaHipError(f"sampled_softmax_loss: L={L} > 1024 profile slots")
-    segs, n_items = _sampled_segments(model, profile, pos, samples)
-    training = model.training
-    seed = ops.new_dropout_seed() if training else 0
-    sink = lp._Sink(len(model.encoder), 0) if getattr(model, "_keep_dropout_masks", False) else None
-    x, S, Tp = lp._EmbedSegsFn.apply(emb, tuple(segs), *cached_parameters(emb))
-    if training and model.dropout.p > 0:  # carca.py:416
-        x = lp._DropoutFn.apply(x, float(model.dropout.p), seed, 1000, sink, ("embed",))
-    for i, blk in enumerate(model.encoder):
-        blk._check_mode()
-        x = lp.sa_block(blk, x, segs[0][0], seed, 4 * i, sink, i)
-    p_n = lp._norm(x, model.norm)  # carca.py:421
-    if isinstance(dec, WeightedDotProduct):  # p[t] * sum_{j<=t} gamma^j (carca.py:385-386)
-        w = torch.cumsum(dec.gamma ** torch.arange(L, dtype=torch.float64, device=p_n.device), 0).to(torch.float32)
-        p_n = p_n * w.view(1, L, 1)
-    if sink is not None:
-        model._last_dropout_masks = sink.masks
-    K = S.shape[1]
-    return ops.sampled_xent(p_n.reshape(B * L, d), Tp.reshape(B * L, d), pos.reshape(-1), S.reshape(K, d),
+    segs, _ = _sampled_segments(model, profile, pos, samples)
+    p_n, (S, Tp) = _composed_rows(model, profile, segs, "sampled_softmax_loss")
+    d = model.embeds.d
+    return ops.sampled_xent(p_n.reshape(-1, d), Tp.reshape(-1, d), pos.reshape(-1), S.reshape(-1, d),
                             samples.reshape(-1), log_q)
 
 

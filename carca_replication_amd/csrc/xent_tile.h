@@ -1,0 +1,414 @@
+// The tile skeleton of the softmax cross-entropy kernels: catalogue_xent.hip (the classes are the whole catalogue,
+// DESIGN.md section 13) and sampled_xent.hip (the classes are K shared samples with the logQ correction, section 14).
+//
+// A workgroup of four waves owns 64 rows of one operand (the "own" tile, staged once in LDS) and streams 64-row tiles of
+// the other through LDS.  Wave w owns own rows 16w .. 16w+15; lane l holds column r16 = l & 15 and the stream rows
+// 16n + 4q + j (q = l >> 4) of the 64 x 16 logit tile Z^T = S O^T, which is exactly the A operand of the second product
+// out += G * stream, so G never leaves the registers.  What lives here, once:
+//   device: the split range of a workgroup, the Z^T product, the running (max, sum-exp) update of masked logits, the
+//           G * stream accumulation, the four-lane merge with its partial store, the output epilogue with its zero tail;
+//           cx_compact_kernel (the valid rows, pos in [1, n_items), in row order), cx_mean_kernel (the fp64 mean of the
+//           row losses) and cx_reduce_kernel (split partials summed in split order, scaled by grad / n_valid);
+//   host:   the scratch layout, the checks both descriptors share, the LDS-size / NCB dispatch, and the launch sequences
+//           of the forward (compact, tile, merge, mean) and the backward (compact, dP tile, reduce, dT tile, reduce).
+// What each kernel keeps: how it stages a tile (catalogue: straight into LDS; sampled: one tile ahead in registers), its
+// mask / G rule with the lane's own-entry metadata, and its merge kernels.
+#pragma once
+#include "carca_common.h"
+#include "../../include/carca_hip.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int XT_THREADS = 256;
+constexpr int XT_TILE = 64;  // own rows per workgroup (16 per wave) and stream rows per step
+constexpr int XT_MAX_D = 256;
+constexpr int XT_MAX_SPLITS = 256;
+constexpr int CX_COMPACT_THREADS = 1024;
+enum { XT_FWD = 0, XT_DP = 1, XT_DT = 2 };  // DT: the gradient of the class operand (dT, dS)
+
+__host__ __device__ inline int64_t cx_r64(int64_t n) { return (n + 63) / 64 * 64; }
+
+// ---- the arguments of a tile kernel ----------------------------------------------------------------------------------
+struct XentTile {
+  int R, n, n_items, d, ld_p, ld_t;  // n: classes (the catalogue's items, or the K samples); ids lie in [1, n_items)
+  const float* P;
+  const float* T;                    // the class operand [n, ld_t]
+  const int32_t* pos;
+  const int32_t* ids;                // sampled: item id of each class (catalogue: null, class i is item i)
+  const float* bias;                 // sampled: logQ correction of each class (catalogue: null)
+  const int32_t* ridx;
+  const int32_t* nv;
+  const float* lse;   // backward: per original row
+  const float* grad;  // backward: upstream scale [1]
+  int splits;         // FWD / DP: class splits; DT: row splits
+  int per_split;      // FWD / DP: classes per split (a multiple of XT_TILE)
+  int pitch;          // LDS row pitch in floats
+  float* part_m;      // FWD: [splits][R]
+  float* part_s;
+  float* out;         // DP: [splits][R][ld_out] by valid-row index; DT: [splits][n][ld_out], or dT itself
+  int64_t out_split_stride;
+  int ld_out;
+  int final_out;      // DT with one split: scale by grad / n_valid and write zeros past d (out = dT)
+};
+
+// ---- device helpers ---------------------------------------------------------------------------------------------------
+// stream entries [s_begin, s_end) of the workgroup of split `split`: FWD / DP stream the classes of one split, DT the
+// valid rows of one split.  (The early return of a FWD / DP row block past n_valid stays in the kernel, in front of this
+// call: returned through here as a bool, it changed the sampled forward's prologue and cost it 2 % at K = 8192.)
+template <int MODE>
+__device__ __forceinline__ void xt_split_range(const XentTile& A, int nv, int split, int& s_begin, int& s_end) {
+  if constexpr (MODE != XT_DT) {
+    s_begin = split * A.per_split;
+    s_end = min(s_begin + A.per_split, A.n);
+  } else {
+    const int nb = (nv + XT_TILE - 1) / XT_TILE;
+    s_begin = (int)((long long)split * nb / A.splits) * XT_TILE;
+    s_end = min((int)((long long)(split + 1) * nb / A.splits) * XT_TILE, nv);
+  }
+}
+
+// Z^T[stream 16n + 4q + reg][own r16] for the four 16-row stream blocks n (own_row: the lane's own row, at column 4q).
+// (The products accumulate in locals, copied to the caller's array at the end: accumulating through the reference costs
+// every instantiation 12 more AGPRs, and two of them a wave of occupancy.)
+template <int NCB>
+__device__ __forceinline__ void xt_logits(const XentTile& A, const float* own_row, const float* str, int r16, int q,
+                                          f32x4 (&z_out)[4]) {
+  const int nkg = round_up(A.d, 16) / 16;
+  f32x4 z[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) z[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kg = 0; kg < NCB; ++kg) {
+    if (kg < nkg) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(own_row + 16 * kg);
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(str + (16 * n + r16) * A.pitch + 16 * kg + 4 * q);
+        z[n] = mfma16_group(a, b, z[n]);
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < 4; ++n) z_out[n] = z[n];
+}
+
+// the lane's running (max, sum-exp) over one more tile of logits, -inf where masked
+__device__ __forceinline__ void xt_running_update(const f32x4 (&z)[4], float& run_m, float& run_s) {
+  float cm = -INFINITY;
+#pragma unroll
+  for (int n = 0; n < 4; ++n)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cm = fmaxf(cm, z[n][j]);
+  if (cm > -INFINITY) {
+    const float mn = fmaxf(run_m, cm);
+    float s = run_m > -INFINITY ? run_s * __expf(run_m - mn) : 0.f;
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (z[n][j] > -INFINITY) s += __expf(z[n][j] - mn);
+    run_m = mn;
+    run_s = s;
+  }
+}
+
+// out[own r16][col 16c + l&15] += sum over the 64 stream rows of G * stream  (k = stream 16n + 4q + j at step j)
+template <int NCB>
+__device__ __forceinline__ void xt_accumulate(const XentTile& A, const f32x4 (&g)[4], const float* str, int r16, int q,
+                                              f32x4 (&acc)[NCB]) {
+  const int ncb = (A.d + 15) / 16;
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    if (c < ncb) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[c] = mfma16(g[n][j], str[(16 * n + 4 * q + j) * A.pitch + 16 * c + r16], acc[c]);
+    }
+  }
+}
+
+// FWD: merge the four lanes of own row r16 (lanes r16 + 16q; max and + are commutative, so every lane gets the same
+// bits) and store the (max, sum) partial of (split, valid row o_idx)
+__device__ __forceinline__ void xt_store_partial(const XentTile& A, float run_m, float run_s, int split, int o_idx, int q,
+                                                 int nv) {
+#pragma unroll
+  for (int x = 16; x <= 32; x *= 2) {
+    const float om = __shfl_xor(run_m, x), os = __shfl_xor(run_s, x);
+    const float mn = fmaxf(run_m, om);
+    const float a = run_m > -INFINITY ? run_s * __expf(run_m - mn) : 0.f;
+    const float b = om > -INFINITY ? os * __expf(om - mn) : 0.f;
+    run_m = mn;
+    run_s = a + b;
+  }
+  if (q == 0 && o_idx < nv) {
+    A.part_m[(size_t)split * A.R + o_idx] = run_m;
+    A.part_s[(size_t)split * A.R + o_idx] = run_s;
+  }
+}
+
+// DP / DT: D of acc[c] is column 16c + r16 of own rows 16w + 4q + j
+template <int MODE, int NCB>
+__device__ __forceinline__ void xt_epilogue(const XentTile& A, const f32x4 (&acc)[NCB], int nv, int own0, int split, int w,
+                                            int lane) {
+  const int r16 = lane & 15, q = lane >> 4, ncb = (A.d + 15) / 16;
+  float* out = A.out + (size_t)split * A.out_split_stride;
+  float coef = 1.f;
+  if constexpr (MODE == XT_DT) {
+    if (A.final_out) coef = nv > 0 ? A.grad[0] / (float)nv : 0.f;
+  }
+  const int own_end = MODE == XT_DP ? nv : A.n;
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    if (c < ncb) {
+      const int col = 16 * c + r16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = own0 + 16 * w + 4 * q + j;
+        if (e < own_end && col < A.ld_out) out[(size_t)e * A.ld_out + col] = col < A.d ? acc[c][j] * coef : 0.f;
+      }
+    }
+  }
+  if (MODE == XT_DT && A.final_out) {  // columns past the 16-column blocks, up to the row stride
+    for (int col = 16 * ncb + lane; col < A.ld_out; col += 64)
+      for (int j = 0; j < 16; ++j) {
+        const int e = own0 + 16 * w + j;
+        if (e < A.n) out[(size_t)e * A.ld_out + col] = 0.f;
+      }
+  }
+}
+
+// ---- valid rows, in row order -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(CX_COMPACT_THREADS) void cx_compact_kernel(const int32_t* __restrict__ pos, int R, int n_items,
+                                                                         int32_t* __restrict__ ridx,
+                                                                         int32_t* __restrict__ rpos, int32_t* __restrict__ nv) {
+  __shared__ int wsum[CX_COMPACT_THREADS / 64];
+  __shared__ int base_s;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid == 0) base_s = 0;
+  __syncthreads();
+  for (int r0 = 0; r0 < R; r0 += CX_COMPACT_THREADS) {
+    const int r = r0 + tid;
+    const int p = r < R ? pos[r] : 0;
+    const bool ok = r < R && p >= 1 && p < n_items;
+    const unsigned long long m = __ballot(ok);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[w] = __popcll(m);
+    __syncthreads();
+    int off = base_s;
+    for (int j = 0; j < w; ++j) off += wsum[j];
+    if (r < R) {
+      const int v = off + before;
+      rpos[r] = ok ? v : -1;
+      if (ok) ridx[v] = r;
+    }
+    __syncthreads();
+    if (tid == CX_COMPACT_THREADS - 1) {
+      int tot = 0;
+      for (int j = 0; j < CX_COMPACT_THREADS / 64; ++j) tot += wsum[j];
+      base_s += tot;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) nv[0] = base_s;
+}
+
+__global__ __launch_bounds__(1024) void cx_mean_kernel(const float* __restrict__ row_loss, int R, float* __restrict__ loss,
+                                                       const int32_t* __restrict__ nv) {
+  __shared__ double red[1024];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int r = tid; r < R; r += 1024) s += (double)row_loss[r];
+  red[tid] = s;
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) loss[0] = nv[0] > 0 ? (float)(red[0] / (double)nv[0]) : 0.f;
+}
+
+// dst[e][col] (col < ld_dst) = coef * sum over splits of part[s][map(e)][col] for col < d, else 0
+__global__ __launch_bounds__(256) void cx_reduce_kernel(const float* __restrict__ part, int64_t split_stride, int splits,
+                                                        int ld_part, const int32_t* __restrict__ rpos, int rows, int d,
+                                                        float* __restrict__ dst, int ld_dst, const int32_t* __restrict__ nv,
+                                                        const float* __restrict__ grad) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)rows * ld_dst) return;
+  const int e = (int)(idx / ld_dst), col = (int)(idx - (int64_t)e * ld_dst);
+  const int src = rpos ? rpos[e] : e;
+  float v = 0.f;
+  if (src >= 0 && col < d) {
+    for (int s = 0; s < splits; ++s) v += part[(size_t)s * split_stride + (size_t)src * ld_part + col];
+    const int n = nv[0];
+    v *= n > 0 ? grad[0] / (float)n : 0.f;
+  }
+  dst[(size_t)e * ld_dst + col] = v;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+// One call under one set of names, filled from either descriptor.  A carries the operands (R, n, n_items, d, P, T, pos,
+// ids, bias, lse, grad, per_split); the rest is what the launch sequences need beside them.
+struct XentCall {
+  XentTile A;
+  const char* op;       // "catalogue_xent" / "sampled_xent"
+  const char* classes;  // what a class is called in messages
+  float* scratch;
+  int64_t scratch_floats;
+  int splits_n, splits_rows;  // class splits (FWD / DP), row splits (DT)
+  int extra_dp;               // dP partials written after the class splits' (sampled: the positive term)
+  float* row_loss;
+  float* loss;
+  float* dP;  // [R, ld_p]
+  float* dT;  // [n, ld_t]
+};
+
+// scratch layout in 4-byte words (mirrored by ops._xent_plan): the row lists, nv, then the forward's (max, sum-exp) per
+// split and valid row, or the backward's dP partials [splits_n + extra_dp][R][ldo] and, with more than one row split,
+// the class operand's partials [splits_rows][n][ldo]
+struct XentLayout {
+  int64_t ridx, rpos, nv, part, part2, total;
+};
+inline XentLayout xt_layout(const XentCall& C, bool bwd) {
+  XentLayout L;
+  const int64_t R = C.A.R, ldo = (C.A.d + 3) / 4 * 4;
+  L.ridx = 0;
+  L.rpos = cx_r64(R);
+  L.nv = 2 * cx_r64(R);
+  L.part = L.nv + 64;
+  if (!bwd) {
+    L.part2 = L.part + cx_r64((int64_t)C.splits_n * R);
+    L.total = L.part2 + cx_r64((int64_t)C.splits_n * R);
+  } else {
+    L.part2 = L.part + cx_r64((int64_t)(C.splits_n + C.extra_dp) * R * ldo);
+    L.total = L.part2 + (C.splits_rows > 1 ? cx_r64((int64_t)C.splits_rows * C.A.n * ldo) : 0);
+  }
+  return L;
+}
+
+// the checks both descriptors share (each entry point checks its own operands and outputs beside these)
+inline int xt_check(const XentCall& C, const char* pass, bool bwd) {
+  const XentTile& A = C.A;
+  CARCA_CHECK_ARG(A.R >= 1 && A.n >= 1 && A.n_items >= 1 && A.d >= 1, "%s_%s: the row, %s and item counts and d must be positive",
+                  C.op, pass, C.classes);
+  CARCA_CHECK_SUPPORTED(A.d <= XT_MAX_D, "%s_%s: d = %d exceeds %d", C.op, pass, A.d, XT_MAX_D);
+  CARCA_CHECK_ARG(A.P && A.T && A.pos && C.scratch, "%s_%s: null P, %s operand, pos or scratch", C.op, pass, C.classes);
+  CARCA_CHECK_ARG(A.ld_p >= A.d && A.ld_p % 4 == 0 && A.ld_t >= A.d && A.ld_t % 4 == 0,
+                  "%s_%s: the row strides must be multiples of 4, at least d", C.op, pass);
+  CARCA_CHECK_ARG(((uintptr_t)A.P & 15) == 0 && ((uintptr_t)A.T & 15) == 0, "%s_%s: P and the %s operand must be 16-byte aligned",
+                  C.op, pass, C.classes);
+  CARCA_CHECK_ARG(C.splits_n >= 1 && C.splits_n <= XT_MAX_SPLITS && C.splits_rows >= 1 && C.splits_rows <= XT_MAX_SPLITS,
+                  "%s_%s: split counts outside 1..%d", C.op, pass, XT_MAX_SPLITS);
+  CARCA_CHECK_ARG(A.per_split >= 1 && A.per_split % XT_TILE == 0 && (int64_t)A.per_split * C.splits_n >= A.n,
+                  "%s_%s: %s per split must be a multiple of %d covering all of them in the given splits", C.op, pass,
+                  C.classes, XT_TILE);
+  CARCA_CHECK_SUPPORTED((int64_t)A.n * A.ld_t < (1ll << 40) && (int64_t)A.R * A.ld_p < (1ll << 40),
+                        "%s_%s: operands too large", C.op, pass);
+  const XentLayout L = xt_layout(C, bwd);
+  CARCA_CHECK_ARG(C.scratch_floats >= L.total, "%s_%s: scratch of %lld floats, %lld needed", C.op, pass,
+                  (long long)C.scratch_floats, (long long)L.total);
+  CARCA_CHECK_ARG(A.lse, "%s_%s: null lse", C.op, pass);
+  if (!bwd) {
+    CARCA_CHECK_ARG(C.row_loss && C.loss, "%s_%s: null row_loss or loss", C.op, pass);
+  } else {
+    CARCA_CHECK_ARG(A.grad && C.dP && C.dT, "%s_%s: null grad or gradient output", C.op, pass);
+  }
+  return CARCA_OK;
+}
+
+// the tile kernels of one mode, built for d <= 64, 128, 256 (NCB = 4, 8, 16)
+using XentKernel = void (*)(XentTile);
+struct XentKernels {
+  XentKernel k4, k8, k16;
+};
+#define XT_KERNELS(kernel, MODE) (XentKernels{kernel<MODE, 4>, kernel<MODE, 8>, kernel<MODE, 16>})
+
+inline int xt_launch_tile(const XentCall& C, const XentKernels& K, const XentTile& A, int own_entries, hipStream_t stream) {
+  const size_t lds = (size_t)2 * XT_TILE * A.pitch * sizeof(float) + XT_TILE * (sizeof(float) + sizeof(int));
+  const XentKernel kern = A.d <= 64 ? K.k4 : A.d <= 128 ? K.k8 : K.k16;
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    carca_set_error("%s: cannot reserve %zu B of LDS: %s", C.op, lds, hipGetErrorString(e));
+    return (int)e;
+  }
+  hipLaunchKernelGGL(kern, dim3((own_entries + XT_TILE - 1) / XT_TILE, A.splits), dim3(XT_THREADS), lds, stream, A);
+  CARCA_LAUNCH_CHECK();
+  return CARCA_OK;
+}
+
+// the scratch pointers of a call's tile arguments, the LDS pitch, and the compact launch every call starts with
+inline int xt_begin(XentCall& C, const XentLayout& L, hipStream_t stream) {
+  int32_t* base = reinterpret_cast<int32_t*>(C.scratch);
+  C.A.ridx = base + L.ridx, C.A.nv = base + L.nv;
+  C.A.pitch = round_up(C.A.d, 16) + 4;  // (+4 floats: the 16 rows of a 16-byte LDS read start 4 banks apart)
+  hipLaunchKernelGGL(cx_compact_kernel, dim3(1), dim3(CX_COMPACT_THREADS), 0, stream, C.A.pos, C.A.R, C.A.n_items,
+                     base + L.ridx, base + L.rpos, base + L.nv);
+  CARCA_LAUNCH_CHECK();
+  return CARCA_OK;
+}
+
+// forward: compact, FWD tile, merge(rpos, part_m, part_s) (the caller's launch: lse and row_loss), the fp64 mean
+template <class Merge>
+int xt_forward(XentCall& C, const XentKernels& fwd, hipStream_t stream, Merge merge) {
+  int rc = xt_check(C, "fwd", false);
+  if (rc != CARCA_OK) return rc;
+  const XentLayout L = xt_layout(C, false);
+  if ((rc = xt_begin(C, L, stream)) != CARCA_OK) return rc;
+  XentTile A = C.A;
+  A.splits = C.splits_n;
+  A.part_m = C.scratch + L.part;
+  A.part_s = C.scratch + L.part2;
+  if ((rc = xt_launch_tile(C, fwd, A, A.R, stream)) != CARCA_OK) return rc;
+  merge(reinterpret_cast<const int32_t*>(C.scratch) + L.rpos, A.part_m, A.part_s);
+  CARCA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cx_mean_kernel, dim3(1), dim3(1024), 0, stream, C.row_loss, A.R, C.loss, A.nv);
+  CARCA_LAUNCH_CHECK();
+  return CARCA_OK;
+}
+
+// a tile launch whose `splits` partials (A.out) cx_reduce_kernel then sums into dst [rows, ld_dst] with `extra` more
+inline void xt_reduce(const XentTile& A, int extra, const int32_t* rpos, int rows, float* dst, int ld_dst, hipStream_t stream) {
+  const int64_t n = (int64_t)rows * ld_dst;
+  hipLaunchKernelGGL(cx_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A.out, A.out_split_stride,
+                     A.splits + extra, A.ld_out, rpos, rows, A.d, dst, ld_dst, A.nv, A.grad);
+}
+
+// backward: compact; the dP tile, extra(rpos, nv, part, ldo) (the caller's launch writing the extra_dp partials; unused
+// with none), the partials summed per original row (padding rows: 0); the dT tile, where one row split writes dT itself
+// and more write partials summed per class
+template <class Extra>
+int xt_backward(XentCall& C, const XentKernels& dp, const XentKernels& dt, hipStream_t stream, Extra extra) {
+  int rc = xt_check(C, "bwd", true);
+  if (rc != CARCA_OK) return rc;
+  const XentLayout L = xt_layout(C, true);
+  if ((rc = xt_begin(C, L, stream)) != CARCA_OK) return rc;
+  const int ldo = (C.A.d + 3) / 4 * 4;
+  const int32_t* rpos = reinterpret_cast<const int32_t*>(C.scratch) + L.rpos;
+  XentTile A = C.A;
+  A.splits = C.splits_n;
+  A.out = C.scratch + L.part, A.out_split_stride = (int64_t)A.R * ldo, A.ld_out = ldo;
+  if ((rc = xt_launch_tile(C, dp, A, A.R, stream)) != CARCA_OK) return rc;
+  if (C.extra_dp) {
+    extra(rpos, A.nv, A.out + (size_t)C.splits_n * A.out_split_stride, ldo);
+    CARCA_LAUNCH_CHECK();
+  }
+  xt_reduce(A, C.extra_dp, rpos, A.R, C.dP, A.ld_p, stream);
+  CARCA_LAUNCH_CHECK();
+  XentTile B = C.A;
+  B.splits = C.splits_rows;
+  if (C.splits_rows == 1) {
+    B.out = C.dT, B.out_split_stride = 0, B.ld_out = B.ld_t, B.final_out = 1;
+  } else {
+    B.out = C.scratch + L.part2, B.out_split_stride = (int64_t)B.n * ldo, B.ld_out = ldo;
+  }
+  if ((rc = xt_launch_tile(C, dt, B, B.n, stream)) != CARCA_OK) return rc;
+  if (C.splits_rows > 1) {
+    xt_reduce(B, 0, nullptr, B.n, C.dT, B.ld_t, stream);
+    CARCA_LAUNCH_CHECK();
+  }
+  return CARCA_OK;
+}
+
+}  // namespace

@@ -1351,32 +1351,41 @@ def split_bind(w: Optional[Tensor], planes: Optional[Tensor], mode: int = 0, K0:
 # --------------------------------------------------------------------------------------------------
 # full-catalogue softmax cross-entropy (carca_catalogue_xent_fwd / _bwd)
 # --------------------------------------------------------------------------------------------------
-CX_TILE = 64        # rows of a workgroup's own tile and of each streamed tile (csrc/catalogue_xent.hip)
+CX_TILE = 64        # rows of a workgroup's own tile and of each streamed tile (csrc/xent_tile.h)
 CX_MAX_SPLITS = 256
 CX_WAVES_PER_CU = 4  # the split counts aim at this many workgroups per CU
 
 
-def catalogue_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
-    """Host-side sizing of carca_catalogue_xent_fwd / _bwd (pure: no device).  The item range is split so that the
-    forward's and dP's (row block x item split) grid has about CX_WAVES_PER_CU workgroups per CU, the rows of dT's
-    (item block x row split) grid likewise.  Returns the split counts and the scratch each call needs, in 4-byte words
-    (the layout csrc/catalogue_xent.hip checks): 2 ceil64(R) + 64 words of row lists, then the forward's (max, sum-exp)
-    partials, or the backward's dP partials [splits_items, R, ld] and, with more than one row split, dT partials
-    [splits_rows, n_items, ld], ld = round_up(d, 4)."""
-    if R < 1 or n_items < 1 or d < 1:
-        raise CarcaHipError("catalogue_xent_plan: R, n_items and d must be positive")
+def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: int) -> Tuple[int, int, int, int, int]:
+    """(class splits, classes per split, row splits, forward scratch, backward scratch) of either loss, the layout
+    csrc/xent_tile.h checks.  The classes are split so that the forward's and dP's (row block x class split) grid has about
+    CX_WAVES_PER_CU workgroups per CU, the rows of the class gradient's (class block x row split) grid likewise.  Scratch in
+    4-byte words: 2 ceil64(R) + 64 of row lists, then the forward's (max, sum-exp) partials, or the backward's dP partials
+    [class splits + extra_dp_partials, R, ld] and, with more than one row split, the class gradient's
+    [row splits, n_classes, ld], ld = round_up(d, 4)."""
     r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
     ldo = (d + 3) // 4 * 4
     target = CX_WAVES_PER_CU * max(1, int(n_cus))
     n_row_blocks = -(-R // CX_TILE)
-    n_item_blocks = -(-n_items // CX_TILE)
-    s_i = max(1, min(n_item_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
-    per = -(-n_item_blocks // s_i) * CX_TILE
-    s_i = -(-n_items // per)  # (no empty split)
-    s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_item_blocks)))
+    n_class_blocks = -(-n_classes // CX_TILE)
+    s_c = max(1, min(n_class_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
+    per = -(-n_class_blocks // s_c) * CX_TILE
+    s_c = -(-n_classes // per)  # (no empty split)
+    s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_class_blocks)))
     head = 2 * r64(R) + 64
-    fwd = head + 2 * r64(s_i * R)
-    bwd = head + r64(s_i * R * ldo) + (r64(s_r * n_items * ldo) if s_r > 1 else 0)
+    fwd = head + 2 * r64(s_c * R)
+    bwd = head + r64((s_c + extra_dp_partials) * R * ldo) + (r64(s_r * n_classes * ldo) if s_r > 1 else 0)
+    return s_c, per, s_r, fwd, bwd
+
+
+def catalogue_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_catalogue_xent_fwd / _bwd (pure: no device): _xent_plan with the catalogue's items as
+    the classes.  Returns the split counts and the scratch each call needs, in 4-byte words: the row lists, then the
+    forward's (max, sum-exp) partials, or the backward's dP partials [splits_items, R, ld] and, with more than one row
+    split, dT partials [splits_rows, n_items, ld], ld = round_up(d, 4)."""
+    if R < 1 or n_items < 1 or d < 1:
+        raise CarcaHipError("catalogue_xent_plan: R, n_items and d must be positive")
+    s_i, per, s_r, fwd, bwd = _xent_plan(R, n_items, d, n_cus, 0)
     return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
 
 
@@ -1392,16 +1401,22 @@ def _xent_operand(x: Tensor, d: int, what: str = "catalogue_xent") -> Tensor:
     return out
 
 
+def _xent_splits(D, plan: dict, split_fields, scratch_key: str, device, keep: list):
+    """Fill D's three split fields from plan's entries of the same names and give it scratch of plan[scratch_key] words."""
+    for f in split_fields:
+        setattr(D, f, plan[f])
+    # scratch through torch's caching allocator (max_memory_allocated sees it); freed when the call returns
+    scratch = torch.empty(plan[scratch_key], dtype=torch.float32, device=device)
+    keep.append(scratch)
+    D.scratch, D.scratch_floats = scratch.data_ptr(), scratch.numel()
+    return D
+
+
 def _xent_desc(P: Tensor, T: Tensor, pos: Tensor, d: int, scratch_key: str, plan: dict, keep: list):
     D = _lib.CatalogueXentDesc()
     D.R, D.n_items, D.d = P.shape[0], T.shape[0], d
     D.P, D.ld_p, D.T, D.ld_t, D.pos = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0), pos.data_ptr()
-    D.splits_items, D.items_per_split, D.splits_rows = plan["splits_items"], plan["items_per_split"], plan["splits_rows"]
-    # scratch through torch's caching allocator (max_memory_allocated sees it); freed when the call returns
-    scratch = torch.empty(plan[scratch_key], dtype=torch.float32, device=P.device)
-    keep.append(scratch)
-    D.scratch, D.scratch_floats = scratch.data_ptr(), scratch.numel()
-    return D
+    return _xent_splits(D, plan, ("splits_items", "items_per_split", "splits_rows"), scratch_key, P.device, keep)
 
 
 def catalogue_xent_fwd(P: Tensor, T: Tensor, pos: Tensor, d: int) -> Tuple[Tensor, Tensor]:
@@ -1472,48 +1487,15 @@ def catalogue_xent(P: Tensor, T: Tensor, pos: Tensor) -> Tensor:
 # --------------------------------------------------------------------------------------------------
 # sampled softmax cross-entropy with the logQ correction (carca_sampled_xent_fwd / _bwd)
 # --------------------------------------------------------------------------------------------------
-SX_TILE = 64  # rows of a workgroup's own tile and of each streamed tile (csrc/sampled_xent.hip)
-
-
 def sampled_xent_plan(R: int, K: int, d: int, n_cus: int = 256) -> dict:
-    """Host-side sizing of carca_sampled_xent_fwd / _bwd (pure: no device), catalogue_xent_plan's with the K samples in
-    place of the catalogue: the samples are split so that the forward's and dP's (row block x sample split) grid has about
-    CX_WAVES_PER_CU workgroups per CU, the rows of dS's (sample block x row split) grid likewise.  Returns the split counts
-    and the scratch each call needs, in 4-byte words (the layout csrc/sampled_xent.hip checks): 2 ceil64(R) + 64 words of
-    row lists, then the forward's (max, sum-exp) partials, or the backward's dP partials [splits_samples + 1, R, ld] (the
-    last: the positive term) and, with more than one row split, dS partials [splits_rows, K, ld], ld = round_up(d, 4)."""
+    """Host-side sizing of carca_sampled_xent_fwd / _bwd (pure: no device): _xent_plan with the K samples as the classes
+    and one more dP partial.  Returns the split counts and the scratch each call needs, in 4-byte words: the row lists,
+    then the forward's (max, sum-exp) partials, or the backward's dP partials [splits_samples + 1, R, ld] (the last: the
+    positive term) and, with more than one row split, dS partials [splits_rows, K, ld], ld = round_up(d, 4)."""
     if R < 1 or K < 1 or d < 1:
         raise CarcaHipError("sampled_xent_plan: R, K and d must be positive")
-    r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
-    ldo = (d + 3) // 4 * 4
-    target = CX_WAVES_PER_CU * max(1, int(n_cus))
-    n_row_blocks = -(-R // SX_TILE)
-    n_sample_blocks = -(-K // SX_TILE)
-    s_s = max(1, min(n_sample_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
-    per = -(-n_sample_blocks // s_s) * SX_TILE
-    s_s = -(-K // per)  # (no empty split)
-    s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_sample_blocks)))
-    head = 2 * r64(R) + 64
-    fwd = head + 2 * r64(s_s * R)
-    bwd = head + r64((s_s + 1) * R * ldo) + (r64(s_r * K * ldo) if s_r > 1 else 0)
+    s_s, per, s_r, fwd, bwd = _xent_plan(R, K, d, n_cus, 1)
     return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
-
-
-def _sx_desc(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int, d: int,
-             scratch_key: str, keep: list):
-    R, K = P.shape[0], S.shape[0]
-    plan = sampled_xent_plan(R, K, d, num_cus())
-    D = _lib.SampledXentDesc()
-    D.R, D.K, D.n_items, D.d = R, K, int(n_items), d
-    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
-    D.bp, D.pos, D.s_ids, D.bs = bp.data_ptr(), pos.data_ptr(), s_ids.data_ptr(), bs.data_ptr()
-    D.splits_samples, D.samples_per_split = plan["splits_samples"], plan["samples_per_split"]
-    D.splits_rows = plan["splits_rows"]
-    # scratch through torch's caching allocator (max_memory_allocated sees it); freed when the call returns
-    scratch = torch.empty(plan[scratch_key], dtype=torch.float32, device=P.device)
-    keep.append(scratch)
-    D.scratch, D.scratch_floats = scratch.data_ptr(), scratch.numel()
-    return D
 
 
 def _sx_vec(t: Tensor, n: int, name: str, ids: bool) -> Tensor:
@@ -1523,18 +1505,29 @@ def _sx_vec(t: Tensor, n: int, name: str, ids: bool) -> Tensor:
     return _ids32(t) if ids else _f32(t)
 
 
+def _sx_desc(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int, d: int,
+             scratch_key: str, keep: list):
+    R, K = P.shape[0], S.shape[0]
+    bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
+    pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
+    keep += [bp, bs, pos, s_ids]
+    D = _lib.SampledXentDesc()
+    D.R, D.K, D.n_items, D.d = R, K, int(n_items), d
+    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
+    D.bp, D.pos, D.s_ids, D.bs = bp.data_ptr(), pos.data_ptr(), s_ids.data_ptr(), bs.data_ptr()
+    plan = sampled_xent_plan(R, K, d, num_cus())
+    return _xent_splits(D, plan, ("splits_samples", "samples_per_split", "splits_rows"), scratch_key, P.device, keep)
+
+
 def sampled_xent_fwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int,
                      d: int) -> Tuple[Tensor, Tensor, Tensor]:
     """Mean sampled softmax cross-entropy (include/carca_hip.h: carca_sampled_xent_fwd) of rows P [R, ld_p] with positives
     Tp [R, ld_tp] against the shared samples S [K, ld_s] (first d columns, strides multiples of 4): pos [R] and
     s_ids [K] int32, bp [R] and bs [K] the logQ corrections.  Returns (loss [1], lse [R], row_loss [R]); no host wait."""
     _need_cuda(P, Tp, bp, pos, S, s_ids, bs)
-    R, K = P.shape[0], S.shape[0]
-    bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
-    pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
-    keep: list = [bp, bs, pos, s_ids]
+    keep: list = []
     D = _sx_desc(P, Tp, bp, pos, S, s_ids, bs, n_items, d, "scratch_fwd", keep)
-    lse = torch.empty(R, dtype=torch.float32, device=P.device)
+    lse = torch.empty(P.shape[0], dtype=torch.float32, device=P.device)
     row_loss = torch.empty_like(lse)
     loss = torch.empty(1, dtype=torch.float32, device=P.device)
     D.lse, D.row_loss, D.loss = lse.data_ptr(), row_loss.data_ptr(), loss.data_ptr()
@@ -1546,15 +1539,12 @@ def sampled_xent_bwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, 
                      lse: Tensor, row_loss: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor]:
     """(dP [R, ld_p], dTp [R, ld_tp], dS [K, ld_s]) of sampled_xent_fwd's loss scaled by grad [1] (device); zeros past d."""
     _need_cuda(P, Tp, bp, pos, S, s_ids, bs, lse, row_loss, grad)
-    R, K = P.shape[0], S.shape[0]
-    bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
-    pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
-    keep: list = [bp, bs, pos, s_ids]
+    keep: list = []
     D = _sx_desc(P, Tp, bp, pos, S, s_ids, bs, n_items, d, "scratch_bwd", keep)
     g = _f32(grad.reshape(1))
-    dP = torch.empty(R, P.stride(0), dtype=torch.float32, device=P.device)
-    dTp = torch.empty(R, Tp.stride(0), dtype=torch.float32, device=P.device)
-    dS = torch.empty(K, S.stride(0), dtype=torch.float32, device=P.device)
+    dP = torch.empty(P.shape[0], P.stride(0), dtype=torch.float32, device=P.device)
+    dTp = torch.empty(P.shape[0], Tp.stride(0), dtype=torch.float32, device=P.device)
+    dS = torch.empty(S.shape[0], S.stride(0), dtype=torch.float32, device=P.device)
     D.lse, D.row_loss, D.grad = lse.data_ptr(), row_loss.data_ptr(), g.data_ptr()
     D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
     _lib.check(_lib.load().carca_sampled_xent_bwd(C.byref(D), _stream()), "sampled_xent_bwd")
