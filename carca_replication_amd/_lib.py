@@ -21,7 +21,7 @@ _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip"]
 HEADERS = ["carca_common.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "xent_tile.h"]
+           "catalogue_sweep.h", "xent_tile.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -231,28 +231,25 @@ class ForwardDesc(C.Structure):
 
 # name -> (restype, argtypes); every symbol include/carca_hip.h declares
 _i, _f = C.c_int, C.c_float
+# the model-side and exclusion fields of CarcaRecommendDesc / CarcaRankDesc, `decoder` through `ld_exclude`
+_CARCA_MODEL = [("decoder", C.c_int32), ("p_ids", _fp), ("ld_p_ids", C.c_int32), ("item_q", _fp), ("ld_item_q", C.c_int32),
+                ("item_w", _fp), ("ld_item_w", C.c_int32), ("user_k", _fp), ("ld_user_k", C.c_int32), ("user_u", _fp),
+                ("ld_user_u", C.c_int32), ("user_q", _fp), ("ld_user_q", C.c_int32), ("user_m", _fp),
+                ("ld_user_m", C.c_int32), ("user_off", _fp), ("ld_user_off", C.c_int32), ("ffn_b", _fp), ("exclude", _fp),
+                ("n_exclude", C.c_int32), ("ld_exclude", C.c_int32)]
+_TOPK_OUT = [("scores", _fp), ("ld_scores", C.c_int32), ("ids_out", _fp), ("ld_ids_out", C.c_int32)]
+_RANK_OUT = [("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("scores", _fp), ("ld_scores", C.c_int32),
+             ("ranks", _fp), ("ld_ranks", C.c_int32)]
+
+
 class RecommendDesc(C.Structure):
     """CarcaRecommendDesc (carca_recommend)."""
-    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("H", C.c_int32),
-                ("k", C.c_int32), ("decoder", C.c_int32), ("p_ids", _fp), ("ld_p_ids", C.c_int32), ("item_q", _fp),
-                ("ld_item_q", C.c_int32), ("item_w", _fp), ("ld_item_w", C.c_int32), ("user_k", _fp),
-                ("ld_user_k", C.c_int32), ("user_u", _fp), ("ld_user_u", C.c_int32), ("user_q", _fp),
-                ("ld_user_q", C.c_int32), ("user_m", _fp), ("ld_user_m", C.c_int32), ("user_off", _fp),
-                ("ld_user_off", C.c_int32), ("ffn_b", _fp), ("exclude", _fp), ("n_exclude", C.c_int32),
-                ("ld_exclude", C.c_int32), ("scores", _fp), ("ld_scores", C.c_int32), ("ids_out", _fp),
-                ("ld_ids_out", C.c_int32)]
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "d", "H", "k")] + _CARCA_MODEL + _TOPK_OUT
 
 
 class RankDesc(C.Structure):
     """CarcaRankDesc (carca_rank_items)."""
-    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("H", C.c_int32),
-                ("decoder", C.c_int32), ("p_ids", _fp), ("ld_p_ids", C.c_int32), ("item_q", _fp),
-                ("ld_item_q", C.c_int32), ("item_w", _fp), ("ld_item_w", C.c_int32), ("user_k", _fp),
-                ("ld_user_k", C.c_int32), ("user_u", _fp), ("ld_user_u", C.c_int32), ("user_q", _fp),
-                ("ld_user_q", C.c_int32), ("user_m", _fp), ("ld_user_m", C.c_int32), ("user_off", _fp),
-                ("ld_user_off", C.c_int32), ("ffn_b", _fp), ("exclude", _fp), ("n_exclude", C.c_int32),
-                ("ld_exclude", C.c_int32), ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32),
-                ("scores", _fp), ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)]
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "d", "H")] + _CARCA_MODEL + _RANK_OUT
 
 
 _KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_user_a", C.c_int64), ("table", _fp),
@@ -262,15 +259,12 @@ _KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_use
 
 class KnnRecommendDesc(C.Structure):
     """CarcaKnnRecommendDesc (carca_knn_recommend)."""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "n_items", "F", "k")] + _KNN_MODEL +
-                [("scores", _fp), ("ld_scores", C.c_int32), ("ids_out", _fp), ("ld_ids_out", C.c_int32)])
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "F", "k")] + _KNN_MODEL + _TOPK_OUT
 
 
 class KnnRankDesc(C.Structure):
     """CarcaKnnRankDesc (carca_knn_rank_items)."""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "n_items", "F")] + _KNN_MODEL +
-                [("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("scores", _fp),
-                 ("ld_scores", C.c_int32), ("ranks", _fp), ("ld_ranks", C.c_int32)])
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "F")] + _KNN_MODEL + _RANK_OUT
 
 class CatalogueXentDesc(C.Structure):
     """CarcaCatalogueXentDesc (carca_catalogue_xent_fwd / _bwd)."""

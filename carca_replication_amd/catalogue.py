@@ -1,0 +1,195 @@
+"""Host side of the full-catalogue top-k and rank calls (CARCA.recommend / rank_items, KNN.recommend / rank_items;
+DESIGN.md sections 10-12).  A call fills the model side of a descriptor (carca_model_side or knn_model_side: what scores
+a (user, item) pair), then does what the four share -- the k / items checks, the exclusion list, the outputs and the
+launch (recommend, rank_items).  A model's two descriptors name their model-side and exclusion fields alike
+(include/carca_hip.h), so one function fills both."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _lib, ops
+from ._lib import CarcaHipError
+
+KMAX = 128  # largest k of recommend and largest list of rank_items (csrc: rc::RC_KMAX, rc::LIST_MAX)
+
+
+def carca_model_side(model, profile, context: Optional[Tensor], what: str, D) -> Tuple[list, Tensor]:
+    """Checks the envelope of CARCA.recommend / rank_items and fills the model-side fields of D (RecommendDesc or RankDesc)
+    -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path of forward
+    (embed_segments + the fused blocks + the final LayerNorm), then K, V -> u, M c, dq and w . M c.  Returns (the tensors
+    D points into, kept alive by the caller until the launch is queued; the profile ids as int32).  Call under no_grad."""
+    from .modules import CrossAttentionBlock, DotProduct, WeightedDotProduct
+
+    p_x, p_a, p_c = profile
+    ops._need_cuda(p_x, p_a, p_c, context)
+    B, L = p_x.shape
+    if L > _lib.MAX_L:
+        raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}")
+    emb, dec = model.embeds, model.decoder
+    d = emb.d
+    bad = [H for H in model._attn_heads() if d > ops.FUSED_MAX_D or not ops.attn_geometry_built(d, H)]
+    if bad:
+        raise CarcaHipError(f"{what}: (d, H) = ({d}, {bad[0]}) has no fused attention kernel built "
+                            "(CARCA_ATT_GEOMETRIES in csrc/attn_common.h)")
+    ca = isinstance(dec, CrossAttentionBlock)
+    if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
+        raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
+    n_ctx = context.shape[-1] if context is not None else 0
+    if context is not None and tuple(context.shape) != (B, n_ctx):
+        raise CarcaHipError(f"{what}: context must be [B, n_ctx], got {tuple(context.shape)}")
+    T = emb.item_table()
+    n_items = T.shape[0]
+    M = emb.context_matrix(n_ctx)
+    H = dec.attn.H if ca else model._heads()
+    dpi, _, _ = ops.padded_dims(d, H)
+    ld = ops.row_ld(d)
+    # profile side: the encoder path of forward (embed_segments + the fused blocks + the final LayerNorm)
+    es, _ = emb.embed_segments([(p_x, p_a, p_c, False)], ld_e=dpi)
+    x = es[0]
+    for blk in model.encoder:
+        blk._check_mode()
+        x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
+    p_n = ops.layernorm_fwd(x.reshape(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)
+    mc = None
+    if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
+        (mc,) = ops.gemm_rows([dict(a0=ops._f32(context))], M, d, n_ctx, ld)
+    p_ids = ops._ids32(p_x)
+    keep = [T, p_ids, p_n, mc]
+    D.B, D.L, D.n_items, D.d, D.H = B, L, n_items, d, H
+    D.p_ids, D.ld_p_ids = p_ids.data_ptr(), L
+    if ca:
+        qt, wt, wd = dec.recommend_tables(T)
+        a = dec.attn
+        (kk,) = ops.gemm_rows([dict(a0=p_n)], a.WK.weight.detach(), d, d, ld, bias=a.WK.bias.detach())
+        (vv,) = ops.gemm_rows([dict(a0=p_n)], a.WV.weight.detach(), d, d, ld, bias=a.WV.bias.detach())
+        (uu,) = ops.gemm_rows([dict(a0=vv)], wd, H, d, 4)  # u_lh = w_h . V_lh (the decoder FFN folded in)
+        keep += [qt, wt, kk, uu]
+        D.decoder = 0
+        D.item_q, D.ld_item_q = qt.data_ptr(), qt.stride(0)
+        D.user_k, D.ld_user_k, D.user_u, D.ld_user_u = kk.data_ptr(), kk.stride(0), uu.data_ptr(), uu.stride(0)
+        D.ffn_b = dec.ffn.bias.data_ptr()
+        if dec.residual:
+            D.item_w, D.ld_item_w = wt.data_ptr(), wt.stride(0)
+        if mc is not None:
+            (dq,) = ops.gemm_rows([dict(a0=mc)], a.WQ.weight.detach(), d, d, ld)  # (M c_u) W_Q^T
+            keep.append(dq)
+            D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
+            if dec.residual:
+                (off,) = ops.gemm_rows([dict(a0=mc)], dec.ffn.weight.detach(), 1, d, 4)  # w_ffn . M c_u
+                keep.append(off)
+                D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
+    else:
+        rows = p_n
+        D.decoder = 1
+        if isinstance(dec, WeightedDotProduct):  # carca.py:385-389
+            rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi)
+            if dec.norm:
+                rows = ops.l2norm_fwd(rows, d, dpi)
+                D.decoder = 2
+        keep.append(rows)
+        last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
+        D.item_q, D.ld_item_q = T.data_ptr(), T.stride(0)
+        D.user_q, D.ld_user_q = last.data_ptr(), last.stride(0)
+        if mc is not None:
+            D.user_m, D.ld_user_m = mc.data_ptr(), mc.stride(0)
+    return keep, p_ids
+
+
+def knn_model_side(model, profile, what: str, D) -> Tuple[list, Tensor]:
+    """Fills the model-side fields of a KnnRecommendDesc / KnnRankDesc: the catalogue is the registered table [n_items, F]
+    (fp32, contiguous rows) with its int8 copy where it qualifies (table mode only), the query p_a[:, L-1] when p_a is
+    given (dense), else the table row of p_x[:, L-1].  Returns (the tensors D points into, p_x as int32)."""
+    table = model._attr_table
+    if table is None:
+        raise CarcaHipError(f"{what}: no attribute table registered -- call register_attr_table(attrs) with the "
+                            "[n_items, n_attrs] item-attribute matrix first (the catalogue is its rows)")
+    p_x, p_a, _ = profile
+    ops._need_cuda(table, p_x, p_a)
+    B, L = p_x.shape
+    n_items, F = table.shape
+    p_ids = ops._ids32(p_x)
+    keep = [table, p_ids]
+    D.B, D.L, D.n_items, D.F = B, L, n_items, F
+    D.p_ids, D.ld_p_ids = p_ids.data_ptr(), p_ids.stride(0)
+    D.table, D.ld_table = table.data_ptr(), table.stride(0)
+    if p_a is not None:
+        if p_a.dim() != 3 or p_a.shape[0] != B or p_a.shape[2] != F:
+            raise CarcaHipError(f"{what}: p_a {tuple(p_a.shape)} does not match [B, L, F] = [{B}, {L}, {F}]")
+        q = p_a[:, -1]
+        if q.dtype != torch.float32 or q.stride(-1) != 1:
+            q = q.to(torch.float32).contiguous()
+        keep.append(q)
+        D.user_a, D.ld_user_a = q.data_ptr(), q.stride(0)
+    else:
+        table_i8 = model.int8_table()
+        if table_i8 is not None:
+            keep.append(table_i8)
+            D.table_i8, D.ld_table_i8 = table_i8.data_ptr(), table_i8.stride(0)
+    return keep, p_ids
+
+
+def _ids32_clamped(ids: Tensor, n_items: int) -> Tensor:  # (clamped first: no int64 id wraps into range on the way to int32)
+    return ops._ids32(ids if ids.dtype == torch.int32 else ids.clamp(-1, n_items))
+
+
+def _exclusion(what: str, exclude, p_ids: Tensor, D, keep: list, clamp: bool) -> None:
+    """exclude ("profile", None or an int [B, E] tensor) -> D.exclude / n_exclude / ld_exclude.  clamp: as _ids32_clamped
+    (the rank call; the top-k call casts as it always has, without the extra launch)."""
+    if isinstance(exclude, str):
+        if exclude != "profile":
+            raise CarcaHipError(f'{what}: exclude must be "profile", None or an int [B, E] tensor')
+        excl = p_ids
+    elif exclude is None:
+        return
+    else:
+        ops._need_cuda(exclude)
+        if exclude.dim() != 2 or exclude.shape[0] != D.B or exclude.is_floating_point():
+            raise CarcaHipError(f"{what}: exclude must be an int [B, E] tensor")
+        excl = _ids32_clamped(exclude, D.n_items) if clamp else ops._ids32(exclude)
+    if excl.shape[1] > 0:
+        keep.append(excl)
+        D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
+
+
+def _launch(what: str, D, entry: str, second: str, n: int, device) -> Tuple[Tensor, Tensor]:
+    """Points D.scores and D.<second> at fresh [B, n] outputs (float32, int64) and queues the C entry point."""
+    outs = (torch.empty(D.B, n, dtype=torch.float32, device=device), torch.empty(D.B, n, dtype=torch.int64, device=device))
+    for name, t in zip(("scores", second), outs):
+        setattr(D, name, t.data_ptr())
+        setattr(D, "ld_" + name, n)
+    _lib.check(getattr(_lib.load(), entry)(C.byref(D), ops._stream()), what)
+    return outs
+
+
+def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, exclude) -> Tuple[Tensor, Tensor]:
+    """The top-k call: desc the descriptor class, entry its C entry point, fill(what, D) -> (keep, p_ids) the model side."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    with torch.no_grad():
+        D = desc()
+        keep, p_ids = fill(what, D)
+        D.k = int(k)
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        return _launch(what, D, entry, "ids_out", int(k), profile[0].device)
+
+
+def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tensor, exclude) -> Tuple[Tensor, Tensor]:
+    """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""
+    ops._need_cuda(items)
+    if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
+        raise CarcaHipError(f"{what}: items must be an int [B, N] tensor")
+    N = items.shape[1]
+    if not 1 <= N <= KMAX:
+        raise CarcaHipError(f"{what}: N = {N} items per user outside 1..{KMAX}")
+    with torch.no_grad():
+        D = desc()
+        keep, p_ids = fill(what, D)
+        _exclusion(what, exclude, p_ids, D, keep, clamp=True)
+        lst = _ids32_clamped(items, D.n_items)
+        keep.append(lst)
+        D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
+        return _launch(what, D, entry, "ranks", N, profile[0].device)

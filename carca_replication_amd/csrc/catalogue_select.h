@@ -2,7 +2,8 @@
 // carca_recommend (recommend.hip) and carca_knn_recommend (knn_catalogue.hip).  Desc is the caller's descriptor, or a view
 // with these fields: n_items, k, decoder, exclude / n_exclude / ld_exclude, scores / ld_scores, ids_out / ld_ids_out.
 // `decoder` picks the link applied to the k selected logits: an int (recommend_common.h: rc::link) or rc::IdentityLink
-// (the raw logit, for models without a link).
+// (the raw logit, for models without a link).  Keys are built and taken apart by recommend_common.h's helpers
+// (rc::order_key, rc::key_id); an item whose order bits are 0 holds the exclusion sentinel and is skipped.
 #pragma once
 #include "recommend_common.h"
 
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(Desc D, const
     for (int i = tid; i < n; i += RC_SEL_THREADS) {
       const unsigned o = rc::order_bits(row[i]);
       if (o == 0u) continue;  // sentinel: excluded
-      const unsigned long long key = ((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
+      const unsigned long long key = rc::order_key(o, (unsigned)i);
       if (pbits > 0 && (key >> (64 - pbits)) != prefix) continue;
       atomicAdd(&hist[(int)((key >> shift) & 255ull)], 1);
     }
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(Desc D, const
     for (int i = tid; i < n; i += RC_SEL_THREADS) {
       const unsigned o = rc::order_bits(row[i]);
       if (o == 0u) continue;
-      const unsigned long long key = ((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
+      const unsigned long long key = rc::order_key(o, (unsigned)i);
       if ((key >> (64 - pbits)) >= prefix) {
         const int at = atomicAdd(&s_cnt, 1);
         if (at < RC_KMAX) skey[at] = key;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(Desc D, const
     long long id = 0;
     if (tid < keff) {
       const unsigned long long key = skey[tid];
-      id = (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+      id = (long long)rc::key_id(key);
       const float y = rc::unorder_bits((unsigned)(key >> 32));
       score = rc::link(y, D.decoder);
     }

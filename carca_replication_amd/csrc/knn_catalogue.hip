@@ -19,11 +19,11 @@
 //   3. recommend: the exclusion and selection launches of carca_recommend (catalogue_select.h) with no link;
 //      rank_items: the listed items' keys are read from the logit buffer, the exclusion launch overwrites excluded ids
 //      with its sentinel, and a counting sweep adds, per (user, target), the items whose key is larger (ballot +
-//      popcount per wave, one 64-bit integer atomic per workgroup and target).
+//      popcount per wave, one 64-bit integer atomic per workgroup and target: rc::count_larger, catalogue_sweep.h).
 // Both calls take every logit from the same scoring launch, so the item at position r of recommend(k = 128) has rank r
 // and the same score bits.  Integer atomics only: results do not depend on scheduling.
 #include "catalogue_select.h"
-#include "../../include/carca_hip.h"
+#include "catalogue_sweep.h"
 
 #include <type_traits>
 
@@ -36,9 +36,8 @@ constexpr int KC_UB = 16 * KC_MU;         // users per workgroup (and the row pa
 constexpr int KC_IB = 16 * KC_WAVES;      // items per workgroup: 16 per wave
 constexpr int KC_UNROLL = 4;              // 64-byte row chunks in flight per operand
 constexpr int KC_FOLD = 16;               // fp32: chunks per MFMA chain (a multiple of KC_UNROLL)
-constexpr int KC_NMAX = 128;              // largest list of rank_items
 constexpr int KC_CNT_PER_THREAD = 8;      // items per lane in the counting sweep
-constexpr unsigned long long KC_NEVER = ~0ull;  // key of an invalid target: no item orders before it
+static_assert(KC_THREADS == rc::TILE, "rc::count_larger counts over a workgroup of rc::TILE threads");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -209,24 +208,23 @@ __global__ __launch_bounds__(KC_THREADS) void kc_score_kernel(KcScore P) {
 }
 
 // ---- 3b. ranks: list keys, then a counting sweep -----------------------------------------------------------------
-__global__ __launch_bounds__(KC_NMAX) void kc_list_kernel(CarcaKnnRankDesc D, const float* __restrict__ logits,
+__global__ __launch_bounds__(rc::LIST_MAX) void kc_list_kernel(CarcaKnnRankDesc D, const float* __restrict__ logits,
                                                           int64_t ld_s, unsigned long long* __restrict__ tkeys) {
   const int u = blockIdx.x, j = threadIdx.x;
   if (j >= D.n_list) return;
   const int id = D.items[(size_t)u * D.ld_items + j];
   const bool valid = id >= 1 && id < D.n_items;
   const float logit = valid ? logits[(size_t)u * ld_s + id] : 0.f;
-  tkeys[(size_t)u * D.n_list + j] = valid ? rc::item_key(logit, id) : KC_NEVER;
+  tkeys[(size_t)u * D.n_list + j] = valid ? rc::item_key(logit, id) : rc::KEY_NEVER;
   D.scores[(size_t)u * D.ld_scores + j] = logit;
   D.ranks[(size_t)u * D.ld_ranks + j] = valid ? 0 : -1;  // the sweep adds to the valid ones only
 }
 
 __global__ __launch_bounds__(KC_THREADS) void kc_count_kernel(CarcaKnnRankDesc D, const float* __restrict__ logits,
                                                               int64_t ld_s, const unsigned long long* __restrict__ tkeys) {
-  __shared__ unsigned long long tk[KC_NMAX];
-  __shared__ int wcnt[KC_WAVES][KC_NMAX];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, u = blockIdx.y;
-  for (int t = tid; t < D.n_list; t += KC_THREADS) tk[t] = tkeys[(size_t)u * D.n_list + t];
+  __shared__ rc::CountLds C;
+  const int tid = threadIdx.x, u = blockIdx.y;
+  for (int t = tid; t < D.n_list; t += KC_THREADS) C.tkey[t] = tkeys[(size_t)u * D.n_list + t];
   const unsigned* row = reinterpret_cast<const unsigned*>(logits + (size_t)u * ld_s);
   const long long base = (long long)blockIdx.x * KC_THREADS * KC_CNT_PER_THREAD;
   unsigned long long key[KC_CNT_PER_THREAD];
@@ -234,30 +232,10 @@ __global__ __launch_bounds__(KC_THREADS) void kc_count_kernel(CarcaKnnRankDesc D
   for (int j = 0; j < KC_CNT_PER_THREAD; ++j) {  // excluded ids and id 0 hold the sentinel, whose order bits are 0
     const long long i = base + (long long)j * KC_THREADS + tid;
     const unsigned o = i < D.n_items ? rc::order_bits(row[i]) : 0u;
-    key[j] = o ? (((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
+    key[j] = o ? rc::order_key(o, (unsigned)i) : 0ull;
   }
   __syncthreads();
-  int c0 = 0, c1 = 0;  // lane l keeps the wave's count for targets l and l + 64
-  for (int t = 0; t < D.n_list; ++t) {
-    const unsigned long long tkt = tk[t];
-    int pc = 0;
-#pragma unroll
-    for (int j = 0; j < KC_CNT_PER_THREAD; ++j) pc += __popcll(__ballot(key[j] > tkt));
-    if (t < 64) {
-      c0 = lane == t ? pc : c0;
-    } else {
-      c1 = lane == t - 64 ? pc : c1;
-    }
-  }
-  wcnt[w][lane] = c0;
-  wcnt[w][lane + 64] = c1;
-  __syncthreads();
-  if (tid < D.n_list) {
-    int s = 0;
-#pragma unroll
-    for (int v = 0; v < KC_WAVES; ++v) s += wcnt[v][tid];
-    if (s) atomicAdd(reinterpret_cast<unsigned long long*>(&D.ranks[(size_t)u * D.ld_ranks + tid]), (unsigned long long)s);
-  }
+  rc::count_larger(key, D.n_list, D.ranks + (size_t)u * D.ld_ranks, C);
 }
 
 // ---- shared host side ----------------------------------------------------------------------------------------------
@@ -274,9 +252,7 @@ int kc_check(const Desc& D, const char* what) {
                   "%s: dense mode needs ld_user_a >= F, table mode p_ids with ld_p_ids >= L", what);
   CARCA_CHECK_ARG(!D.table_i8 || (!D.user_a && D.ld_table_i8 >= D.F && D.ld_table_i8 % 64 == 0),
                   "%s: table_i8 needs table mode and ld_table_i8 >= F, a multiple of 64", what);
-  CARCA_CHECK_ARG(D.n_exclude >= 0 && (D.n_exclude == 0 || (D.exclude && D.ld_exclude >= D.n_exclude)),
-                  "%s: bad exclusion list", what);
-  return CARCA_OK;
+  return rc::check_exclusion(D, what);
 }
 
 // scratch: [B, n_items] logits, then the [Bp, ldq] query rows, then `extra` bytes; launches the query and scoring kernels
@@ -358,7 +334,7 @@ extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_)
   const CarcaKnnRankDesc& D = *desc;
   int rc = kc_check(D, "knn_rank_items");
   if (rc != CARCA_OK) return rc;
-  CARCA_CHECK_SUPPORTED(D.n_list >= 1 && D.n_list <= KC_NMAX, "knn_rank_items: n_list = %d outside 1..128", D.n_list);
+  CARCA_CHECK_SUPPORTED(D.n_list >= 1 && D.n_list <= rc::LIST_MAX, "knn_rank_items: n_list = %d outside 1..128", D.n_list);
   CARCA_CHECK_ARG(D.items && D.scores && D.ranks && D.ld_items >= D.n_list && D.ld_scores >= D.n_list &&
                       D.ld_ranks >= D.n_list,
                   "knn_rank_items: null list / output or row stride shorter than n_list");
@@ -369,7 +345,7 @@ extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_)
   if (rc != CARCA_OK) return rc;
   unsigned long long* tkeys = (unsigned long long*)kp;
   // the targets' keys before the exclusion overwrites any of them: an excluded target keeps its position
-  hipLaunchKernelGGL(kc_list_kernel, dim3(D.B), dim3(KC_NMAX), 0, stream, D, logits, ld_s, tkeys);
+  hipLaunchKernelGGL(kc_list_kernel, dim3(D.B), dim3(rc::LIST_MAX), 0, stream, D, logits, ld_s, tkeys);
   CARCA_LAUNCH_CHECK();
   KcSelect S = {};
   S.n_items = D.n_items, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;

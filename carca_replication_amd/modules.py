@@ -20,16 +20,16 @@ DotProduct / WeightedDotProduct  carca.py:352-399  ops.dot_score_fwd (+ layernor
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from abc import ABC, abstractmethod
+from functools import partial
 from typing import Iterable, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from . import _lib, ops
+from . import _lib, catalogue, ops
 from ._lib import CarcaHipError
 
 # ------------------------------------------------------------------------------------------------
@@ -1243,106 +1243,6 @@ class CARCA(_PackedModule, Model):
         return sampled_softmax_loss(self, profile, pos, samples, log_q)
 
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items) -
-    def _catalogue_user_side(self, what: str, profile, context: Optional[Tensor], D) -> list:
-        """Checks the envelope of recommend / rank_items and fills the model-side fields of D (RecommendDesc or RankDesc:
-        same names) -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path
-        of forward (embed_segments + the fused blocks + the final LayerNorm), then K, V -> u, M c, dq and w . M c.
-        Returns the tensors D points into (kept alive by the caller until the launch is queued).  Call under no_grad."""
-        p_x, p_a, p_c = profile
-        ops._need_cuda(p_x, p_a, p_c, context)
-        B, L = p_x.shape
-        if L > _lib.MAX_L:
-            raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}")
-        emb, dec = self.embeds, self.decoder
-        d = emb.d
-        bad = [H for H in self._attn_heads() if d > ops.FUSED_MAX_D or not ops.attn_geometry_built(d, H)]
-        if bad:
-            raise CarcaHipError(f"{what}: (d, H) = ({d}, {bad[0]}) has no fused attention kernel built "
-                                "(CARCA_ATT_GEOMETRIES in csrc/attn_common.h)")
-        ca = isinstance(dec, CrossAttentionBlock)
-        if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
-            raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
-        n_ctx = context.shape[-1] if context is not None else 0
-        if context is not None and tuple(context.shape) != (B, n_ctx):
-            raise CarcaHipError(f"{what}: context must be [B, n_ctx], got {tuple(context.shape)}")
-        T = emb.item_table()
-        n_items = T.shape[0]
-        M = emb.context_matrix(n_ctx)
-        H = dec.attn.H if ca else self._heads()
-        dpi, _, _ = ops.padded_dims(d, H)
-        ld = ops.row_ld(d)
-        # profile side: the encoder path of forward (embed_segments + the fused blocks + the final LayerNorm)
-        es, _ = emb.embed_segments([(p_x, p_a, p_c, False)], ld_e=dpi)
-        x = es[0]
-        for blk in self.encoder:
-            blk._check_mode()
-            x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
-        p_n = ops.layernorm_fwd(x.reshape(B * L, -1), self.norm.weight, self.norm.bias, d, dpi)
-        mc = None
-        if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
-            (mc,) = ops.gemm_rows([dict(a0=ops._f32(context))], M, d, n_ctx, ld)
-        p_ids = ops._ids32(p_x)
-        keep = [T, p_ids, p_n, mc]
-        D.B, D.L, D.n_items, D.d, D.H = B, L, n_items, d, H
-        D.p_ids, D.ld_p_ids = p_ids.data_ptr(), L
-        if ca:
-            qt, wt, wd = dec.recommend_tables(T)
-            a = dec.attn
-            (kk,) = ops.gemm_rows([dict(a0=p_n)], a.WK.weight.detach(), d, d, ld, bias=a.WK.bias.detach())
-            (vv,) = ops.gemm_rows([dict(a0=p_n)], a.WV.weight.detach(), d, d, ld, bias=a.WV.bias.detach())
-            (uu,) = ops.gemm_rows([dict(a0=vv)], wd, H, d, 4)  # u_lh = w_h . V_lh (the decoder FFN folded in)
-            keep += [qt, wt, kk, uu]
-            D.decoder = 0
-            D.item_q, D.ld_item_q = qt.data_ptr(), qt.stride(0)
-            D.user_k, D.ld_user_k, D.user_u, D.ld_user_u = kk.data_ptr(), kk.stride(0), uu.data_ptr(), uu.stride(0)
-            D.ffn_b = dec.ffn.bias.data_ptr()
-            if dec.residual:
-                D.item_w, D.ld_item_w = wt.data_ptr(), wt.stride(0)
-            if mc is not None:
-                (dq,) = ops.gemm_rows([dict(a0=mc)], a.WQ.weight.detach(), d, d, ld)  # (M c_u) W_Q^T
-                keep.append(dq)
-                D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
-                if dec.residual:
-                    (off,) = ops.gemm_rows([dict(a0=mc)], dec.ffn.weight.detach(), 1, d, 4)  # w_ffn . M c_u
-                    keep.append(off)
-                    D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
-        else:
-            rows = p_n
-            D.decoder = 1
-            if isinstance(dec, WeightedDotProduct):  # carca.py:385-389
-                rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi)
-                if dec.norm:
-                    rows = ops.l2norm_fwd(rows, d, dpi)
-                    D.decoder = 2
-            keep.append(rows)
-            last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
-            D.item_q, D.ld_item_q = T.data_ptr(), T.stride(0)
-            D.user_q, D.ld_user_q = last.data_ptr(), last.stride(0)
-            if mc is not None:
-                D.user_m, D.ld_user_m = mc.data_ptr(), mc.stride(0)
-        return keep
-
-    @staticmethod
-    def _catalogue_exclusion(what: str, exclude, p_ids: Tensor, B: int, D, keep: list, clamp: Optional[int] = None):
-        """exclude ("profile", None or an int [B, E] tensor) -> D.exclude / n_exclude / ld_exclude.  clamp: int64 ids are
-        first clamped to [-1, clamp] so that none wraps into range on the way to int32."""
-        if isinstance(exclude, str):
-            if exclude != "profile":
-                raise CarcaHipError(f'{what}: exclude must be "profile", None or an int [B, E] tensor')
-            excl = p_ids
-        elif exclude is None:
-            excl = None
-        else:
-            ops._need_cuda(exclude)
-            if exclude.dim() != 2 or exclude.shape[0] != B or exclude.is_floating_point():
-                raise CarcaHipError(f"{what}: exclude must be an int [B, E] tensor")
-            if clamp is not None and exclude.dtype != torch.int32:
-                exclude = exclude.clamp(-1, clamp)
-            excl = ops._ids32(exclude)
-        if excl is not None and excl.shape[1] > 0:
-            keep.append(excl)
-            D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
-
     def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
                   exclude="profile") -> Tuple[Tensor, Tensor]:
         """The k best items of the whole catalogue per user: (scores [B, k] float32, ids [B, k] int64), best first.
@@ -1358,19 +1258,8 @@ class CARCA(_PackedModule, Model):
             raise CarcaHipError("recommend: the model is in training mode; recommendation scores with eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
-        if not 1 <= int(k) <= 128:
-            raise CarcaHipError(f"recommend: k = {k} outside 1..128 (the largest k the selection keeps is 128)")
-        with torch.no_grad():
-            D = _lib.RecommendDesc()
-            keep = self._catalogue_user_side("recommend", profile, context, D)
-            B, p_ids, device = D.B, keep[1], profile[0].device
-            D.k = int(k)
-            self._catalogue_exclusion("recommend", exclude, p_ids, B, D, keep)
-            scores = torch.empty(B, int(k), dtype=torch.float32, device=device)
-            ids = torch.empty(B, int(k), dtype=torch.int64, device=device)
-            D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), int(k), ids.data_ptr(), int(k)
-            _lib.check(_lib.load().carca_recommend(C.byref(D), ops._stream()), "recommend")
-        return scores, ids
+        return catalogue.recommend("recommend", _lib.RecommendDesc, "carca_recommend",
+                                   partial(catalogue.carca_model_side, self, profile, context), profile, k, exclude)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile") -> Tuple[Tensor, Tensor]:
@@ -1386,25 +1275,8 @@ class CARCA(_PackedModule, Model):
             raise CarcaHipError("rank_items: the model is in training mode; ranks use eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
-        ops._need_cuda(items)
-        if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
-            raise CarcaHipError("rank_items: items must be an int [B, N] tensor")
-        N = items.shape[1]
-        if not 1 <= N <= 128:
-            raise CarcaHipError(f"rank_items: N = {N} items per user outside 1..128")
-        with torch.no_grad():
-            D = _lib.RankDesc()
-            keep = self._catalogue_user_side("rank_items", profile, context, D)
-            B, p_ids, device, n_items = D.B, keep[1], profile[0].device, D.n_items
-            self._catalogue_exclusion("rank_items", exclude, p_ids, B, D, keep, clamp=n_items)
-            lst = ops._ids32(items if items.dtype == torch.int32 else items.clamp(-1, n_items))
-            keep.append(lst)
-            scores = torch.empty(B, N, dtype=torch.float32, device=device)
-            ranks = torch.empty(B, N, dtype=torch.int64, device=device)
-            D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
-            D.scores, D.ld_scores, D.ranks, D.ld_ranks = scores.data_ptr(), N, ranks.data_ptr(), N
-            _lib.check(_lib.load().carca_rank_items(C.byref(D), ops._stream()), "rank_items")
-        return scores, ranks
+        return catalogue.rank_items("rank_items", _lib.RankDesc, "carca_rank_items",
+                                    partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude)
 
     # ---- inference: one host call per forward (include/carca_hip.h: carca_forward) -----------------------------
     def _fused_ok(self, trace) -> bool:
@@ -1651,15 +1523,6 @@ class KNN(Model):
             self.__dict__["_i8_cache"] = c
         return c[2]
 
-    def _catalogue(self, what: str, profile, D, exclude, keep: list, clamp: Optional[int] = None) -> None:
-        if self._attr_table is None:
-            raise CarcaHipError(f"KNN.{what}: no attribute table registered -- call register_attr_table(attrs) with the "
-                                "[n_items, n_attrs] item-attribute matrix first (the catalogue is its rows)")
-        p_x, p_a, _ = profile
-        table = self._attr_table
-        p_ids = ops.knn_catalogue(D, table, None if p_a is not None else self.int8_table(), p_x, p_a, keep)
-        CARCA._catalogue_exclusion(what, exclude, p_ids, D.B, D, keep, clamp=clamp)
-
     def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None, k: int = 10,
                   exclude="profile") -> Tuple[Tensor, Tensor]:
         """The k best items of the catalogue (the rows of the registered attribute table) per user: (scores [B, k]
@@ -1668,18 +1531,8 @@ class KNN(Model):
         context is ignored (knn.py ignores it).  Order, exclusion ("profile", None or an int [B, E] tensor, 0 = no
         entry) and padding are CARCA.recommend's: ties go to the smaller id, id 0 is never listed, fewer than k
         eligible items pad with id 0 and score 0.  1 <= k <= 128; any L; train and eval mode alike."""
-        if not 1 <= int(k) <= 128:
-            raise CarcaHipError(f"recommend: k = {k} outside 1..128 (the largest k the selection keeps is 128)")
-        with torch.no_grad():
-            D, keep = _lib.KnnRecommendDesc(), []
-            self._catalogue("recommend", profile, D, exclude, keep)
-            B, device = D.B, profile[0].device
-            scores = torch.empty(B, int(k), dtype=torch.float32, device=device)
-            ids = torch.empty(B, int(k), dtype=torch.int64, device=device)
-            D.k = int(k)
-            D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), int(k), ids.data_ptr(), int(k)
-            _lib.check(_lib.load().carca_knn_recommend(C.byref(D), ops._stream()), "KNN.recommend")
-        return scores, ids
+        return catalogue.recommend("KNN.recommend", _lib.KnnRecommendDesc, "carca_knn_recommend",
+                                   partial(catalogue.knn_model_side, self, profile), profile, k, exclude)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile") -> Tuple[Tensor, Tensor]:
@@ -1688,25 +1541,8 @@ class KNN(Model):
         not excluded) before items[u, j] in recommend's order; an excluded or repeated item keeps its position.  Id 0
         or an id outside [0, n_items) gives rank -1 and score 0.  Scores and the order are bit-identical to
         recommend's; profile, context and exclude are recommend's."""
-        ops._need_cuda(items)
-        if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
-            raise CarcaHipError("rank_items: items must be an int [B, N] tensor")
-        N = items.shape[1]
-        if not 1 <= N <= 128:
-            raise CarcaHipError(f"rank_items: N = {N} items per user outside 1..128")
-        with torch.no_grad():
-            D, keep = _lib.KnnRankDesc(), []
-            n_items = 0 if self._attr_table is None else self._attr_table.shape[0]
-            self._catalogue("rank_items", profile, D, exclude, keep, clamp=n_items)
-            B, device = D.B, profile[0].device
-            lst = ops._ids32(items if items.dtype == torch.int32 else items.clamp(-1, n_items))
-            keep.append(lst)
-            scores = torch.empty(B, N, dtype=torch.float32, device=device)
-            ranks = torch.empty(B, N, dtype=torch.int64, device=device)
-            D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
-            D.scores, D.ld_scores, D.ranks, D.ld_ranks = scores.data_ptr(), N, ranks.data_ptr(), N
-            _lib.check(_lib.load().carca_knn_rank_items(C.byref(D), ops._stream()), "KNN.rank_items")
-        return scores, ranks
+        return catalogue.rank_items("KNN.rank_items", _lib.KnnRankDesc, "carca_knn_rank_items",
+                                    partial(catalogue.knn_model_side, self, profile), profile, items, exclude)
 
     def forward(self, profile: Tuple[Tensor, Tensor, Tensor], targets: List[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
         p_x, p_a, p_c = profile

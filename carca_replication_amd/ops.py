@@ -1073,31 +1073,6 @@ def knn_int8_table(table: Tensor) -> Optional[Tensor]:
     return t8
 
 
-def knn_catalogue(D, table: Tensor, table_i8: Optional[Tensor], p_x: Tensor, p_a: Optional[Tensor], keep: list) -> Tensor:
-    """Fills the model-side fields of a KnnRecommendDesc / KnnRankDesc: the catalogue `table` [n_items, F] (fp32,
-    contiguous rows), its int8 copy or None, and the query -- p_a[:, L-1] when p_a is given (dense), else the table row of
-    p_x[:, L-1].  Returns p_x as int32 (the "profile" exclusion list); what D points into is appended to `keep`."""
-    _need_cuda(table, p_x, p_a)
-    B, L = p_x.shape
-    n_items, F = table.shape
-    p_ids = _ids32(p_x)
-    keep += [table, p_ids]
-    D.B, D.L, D.n_items, D.F = B, L, n_items, F
-    D.p_ids, D.ld_p_ids = p_ids.data_ptr(), p_ids.stride(0)
-    D.table, D.ld_table = table.data_ptr(), table.stride(0)
-    if p_a is not None:
-        if p_a.dim() != 3 or p_a.shape[0] != B or p_a.shape[2] != F:
-            raise CarcaHipError(f"knn: p_a {tuple(p_a.shape)} does not match [B, L, F] = [{B}, {L}, {F}]")
-        q = p_a[:, -1]
-        if q.dtype != torch.float32 or q.stride(-1) != 1:
-            q = q.to(torch.float32).contiguous()
-        keep.append(q)
-        D.user_a, D.ld_user_a = q.data_ptr(), q.stride(0)
-    elif table_i8 is not None:
-        keep.append(table_i8)
-        D.table_i8, D.ld_table_i8 = table_i8.data_ptr(), table_i8.stride(0)
-    return p_ids
-
 def slot_decay_scale(x: Tensor, B: int, L: int, d: int, gamma: float, out_ld: int) -> Tensor:
     """out[b][t] = x[b][t] * sum_{j<=t} gamma^j (WeightedDotProduct's history weights; its own backward); [B*L, out_ld]."""
     lib = _lib.load()
