@@ -341,6 +341,7 @@ SIGNATURES = {
     "carca_mha_core_bwd": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp,
                                 _fp]),
     "carca_gemm_rows_log": (_i, [C.c_char_p, _i]),
+    "carca_feat_dedup_rows_multiplied": (C.c_longlong, []),
     "carca_mha_core_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, C.POINTER(Dropout),
                                  _fp, _fp]),
     "carca_mha_core_bwd_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp,

@@ -261,17 +261,19 @@ int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* 
 // The evaluation feature product over distinct attribute rows (feat_dedup.hip, gemm.hip: carca_gemm_rows_feat_dedup).
 // One launch's state: the product's descriptor, the rows of all segments laid end to end (segment s from row0[s]), the
 // id table (key / val: 2^hbits slots, zero between launches), per row its slot (the table slot it owns, else -1), its
-// representative row (-1: id 0) and its flag (1: a representative -- what gemm_rows_skc_kernel plans from), and P
-// [R, ldp] (written at the representatives' rows).
+// representative row (-1: id 0) and its flag (1: a representative -- what gemm_rows_skc_kernel plans from), P
+// [R, ldp] (written at the representatives' rows), and wcb [K1 + 1][N]: W_c^T over b_f, written by the insert launch for
+// the expand launch (vec2: that one may use 8-byte accesses).
 struct CarcaDedupRun {
   CarcaGemmDesc d;
-  int nseg, R, vec, hbits;
+  int nseg, R, vec, vec2, hbits;
   int row0[CARCA_MAX_SEGS + 1];
   unsigned hmask;
   int* key;
   unsigned* val;
   int *slot, *rep, *flag;
   float* P;
+  float* wcb;
   int ldp;
 };
 // 1 = not this product's path (nothing launched), CARCA_OK with *run filled, or an error

@@ -6,6 +6,8 @@
 // so the 4096-deep product runs over one representative row per group and the six context columns per row.  Four launches:
 //   1. dedup_insert_kernel   every kept row into an open-addressing table keyed by id (2x the rows, CAS on the key):
 //                            the group's representative is its LOWEST row (atomicMax of ~row), whatever the timing;
+//                            its grid also writes [W_c^T ; b_f] as one compact [K1 + 1][N] block for launch 4 (per
+//                            launch: the weights change between evaluations);
 //   2. dedup_resolve_kernel  a row whose representative is another row compares the two attribute rows as 32-bit
 //                            integers (dense batches; rows gathered from one table by the same id are the same row) and
 //                            stays its own representative on any difference (-0.0 / +0.0, NaN payloads: never merged);
@@ -14,18 +16,27 @@
 //   4. dedup_expand_kernel   q_r = P[u(r)] + c_r W_c^T + b_f for every kept row (multiply-adds in k order, then the bias),
 //                            zeros for id 0; it also hands the table back clean (the owner row of each slot clears it),
 //                            so nothing is cleared per batch: the table is zeroed once, when its buffer is allocated.
+//                            Memory-bound (R g floats written, the distinct P rows read): a workgroup takes the compact
+//                            weight block and its rows' rep / slot / context values in ONE round trip, then every wave
+//                            has all the P loads of its four rows in flight together, 8 bytes per lane where the rows
+//                            are 8-byte aligned (g = 450: rows are never 16-byte aligned).
 // Results are the same bits run to run and in a graph replay (nothing depends on timing), and the same between a dense
 // batch and the attribute table (the same groups: equal ids carry equal bytes).
 #include <hip/hip_ext.h>
+
+#include <vector>
 
 #include "carca_common.h"
 #include "../../include/carca_hip.h"
 
 namespace {
 
-constexpr int EXP_ROWS = 32;      // rows per expand workgroup (8 per wave)
+constexpr int EXP_ROWS = 16;      // rows per expand workgroup (4 per wave, all in flight together)
 constexpr int EXP_MAX_N = 1024;   // output columns the expand kernel keeps W_c / b_f of in LDS
 constexpr int EXP_MAX_K1 = 8;
+constexpr int EXP_WB4 = ((EXP_MAX_K1 + 1) * EXP_MAX_N / 4 + 255) / 256;  // 16-byte pieces of the weight block per thread
+// floats of the compact weight block [K1 + 1][N] (rows 0 .. K1-1: W_c^T, row K1: b_f), padded to whole 16-byte pieces
+__host__ __device__ inline int exp_wb_floats(int K1, int N) { return ((K1 + 1) * N + 3) / 4 * 4; }
 
 __device__ __forceinline__ int dd_seg(const CarcaDedupRun& a, int g) {
   int s = 0;
@@ -40,14 +51,16 @@ __device__ __forceinline__ const float* dd_a0_row(const CarcaDedupRun& a, int s,
   if (sg.a0_bstride) return sg.a0 + (size_t)(r / sg.T) * sg.a0_bstride + (size_t)(r % sg.T) * a.d.lda0;
   return sg.a0 + (size_t)r * a.d.lda0;
 }
-__device__ __forceinline__ const float* dd_a1_row(const CarcaDedupRun& a, int s, int r) {
-  const CarcaGemmSeg& sg = a.d.seg[s];
-  if (sg.a1_bstride) return sg.a1 + (size_t)(r / sg.T) * sg.a1_bstride + (size_t)(r % sg.T) * a.d.lda1;
-  return sg.a1 + (size_t)r * a.d.lda1;
-}
 
 __global__ __launch_bounds__(256) void dedup_insert_kernel(const CarcaDedupRun a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
+  {  // the expand launch's weight block: one strided element per thread here instead of all of them per workgroup there
+    const int N = a.d.N, K1 = a.d.K1, nw = exp_wb_floats(K1, N);
+    for (int i = g; i < nw; i += gridDim.x * 256) {
+      const int k = i / N, n = i - k * N;
+      a.wcb[i] = k < K1 ? a.d.bt1[(size_t)n * a.d.ldb1 + k] : (k == K1 && a.d.bias ? a.d.bias[n] : 0.f);
+    }
+  }
   if (g >= a.R) return;
   const int s = dd_seg(a, g);
   const int id = a.d.seg[s].ids[g - a.row0[s]];
@@ -127,50 +140,129 @@ __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun 
   }
 }
 
+// what the expand kernel needs of a row's segment, picked with constant indices (a per-lane index into the kernel
+// arguments would be a memory round trip of its own)
+struct DdRowSeg {
+  const float* a1;
+  float* c;
+  long a1_bstride;
+  int T, r;
+};
+__device__ __forceinline__ DdRowSeg dd_row_seg(const CarcaDedupRun& a, int g) {
+  DdRowSeg o{a.d.seg[0].a1, a.d.seg[0].c, a.d.seg[0].a1_bstride, a.d.seg[0].T, g};
+#pragma unroll
+  for (int i = 1; i < CARCA_MAX_SEGS; ++i)
+    if (i < a.nseg && g >= a.row0[i]) o = DdRowSeg{a.d.seg[i].a1, a.d.seg[i].c, a.d.seg[i].a1_bstride, a.d.seg[i].T, g - a.row0[i]};
+  return o;
+}
+
+// VW: floats per access (2: N, ldc, ldp even and every output segment 8-byte aligned)
+template <int VW>
 __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a) {
-  __shared__ float Ws[EXP_MAX_K1 * EXP_MAX_N];  // W_c transposed: [k][n]
-  __shared__ float Bb[EXP_MAX_N];
-  const CarcaGemmDesc& D = a.d;
-  const int N = D.N, K1 = D.K1;
-  for (int i = threadIdx.x; i < K1 * N; i += 256) {
-    const int k = i / N, n = i - k * N;
-    Ws[i] = D.bt1[(size_t)n * D.ldb1 + k];
+  typedef float vec __attribute__((ext_vector_type(VW)));
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  extern __shared__ f4 exp_lds[];  // the weight block [K1 + 1][N] | context values [EXP_ROWS][8] | representatives [EXP_ROWS]
+  carca_warm_kernargs<sizeof(CarcaDedupRun)>();
+  const int N = a.d.N, K1 = a.d.K1, nw4 = exp_wb_floats(K1, N) / 4;
+  float* Ws = reinterpret_cast<float*>(exp_lds);
+  float* cxs = Ws + nw4 * 4;
+  int* reps = reinterpret_cast<int*>(cxs + EXP_ROWS * EXP_MAX_K1);
+  const int tid = threadIdx.x, g0 = blockIdx.x * EXP_ROWS;
+  // one round trip: the weight block, the rows' context values (thread = row, k), rep and slot (thread = row)
+  f4 w[EXP_WB4];
+  const f4* wcb4 = reinterpret_cast<const f4*>(a.wcb);
+#pragma unroll
+  for (int j = 0; j < EXP_WB4; ++j) {
+    const int i = tid + j * 256;
+    if (i < nw4) w[j] = wcb4[i];
   }
-  for (int n = threadIdx.x; n < N; n += 256) Bb[n] = D.bias ? D.bias[n] : 0.f;
+  if (tid < EXP_ROWS * EXP_MAX_K1) {
+    const int row = tid / EXP_MAX_K1, k = tid % EXP_MAX_K1, g = g0 + row;
+    float cv = 0.f;
+    if (g < a.R && k < K1) {
+      const DdRowSeg sg = dd_row_seg(a, g);
+      const float* cr = sg.a1_bstride ? sg.a1 + (size_t)(sg.r / sg.T) * sg.a1_bstride + (size_t)(sg.r % sg.T) * a.d.lda1
+                                      : sg.a1 + (size_t)sg.r * a.d.lda1;
+      cv = cr[k];
+    }
+    cxs[tid] = cv;
+  } else if (tid < EXP_ROWS * EXP_MAX_K1 + EXP_ROWS) {
+    const int row = tid - EXP_ROWS * EXP_MAX_K1, g = g0 + row;
+    int u = -2;  // (-2: past the last row, -1: id 0 -- the resolve kernel wrote rep = -1 there and P has no such row)
+    if (g < a.R) {
+      u = a.rep[g];
+      const int h = a.slot[g];
+      if (h >= 0) {  // (nobody reads the table after the resolve kernel)
+        a.key[h] = 0;
+        a.val[h] = 0u;
+      }
+    }
+    reps[row] = u;
+  }
+#pragma unroll
+  for (int j = 0; j < EXP_WB4; ++j) {
+    const int i = tid + j * 256;
+    if (i < nw4) exp_lds[i] = w[j];
+  }
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int RW = EXP_ROWS / 4, CH = 4;  // rows per wave; 64-lane column chunks in flight per row
+  const int nv = N / VW;                    // (VW = 2: N is even)
+  int u[RW];
+  vec* crow[RW];
+#pragma unroll
+  for (int i = 0; i < RW; ++i) {
+    const int row = wave * RW + i;
+    u[i] = __builtin_amdgcn_readfirstlane(reps[row]);
+    const DdRowSeg sg = dd_row_seg(a, min(g0 + row, a.R - 1));
+    crow[i] = reinterpret_cast<vec*>(sg.c + (size_t)sg.r * a.d.ldc);
+  }
+  const vec* Wv = reinterpret_cast<const vec*>(Ws);
+  for (int c0 = 0; c0 < nv; c0 += CH * 64) {
+    vec v[RW][CH];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+      const vec* prow = reinterpret_cast<const vec*>(a.P + (size_t)max(u[i], 0) * a.ldp);
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const int p = c0 + c * 64 + lane;
+        v[i][c] = u[i] >= 0 && p < nv ? prow[p] : vec(0.f);
+      }
+    }
+    // (k outermost: one read of W_c's row k and of the rows' context values serves all RW x CH accesses; per element
+    // the multiply-adds still run in k order from P's value, then the bias)
 #pragma unroll 1
-  for (int i = 0; i < EXP_ROWS / 4; ++i) {
-    const int g = blockIdx.x * EXP_ROWS + i * 4 + wave;
-    if (g >= a.R) break;
-    const int s = dd_seg(a, g), r = g - a.row0[s];
-    const CarcaGemmSeg& sg = D.seg[s];
-    float* crow = sg.c + (size_t)r * D.ldc;
-    if (sg.ids[r] == 0) {
-      for (int n = lane; n < D.ncols_out; n += 64) crow[n] = 0.f;
-      continue;
-    }
-    const int u = a.rep[g], h = a.slot[g];
-    if (h >= 0 && lane == 0) {  // (nobody reads the table after the resolve kernel)
-      a.key[h] = 0;
-      a.val[h] = 0u;
-    }
-    float cx[EXP_MAX_K1];
-    if (K1 > 0) {
-      const float* cr = dd_a1_row(a, s, r);
+    for (int k = 0; k < K1; ++k) {
+      vec wk[CH];
 #pragma unroll
-      for (int k = 0; k < EXP_MAX_K1; ++k) cx[k] = k < K1 ? cr[k] : 0.f;
-    }
-    const float* prow = a.P + (size_t)u * a.ldp;
-    for (int n = lane; n < N; n += 64) {
-      float v = prow[n];
+      for (int c = 0; c < CH; ++c) wk[c] = Wv[k * nv + min(c0 + c * 64 + lane, nv - 1)];
 #pragma unroll
-      for (int k = 0; k < EXP_MAX_K1; ++k)
-        if (k < K1) v = fmaf(cx[k], Ws[k * N + n], v);
-      crow[n] = v + Bb[n];
+      for (int i = 0; i < RW; ++i) {
+        const float cx = cxs[(wave * RW + i) * EXP_MAX_K1 + k];
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+#pragma unroll
+          for (int e = 0; e < VW; ++e) v[i][c][e] = fmaf(cx, wk[c][e], v[i][c][e]);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int p = c0 + c * 64 + lane;
+      const vec b = Wv[K1 * nv + min(p, nv - 1)];
+#pragma unroll
+      for (int i = 0; i < RW; ++i)
+        if (u[i] >= -1 && p < nv) crow[i][p] = u[i] >= 0 ? v[i][c] + b : vec(0.f);
     }
   }
 }
+
+// the last eager launch of this thread, for carca_feat_dedup_rows_multiplied: where its flags lie in the stream's scratch
+struct DdLast {
+  hipStream_t stream;
+  size_t bytes, flag_off;
+  int R;
+};
+thread_local DdLast g_dd_last{nullptr, 0, 0, 0};
 
 }  // namespace
 
@@ -202,10 +294,15 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
   a.hbits = hb;
   a.hmask = (1u << hb) - 1;
   a.ldp = D.N;
-  // the table (zeroed when allocated, kept clean by the expand kernel) and the per-launch arrays + P
+  // 8-byte accesses in the expand launch: every q row and P row 8-byte aligned (g = 450: never 16)
+  bool vec2 = D.N % 2 == 0 && D.ldc % 2 == 0;
+  for (int s = 0; s < D.nseg; ++s) vec2 = vec2 && ((uintptr_t)D.seg[s].c & 7) == 0;
+  a.vec2 = vec2 ? 1 : 0;
+  // the table (zeroed when allocated, kept clean by the expand kernel) and the per-launch arrays + weight block + P
   const size_t hbytes = (size_t)2 * sizeof(int) << hb;
   const size_t ibytes = ((size_t)3 * R * sizeof(int) + 255) / 256 * 256;
-  const size_t bytes = ibytes + (size_t)R * a.ldp * sizeof(float);
+  const size_t wbytes = ((size_t)exp_wb_floats(D.K1, D.N) * sizeof(float) + 255) / 256 * 256;
+  const size_t bytes = ibytes + wbytes + (size_t)R * a.ldp * sizeof(float);
   const bool cap = carca_stream_capturing(stream);
   char* ht = (char*)(cap ? carca_capture_alloc(stream, hbytes, false, nullptr, hbytes)
                          : carca_stream_scratch(stream, CARCA_SCRATCH_DEDUP_HASH, hbytes, hbytes));
@@ -217,7 +314,9 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
   a.slot = (int*)buf;
   a.rep = a.slot + R;
   a.flag = a.rep + R;
-  a.P = (float*)(buf + ibytes);
+  a.wcb = (float*)(buf + ibytes);
+  a.P = (float*)(buf + ibytes + wbytes);
+  g_dd_last = cap ? DdLast{nullptr, 0, 0, 0} : DdLast{stream, bytes, (size_t)2 * R * sizeof(int), a.R};
   return CARCA_OK;
 }
 
@@ -242,10 +341,30 @@ int carca_feat_dedup_plan(const CarcaDedupRun* run, hipStream_t stream, hipEvent
 int carca_feat_dedup_expand(const CarcaDedupRun* run, hipStream_t stream, hipEvent_t stop) {
   const CarcaDedupRun& a = *run;
   const dim3 ge((a.R + EXP_ROWS - 1) / EXP_ROWS);
+  const size_t lds = ((size_t)exp_wb_floats(a.d.K1, a.d.N) + EXP_ROWS * EXP_MAX_K1 + EXP_ROWS) * sizeof(float);
+  auto kern = a.vec2 ? dedup_expand_kernel<2> : dedup_expand_kernel<1>;
   if (stop)
-    hipExtLaunchKernelGGL(dedup_expand_kernel, ge, dim3(256), 0, stream, nullptr, stop, 0, a);
+    hipExtLaunchKernelGGL(kern, ge, dim3(256), lds, stream, nullptr, stop, 0, a);
   else
-    hipLaunchKernelGGL(dedup_expand_kernel, ge, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(kern, ge, dim3(256), lds, stream, a);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
+}
+
+// Rows the product of this thread's last eager dedup launch multiplied (its flagged rows), read back after the launch's
+// stream has drained; -1: no such launch (none yet, or the last one was captured).  For tests: a table that is not handed
+// back clean shows here (rows that no longer merge), never in q.
+extern "C" long long carca_feat_dedup_rows_multiplied(void) {
+  const DdLast l = g_dd_last;
+  if (!l.R) return -1;
+  // (the same request as the launch's: the stream's buffer as it stands, not a pointer kept past a release)
+  const char* buf = (const char*)carca_stream_scratch(l.stream, CARCA_SCRATCH_DEDUP, l.bytes);
+  if (!buf) return -1;
+  std::vector<int> flag(l.R);
+  if (hipMemcpyAsync(flag.data(), buf + l.flag_off, (size_t)l.R * sizeof(int), hipMemcpyDeviceToHost, l.stream) != hipSuccess ||
+      hipStreamSynchronize(l.stream) != hipSuccess)
+    return -1;
+  long long n = 0;
+  for (int f : flag) n += f != 0;
+  return n;
 }

@@ -1282,6 +1282,12 @@ def gemm_rows_log(on: Optional[bool] = None) -> str:
     return buf.value.decode()
 
 
+def feat_dedup_rows_multiplied() -> int:
+    """Rows the feature product of the calling thread's last eager "+dedup" launch multiplied (waits for its stream);
+    -1 when there was none or the last one was captured."""
+    return int(_lib.load().carca_feat_dedup_rows_multiplied())
+
+
 def set_feature_gemm_precision(mode: str, force: bool = False) -> None:
     """'fp32' (default): exact-fp32 MFMA.  'bf16x3': both operands split into three bf16 parts, six products, fp32
     accumulation.  'fp16x2': two fp16 parts, three products (|operands| < 65504).  Applies to AllEmbedding.feats_embed

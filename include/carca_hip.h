@@ -478,6 +478,10 @@ int carca_mha_core(const float* q, int ldq, const float* k, const float* v, int 
  * carca_gemm_rows_log(buf, cap) copies the log (NUL-terminated) and returns its length.  tools/bench_configs.py names each
  * configuration's dominant kernel with it. */
 int carca_gemm_rows_log(char* out /*or NULL*/, int cap);
+/* Rows the feature product of the calling thread's last eager "+dedup" launch multiplied (one per group of equal attribute
+ * rows), read back once the launch's stream has drained; -1 when there was none or the last one was captured.  A hash
+ * table that a launch did not hand back clean shows here -- rows stop merging -- and never in the results. */
+long long carca_feat_dedup_rows_multiplied(void);
 /* carca_mha_core with nn.Dropout on the weights (carca.py:258): W * keep / (1 - p) multiplies v, w_out stays pre-dropout
  * (carca.py:262-263); element (b, h, t, j) of site drop->site, keep-mask written to keep_out [B, H, Tq, Tk] (uint8,
  * or NULL).  drop NULL or p = 0: carca_mha_core.  The attention of profiles longer than the fused kernels' 64 slots
