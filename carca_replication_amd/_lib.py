@@ -252,6 +252,11 @@ class RankDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "d", "H")] + _CARCA_MODEL + _RANK_OUT
 
 
+class Candidates(C.Structure):
+    """CarcaCandidates (carca_recommend_among / carca_rank_items_among)."""
+    _fields_ = [("ids", _fp), ("n", C.c_int32)]
+
+
 _KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_user_a", C.c_int64), ("table", _fp),
               ("ld_table", C.c_int32), ("table_i8", _fp), ("ld_table_i8", C.c_int32), ("exclude", _fp),
               ("n_exclude", C.c_int32), ("ld_exclude", C.c_int32)]
@@ -363,6 +368,8 @@ SIGNATURES = {
                                     _fp]),
     "carca_recommend": (_i, [C.POINTER(RecommendDesc), _fp]),
     "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
+    "carca_recommend_among": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), _fp]),
+    "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
     "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
     "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),

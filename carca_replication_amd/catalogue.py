@@ -2,7 +2,8 @@
 DESIGN.md sections 10-12).  A call fills the model side of a descriptor (carca_model_side or knn_model_side: what scores
 a (user, item) pair), then does what the four share -- the k / items checks, the exclusion list, the outputs and the
 launch (recommend, rank_items).  A model's two descriptors name their model-side and exclusion fields alike
-(include/carca_hip.h), so one function fills both."""
+(include/carca_hip.h), so one function fills both.  CandidateSet is the item set the CARCA calls can be restricted to
+(DESIGN.md section 15)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +16,72 @@ from . import _lib, ops
 from ._lib import CarcaHipError
 
 KMAX = 128  # largest k of recommend and largest list of rank_items (csrc: rc::RC_KMAX, rc::LIST_MAX)
+
+
+class CandidateSet:
+    """A set S of item ids that CARCA.recommend / rank_items and train.evaluate_full / evaluate_full_ranks can be restricted
+    to ("among these items"), shared by every user of a batch.
+
+    items: a 1-D integer tensor of ids, in any order -- duplicates, zeros and ids outside [1, n_items) are dropped -- or a
+    bool mask [n_items] (entry 0, the padding item, is ignored).  The constructor normalises once (sort, unique, range
+    filter), which is the set's only host sync; build it once and reuse it across calls.  `ids` is the result: int32 [C],
+    ascending and distinct, on `device` (default: where `items` lives); `n_items` the catalogue size it was built for.
+    C = 0 is a legal set."""
+
+    def __init__(self, items: Tensor, n_items: int, device=None):
+        n_items = int(n_items)
+        if n_items < 1:
+            raise CarcaHipError(f"CandidateSet: n_items = {n_items} must be positive")
+        if not isinstance(items, Tensor) or items.dim() != 1 or items.is_floating_point() or items.is_complex():
+            raise CarcaHipError("CandidateSet: items must be a 1-D integer tensor of ids or a bool mask [n_items]")
+        if items.dtype == torch.bool:
+            if items.shape[0] != n_items:
+                raise CarcaHipError(f"CandidateSet: a mask must have n_items = {n_items} entries, got {items.shape[0]}")
+            ids = torch.nonzero(items, as_tuple=False).reshape(-1)
+        else:
+            ids = torch.unique(items.to(torch.int64))  # (sorted ascending)
+        ids = ids[(ids >= 1) & (ids < n_items)]
+        self.n_items = n_items
+        self.ids = ids.to(dtype=torch.int32, device=items.device if device is None else device).contiguous()
+
+    def __len__(self) -> int:
+        return self.ids.shape[0]
+
+    def to(self, device) -> "CandidateSet":
+        """The set on `device`: itself when it is there already, else a copy of the normalised ids (no host sync)."""
+        ids = self.ids.to(device)
+        if ids is self.ids:
+            return self
+        out = object.__new__(CandidateSet)
+        out.n_items, out.ids = self.n_items, ids
+        return out
+
+    def contains(self, ids: Tensor) -> Tensor:
+        """Membership of each id of an integer tensor on the set's device, as a bool tensor of its shape (no host sync)."""
+        C_ = self.ids.shape[0]
+        if C_ == 0:
+            return torch.zeros_like(ids, dtype=torch.bool)
+        q = ids.to(torch.int64).clamp(-1, self.n_items).to(torch.int32).contiguous()
+        at = torch.searchsorted(self.ids, q).clamp(max=C_ - 1)
+        return self.ids[at] == q
+
+
+def _candidates(what: str, candidates, D, keep: list, device):
+    """candidates (None, a CandidateSet, or a raw tensor: a CandidateSet built for this call, one host sync) -> None or the
+    CarcaCandidates struct of the launch."""
+    if candidates is None:
+        return None
+    if not isinstance(candidates, CandidateSet):
+        if not isinstance(candidates, Tensor):
+            raise CarcaHipError(f"{what}: candidates must be None, a CandidateSet or a 1-D integer / bool tensor")
+        candidates = CandidateSet(candidates, D.n_items, device=device)
+    if candidates.n_items != D.n_items:
+        raise CarcaHipError(f"{what}: the candidate set was built for n_items = {candidates.n_items}, the model has "
+                            f"{D.n_items}")
+    ids = candidates.to(device).ids
+    ops._need_cuda(ids)
+    keep.append(ids)
+    return _lib.Candidates(ids.data_ptr() if ids.shape[0] else None, ids.shape[0])
 
 
 def carca_model_side(model, profile, context: Optional[Tensor], what: str, D) -> Tuple[list, Tensor]:
@@ -155,18 +222,25 @@ def _exclusion(what: str, exclude, p_ids: Tensor, D, keep: list, clamp: bool) ->
         D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
 
 
-def _launch(what: str, D, entry: str, second: str, n: int, device) -> Tuple[Tensor, Tensor]:
-    """Points D.scores and D.<second> at fresh [B, n] outputs (float32, int64) and queues the C entry point."""
+def _launch(what: str, D, entry: str, second: str, n: int, device, cand=None) -> Tuple[Tensor, Tensor]:
+    """Points D.scores and D.<second> at fresh [B, n] outputs (float32, int64) and queues the C entry point -- with a
+    candidate list `cand`, its _among form."""
     outs = (torch.empty(D.B, n, dtype=torch.float32, device=device), torch.empty(D.B, n, dtype=torch.int64, device=device))
     for name, t in zip(("scores", second), outs):
         setattr(D, name, t.data_ptr())
         setattr(D, "ld_" + name, n)
-    _lib.check(getattr(_lib.load(), entry)(C.byref(D), ops._stream()), what)
+    if cand is None:
+        rc = getattr(_lib.load(), entry)(C.byref(D), ops._stream())
+    else:
+        rc = getattr(_lib.load(), entry + "_among")(C.byref(D), C.byref(cand), ops._stream())
+    _lib.check(rc, what)
     return outs
 
 
-def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, exclude) -> Tuple[Tensor, Tensor]:
-    """The top-k call: desc the descriptor class, entry its C entry point, fill(what, D) -> (keep, p_ids) the model side."""
+def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, exclude,
+              candidates=None) -> Tuple[Tensor, Tensor]:
+    """The top-k call: desc the descriptor class, entry its C entry point, fill(what, D) -> (keep, p_ids) the model side;
+    candidates: None, or the set the call is restricted to (entry + "_among")."""
     if not 1 <= int(k) <= KMAX:
         raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
     with torch.no_grad():
@@ -174,10 +248,12 @@ def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, excl
         keep, p_ids = fill(what, D)
         D.k = int(k)
         _exclusion(what, exclude, p_ids, D, keep, clamp=False)
-        return _launch(what, D, entry, "ids_out", int(k), profile[0].device)
+        cand = _candidates(what, candidates, D, keep, profile[0].device)
+        return _launch(what, D, entry, "ids_out", int(k), profile[0].device, cand)
 
 
-def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tensor, exclude) -> Tuple[Tensor, Tensor]:
+def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tensor, exclude,
+               candidates=None) -> Tuple[Tensor, Tensor]:
     """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""
     ops._need_cuda(items)
     if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
@@ -192,4 +268,5 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
         lst = _ids32_clamped(items, D.n_items)
         keep.append(lst)
         D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
-        return _launch(what, D, entry, "ranks", N, profile[0].device)
+        cand = _candidates(what, candidates, D, keep, profile[0].device)
+        return _launch(what, D, entry, "ranks", N, profile[0].device, cand)

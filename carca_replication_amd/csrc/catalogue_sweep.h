@@ -2,24 +2,26 @@
 // recommend_common.h, and the counting step they share with carca_knn_rank_items (knn_catalogue.hip):
 //   sweep_kernel   a 256-item tile in registers walks a chunk of users, stages each user in LDS and scores the pair.  The
 //                  scorer (rc::CaScorer / rc::DotScorer) says how, the sink what becomes of the logit: recommend stores
-//                  it, rank_items compares its key with the user's target keys;
+//                  it, rank_items compares its key with the user's target keys; the item map (recommend_common.h:
+//                  rc::AllItems / rc::ListedItems) says which item a lane owns: the catalogue's, or a candidate list's;
 //   count_larger   per target, the keys of the workgroup that are larger, one integer atomic per target;
 //   host side      the model-side descriptor checks, the exclusion-list check, the sweep grid and the dispatch from a
 //                  descriptor's (decoder, d, H) to a scorer type.
 // A sink has: Desc, Lds (its own LDS block), begin_user (before the user's staging, whose barriers publish what it
-// writes) and put (every thread of the workgroup, live or not).
+// writes) and put (every thread of the workgroup, live or not; pos is the lane's position under the map, item its id).
 #pragma once
 #include "recommend_common.h"
 
 namespace rc {
 
 // ---- the sweep ---------------------------------------------------------------------------------------------------
-template <class Scorer, class Sink>
-__global__ __launch_bounds__(TILE) void sweep_kernel(typename Sink::Desc D, Sink sink, int users_per_block) {
+template <class Scorer, class Sink, class Map = AllItems>
+__global__ __launch_bounds__(TILE) void sweep_kernel(typename Sink::Desc D, Sink sink, int users_per_block, Map map) {
   __shared__ typename Scorer::User S;
   __shared__ typename Sink::Lds C;
   Scorer scorer(D);
-  const int item = blockIdx.x * TILE + threadIdx.x;
+  const int pos = blockIdx.x * TILE + threadIdx.x;
+  const int item = map.item(pos);
   const bool live = item >= 1 && item < D.n_items;
   typename Scorer::Item I;
   scorer.load_item(D, item, live, I);
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(TILE) void sweep_kernel(typename Sink::Desc D, Sink
     __syncthreads();  // the previous user's LDS is read out
     sink.begin_user(D, u, C);
     scorer.stage_user(D, u, S);
-    sink.put(D, u, item, live, scorer.logit(D, u, I, S), C);
+    sink.put(D, u, pos, item, live, scorer.logit(D, u, I, S), C);
   }
 }
 
@@ -109,16 +111,24 @@ int check_model(const Desc& D, const char* what) {
   return CARCA_OK;
 }
 
-// item tiles x user chunks, about two workgroups per CU; each workgroup keeps its tile's rows in registers
+// item tiles x user chunks, about two workgroups per CU; each workgroup keeps its tile's rows in registers.  n_slots is
+// the map's size (n_items, or the candidate count: at least 1, an empty list launches no sweep)
 struct SweepGrid {
   dim3 grid;
   int users_per_block;
 };
-inline SweepGrid sweep_grid(int n_items, int B) {
-  const int tiles = (n_items + TILE - 1) / TILE;
+inline SweepGrid sweep_grid(int n_slots, int B) {
+  const int tiles = (n_slots + TILE - 1) / TILE;
   const int chunks = max(1, min(B, (2 * carca_num_cus() + tiles - 1) / tiles));
   const int upb = (B + chunks - 1) / chunks;
   return {dim3(tiles, (B + upb - 1) / upb), upb};
+}
+
+// the candidate list of carca_recommend_among / carca_rank_items_among
+inline int check_candidates(const CarcaCandidates* cand, const char* what) {
+  CARCA_CHECK_ARG(cand, "%s: null candidate list", what);
+  CARCA_CHECK_ARG(cand->n >= 0 && (cand->n == 0 || cand->ids), "%s: bad candidate list", what);
+  return CARCA_OK;
 }
 
 // launch(ScorerOf<Scorer>{}) for the descriptor's scorer: one of CARCA_ATT_GEOMETRIES, or one of the three dot widths

@@ -320,10 +320,11 @@ extern "C" int carca_knn_recommend(const CarcaKnnRecommendDesc* desc, void* stre
   KcSelect S;
   S.n_items = D.n_items, S.k = D.k, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;
   S.scores = D.scores, S.ld_scores = D.ld_scores, S.ids_out = D.ids_out, S.ld_ids_out = D.ld_ids_out;
-  hipLaunchKernelGGL(rc::rc_exclude_kernel<KcSelect>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s);
+  hipLaunchKernelGGL(rc::rc_exclude_kernel<KcSelect>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s,
+                     rc::AllItems{});
   CARCA_LAUNCH_CHECK();
   hipLaunchKernelGGL(rc::rc_select_kernel<KcSelect>, dim3(D.B), dim3(rc::RC_SEL_THREADS), 0, stream, S, logits,
-                     (int)ld_s);
+                     (int)ld_s, rc::AllItems{});
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -349,7 +350,8 @@ extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_)
   CARCA_LAUNCH_CHECK();
   KcSelect S = {};
   S.n_items = D.n_items, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;
-  hipLaunchKernelGGL(rc::rc_exclude_kernel<KcSelect>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s);
+  hipLaunchKernelGGL(rc::rc_exclude_kernel<KcSelect>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s,
+                     rc::AllItems{});
   CARCA_LAUNCH_CHECK();
   const int per_block = KC_THREADS * KC_CNT_PER_THREAD;
   const dim3 grid((D.n_items + per_block - 1) / per_block, D.B);

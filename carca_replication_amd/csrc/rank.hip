@@ -16,6 +16,11 @@
 //   3. correction, one workgroup per user: the distinct excluded ids (not 0, inside [0, n_items)) whose key is larger than
 //      the target's are subtracted; an excluded target has its own key, which is not larger than itself.
 // Integer atomics only: the counts do not depend on scheduling.
+//
+// carca_rank_items_among counts among a candidate list S (ascending, distinct ids) through the item map rc::ListedItems:
+// launch 1 is unchanged (targets and excluded entries are scored by id, in S or not), the counting sweep runs over S
+// (a lane at position p owns item ids[p]; keys carry the real id), and the correction subtracts only excluded ids that S
+// holds (binary search): the others were never counted.
 #include "catalogue_sweep.h"
 
 namespace {
@@ -69,14 +74,15 @@ struct RkCountSink {
   __device__ __forceinline__ void begin_user(const Desc& D, int u, Lds& C) const {
     for (int t = threadIdx.x; t < D.n_list; t += RK_TILE) C.tkey[t] = W.keys[(size_t)u * W.ldk + t];
   }
-  __device__ __forceinline__ void put(const Desc& D, int u, int item, bool live, float logit, Lds& C) const {
+  __device__ __forceinline__ void put(const Desc& D, int u, int, int item, bool live, float logit, Lds& C) const {
     const unsigned long long key[1] = {live ? rc::item_key(logit, item) : 0ull};
     rc::count_larger(key, D.n_list, W.counts + (size_t)u * D.n_list, C);
   }
 };
 
 // ---- 3. correction -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RK_TILE) void rk_correct_kernel(CarcaRankDesc D, RkScratch W) {
+template <class Map>
+__global__ __launch_bounds__(RK_TILE) void rk_correct_kernel(CarcaRankDesc D, RkScratch W, Map map) {
   __shared__ unsigned long long ekey[RK_EX_CHUNK];
   const int u = blockIdx.x, tid = threadIdx.x;
   const unsigned long long* row = W.keys + (size_t)u * W.ldk;
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(RK_TILE) void rk_correct_kernel(CarcaRankDesc D, Rk
     __syncthreads();  // the previous chunk is read out
     for (int j = tid; j < n; j += RK_TILE) {  // keep an entry's key only at the first occurrence of its id
       const int e = base + j, id = ex[e];
-      bool first = rk_valid(id, D.n_items);
+      bool first = rk_valid(id, D.n_items) && map.find(id) >= 0;  // (an id the sweep did not count is not subtracted)
       for (int e2 = 0; first && e2 < e; ++e2) first = ex[e2] != id;
       ekey[j] = first ? row[D.n_list + e] : 0ull;
     }
@@ -103,12 +109,9 @@ __global__ __launch_bounds__(RK_TILE) void rk_correct_kernel(CarcaRankDesc D, Rk
   }
 }
 
-}  // namespace
-
-extern "C" int carca_rank_items(const CarcaRankDesc* desc, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  CARCA_CHECK_ARG(desc, "rank_items: null descriptor");
-  const CarcaRankDesc& D = *desc;
+// n_slots: the positions the counting sweep covers, n_items or the candidate count
+template <class Map>
+int rk_run(const CarcaRankDesc& D, Map map, int n_slots, hipStream_t stream) {
   if (int rc = rc::check_model(D, "rank_items")) return rc;
   CARCA_CHECK_SUPPORTED(D.n_list >= 1 && D.n_list <= rc::LIST_MAX, "rank_items: n_list = %d outside 1..128", D.n_list);
   CARCA_CHECK_ARG(D.items && D.scores && D.ranks, "rank_items: null pointer");
@@ -124,18 +127,32 @@ extern "C" int carca_rank_items(const CarcaRankDesc* desc, void* stream_) {
   CARCA_CHECK_ARG(base, "rank_items: scratch allocation of %zu bytes failed", bytes);
   W.counts = (int*)base;
   W.keys = (unsigned long long*)(base + count_bytes);
-  const rc::SweepGrid G = rc::sweep_grid(D.n_items, D.B);
+  const rc::SweepGrid G = rc::sweep_grid(std::max(n_slots, 1), D.B);
   const int rc = rc::dispatch_scorer(D, "rank_items", [&](auto scorer) -> int {
     using Scorer = typename decltype(scorer)::type;
     hipLaunchKernelGGL(rk_list_kernel<Scorer>, dim3(D.B), dim3(RK_TILE), 0, stream, D, W);
     CARCA_LAUNCH_CHECK();
-    hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RkCountSink>), G.grid, dim3(RK_TILE), 0, stream, D, RkCountSink{W},
-                       G.users_per_block);
+    if (n_slots == 0) return CARCA_OK;  // (an empty candidate list: no tile to sweep, every count stays 0)
+    hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RkCountSink, Map>), G.grid, dim3(RK_TILE), 0, stream, D, RkCountSink{W},
+                       G.users_per_block, map);
     CARCA_LAUNCH_CHECK();
     return CARCA_OK;
   });
   if (rc != CARCA_OK) return rc;
-  hipLaunchKernelGGL(rk_correct_kernel, dim3(D.B), dim3(RK_TILE), 0, stream, D, W);
+  hipLaunchKernelGGL(rk_correct_kernel<Map>, dim3(D.B), dim3(RK_TILE), 0, stream, D, W, map);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
+}
+
+}  // namespace
+
+extern "C" int carca_rank_items(const CarcaRankDesc* desc, void* stream) {
+  CARCA_CHECK_ARG(desc, "rank_items: null descriptor");
+  return rk_run(*desc, rc::AllItems{}, desc->n_items, (hipStream_t)stream);
+}
+
+extern "C" int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* cand, void* stream) {
+  CARCA_CHECK_ARG(desc, "rank_items: null descriptor");
+  if (int rc = rc::check_candidates(cand, "rank_items")) return rc;
+  return rk_run(*desc, rc::ListedItems{cand->ids, cand->n}, cand->n, (hipStream_t)stream);
 }

@@ -16,53 +16,77 @@
 //      (sigmoid, or (y + 1) / 2) applied to the k selected logits only.
 // Launches 2 and 3 live in catalogue_select.h, shared with carca_knn_recommend (knn_catalogue.hip).
 // Integer LDS atomics only (histograms, slot counters); the result does not depend on scheduling.
+//
+// carca_recommend_among runs the same three launches over a candidate list S (ascending, distinct ids) in place of the
+// catalogue, through the item map rc::ListedItems: the sweep's lane at position p owns item ids[p] (the same row gather,
+// so the same logit bits), the buffer is [B, |S|] indexed by position, exclusion finds an id's position by binary search,
+// and selection keys on the position (S ascending: ties still go to the smaller id) and writes ids[p].
 #include "catalogue_select.h"
 #include "catalogue_sweep.h"
 
 namespace {
 
-// the sweep's sink: the raw logit into the [B, n_items] buffer
+// the sweep's sink: the raw logit into the [B, n_items] buffer -- or, under a candidate list, into the [B, C] buffer at
+// the item's position, a listed id outside the catalogue as the exclusion sentinel
+template <class Map>
 struct RcStoreSink {
   using Desc = CarcaRecommendDesc;
   struct Lds {};
   float* logits;
   int ld_s;
   __device__ __forceinline__ void begin_user(const Desc&, int, Lds&) const {}
-  __device__ __forceinline__ void put(const Desc&, int u, int item, bool live, float logit, Lds&) const {
-    if (live) logits[(size_t)u * ld_s + item] = logit;
+  __device__ __forceinline__ void put(const Desc&, int u, int pos, int, bool live, float logit, Lds&) const {
+    if constexpr (Map::listed) {
+      if (pos < ld_s) logits[(size_t)u * ld_s + pos] = live ? logit : __uint_as_float(rc::RC_SENTINEL);
+    } else {
+      if (live) logits[(size_t)u * ld_s + pos] = logit;
+    }
   }
 };
 
-}  // namespace
-
-extern "C" int carca_recommend(const CarcaRecommendDesc* desc, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  CARCA_CHECK_ARG(desc, "recommend: null descriptor");
-  const CarcaRecommendDesc& D = *desc;
+// n_slots: the columns of the logit buffer, n_items or the candidate count
+template <class Map>
+int rc_run(const CarcaRecommendDesc& D, Map map, int n_slots, hipStream_t stream) {
   if (int rc = rc::check_model(D, "recommend")) return rc;
   CARCA_CHECK_ARG(D.k >= 1, "recommend: k must be positive");
   CARCA_CHECK_SUPPORTED(D.k <= rc::RC_KMAX, "recommend: k = %d exceeds the largest k, 128", D.k);
   CARCA_CHECK_ARG(D.scores && D.ids_out, "recommend: null pointer");
   CARCA_CHECK_ARG(D.ld_scores >= D.k && D.ld_ids_out >= D.k, "recommend: row stride shorter than its row");
-  // raw logits [B, n_items]: stream scratch (or the capture's memory), consumed by the two launches behind the scoring one
-  const int ld_s = D.n_items;
-  const size_t bytes = (size_t)D.B * (size_t)ld_s * sizeof(float);
+  // raw logits [B, n_slots]: stream scratch (or the capture's memory), consumed by the two launches behind the scoring one
+  const int ld_s = n_slots;
+  const size_t bytes = std::max((size_t)D.B * (size_t)ld_s, (size_t)1) * sizeof(float);
   float* logits = (float*)(carca_stream_capturing(stream) ? carca_capture_alloc(stream, bytes, false, nullptr)
                                                           : carca_stream_scratch(stream, CARCA_SCRATCH_RECOMMEND, bytes));
   CARCA_CHECK_ARG(logits, "recommend: scratch allocation of %zu bytes failed", bytes);
-  const rc::SweepGrid G = rc::sweep_grid(D.n_items, D.B);
-  const int rc = rc::dispatch_scorer(D, "recommend", [&](auto scorer) -> int {
-    using Scorer = typename decltype(scorer)::type;
-    hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RcStoreSink>), G.grid, dim3(rc::TILE), 0, stream, D,
-                       RcStoreSink{logits, ld_s}, G.users_per_block);
+  if (n_slots > 0) {  // (an empty candidate list: no tile to sweep, selection finds no eligible item)
+    const rc::SweepGrid G = rc::sweep_grid(n_slots, D.B);
+    const int rc = rc::dispatch_scorer(D, "recommend", [&](auto scorer) -> int {
+      using Scorer = typename decltype(scorer)::type;
+      hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
+                         RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
+      CARCA_LAUNCH_CHECK();
+      return CARCA_OK;
+    });
+    if (rc != CARCA_OK) return rc;
+    hipLaunchKernelGGL((rc::rc_exclude_kernel<CarcaRecommendDesc, Map>), dim3(D.B), dim3(64), 0, stream, D, logits, ld_s,
+                       map);
     CARCA_LAUNCH_CHECK();
-    return CARCA_OK;
-  });
-  if (rc != CARCA_OK) return rc;
-  hipLaunchKernelGGL(rc::rc_exclude_kernel<CarcaRecommendDesc>, dim3(D.B), dim3(64), 0, stream, D, logits, ld_s);
-  CARCA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rc::rc_select_kernel<CarcaRecommendDesc>, dim3(D.B), dim3(rc::RC_SEL_THREADS), 0, stream, D, logits,
-                     ld_s);
+  }
+  hipLaunchKernelGGL((rc::rc_select_kernel<CarcaRecommendDesc, Map>), dim3(D.B), dim3(rc::RC_SEL_THREADS), 0, stream, D,
+                     logits, ld_s, map);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
+}
+
+}  // namespace
+
+extern "C" int carca_recommend(const CarcaRecommendDesc* desc, void* stream) {
+  CARCA_CHECK_ARG(desc, "recommend: null descriptor");
+  return rc_run(*desc, rc::AllItems{}, desc->n_items, (hipStream_t)stream);
+}
+
+extern "C" int carca_recommend_among(const CarcaRecommendDesc* desc, const CarcaCandidates* cand, void* stream) {
+  CARCA_CHECK_ARG(desc, "recommend: null descriptor");
+  if (int rc = rc::check_candidates(cand, "recommend")) return rc;
+  return rc_run(*desc, rc::ListedItems{cand->ids, cand->n}, cand->n, (hipStream_t)stream);
 }

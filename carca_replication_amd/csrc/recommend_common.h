@@ -35,6 +35,37 @@ __device__ __forceinline__ float link(float y, int decoder) {
   return decoder == 2 ? (y + 1.f) * 0.5f : 1.f / (1.f + expf(-y));
 }
 
+// ---- the item maps ---------------------------------------------------------------------------------------------------
+// Which items a catalogue launch covers: positions 0 .. size - 1, each holding one item id.  AllItems is the catalogue
+// itself (position = id); ListedItems a candidate list (CarcaCandidates: ascending, distinct, so positions order as ids
+// do and a tie between two positions goes the way the tie between their ids goes).  An item's logit does not depend on
+// the position that holds it (load_item gathers its row by id).
+struct AllItems {
+  static constexpr bool listed = false;
+  __device__ __forceinline__ int size(int n_items) const { return n_items; }
+  __device__ __forceinline__ int item(int pos) const { return pos; }
+  __device__ __forceinline__ int find(int id) const { return id; }  // (the caller has checked 1 <= id < n_items)
+};
+struct ListedItems {
+  static constexpr bool listed = true;
+  const int32_t* ids;
+  int n;
+  __device__ __forceinline__ int size(int) const { return n; }
+  __device__ __forceinline__ int item(int pos) const { return pos < n ? ids[pos] : 0; }  // (0 is never live)
+  __device__ __forceinline__ int find(int id) const {  // the position of id, -1 when the list does not hold it
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ids[mid] < id) {
+        lo = mid + 1;
+      } else {
+        hi = mid;
+      }
+    }
+    return (lo < n && ids[lo] == id) ? lo : -1;
+  }
+};
+
 // ---- the two scorers -----------------------------------------------------------------------------------------------
 // A scorer is built per thread from the descriptor and has: User (one user's share, in LDS), Item (one item's share, in
 // registers), load_item (zeros where !live), stage_user (whole workgroup of TILE threads; the caller has synchronised

@@ -1244,7 +1244,7 @@ class CARCA(_PackedModule, Model):
 
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items) -
     def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
-                  exclude="profile") -> Tuple[Tensor, Tensor]:
+                  exclude="profile", candidates=None) -> Tuple[Tensor, Tensor]:
         """The k best items of the whole catalogue per user: (scores [B, k] float32, ids [B, k] int64), best first.
 
         Scores equal what forward(profile, [(ids, attrs, context broadcast)]) returns for those items (eval mode: the
@@ -1253,16 +1253,23 @@ class CARCA(_PackedModule, Model):
         exclude: "profile" (the profile's items), None, or an int [B, E] tensor of ids (0 = no entry).  Ties go to the
         smaller id; fewer than k eligible items pad with id 0 and score 0.  Needs model.eval(); L <= 64, a (d, H) with
         fused kernels built and 1 <= k <= 128.  The item-side tables are built on the first call and cached per weight
-        version (item_table / context_matrix / recommend_tables)."""
+        version (item_table / context_matrix / recommend_tables).
+
+        candidates: None (the whole catalogue), or a set S of item ids shared by the batch -- a catalogue.CandidateSet
+        built for this model's n_items, or a raw 1-D integer tensor / bool mask [n_items], which builds one for this call
+        and so costs a host sync per call.  The result is then the k best items of S minus the excluded ones, in the same
+        order and with the same padding; a returned item's score is bit-identical to the unrestricted call's for that
+        (user, item), and time and scratch ([B, |S|]) follow |S|, not n_items.  An empty S returns all zeros."""
         if self.training:
             raise CarcaHipError("recommend: the model is in training mode; recommendation scores with eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
         return catalogue.recommend("recommend", _lib.RecommendDesc, "carca_recommend",
-                                   partial(catalogue.carca_model_side, self, profile, context), profile, k, exclude)
+                                   partial(catalogue.carca_model_side, self, profile, context), profile, k, exclude,
+                                   candidates)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
-                   exclude="profile") -> Tuple[Tensor, Tensor]:
+                   exclude="profile", candidates=None) -> Tuple[Tensor, Tensor]:
         """Exact full-catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64).
 
         items: an int32 / int64 [B, N] tensor, 1 <= N <= 128.  ranks[u, j] is the 0-based number of ELIGIBLE catalogue
@@ -1270,13 +1277,19 @@ class CARCA(_PackedModule, Model):
         smaller id) -- the position recommend would give it, at any depth; an excluded item still gets the position it
         would take.  scores[u, j] is what forward / recommend returns for it.  An id of 0 or outside [0, n_items) gives
         rank -1 and score 0 (no host check, no out-of-bounds read).  profile, context, exclude and the envelope are
-        recommend's; the item-side tables come from the same caches."""
+        recommend's; the item-side tables come from the same caches.
+
+        candidates: as recommend's.  With a set S, ranks[u, j] counts the eligible items OF S (in S, not excluded) that
+        come before items[u, j] -- the position recommend(candidates=S) would give it; a target outside S, like an
+        excluded or repeated one, still gets the position it would take, and with an empty S every valid target has
+        rank 0.  scores keep their meaning and their bits."""
         if self.training:
             raise CarcaHipError("rank_items: the model is in training mode; ranks use eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
         return catalogue.rank_items("rank_items", _lib.RankDesc, "carca_rank_items",
-                                    partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude)
+                                    partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude,
+                                    candidates)
 
     # ---- inference: one host call per forward (include/carca_hip.h: carca_forward) -----------------------------
     def _fused_ok(self, trace) -> bool:

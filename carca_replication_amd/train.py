@@ -102,25 +102,55 @@ def evaluate(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[flo
     return hr / users, ndcg / users, loss_sum / max(n_batches, 1)
 
 
-def evaluate_full(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[float, float]:
+def _candidate_set(model, method: str, candidates, device):
+    """candidates of evaluate_full / evaluate_full_ranks -> None or a catalogue.CandidateSet on `device`, built once for
+    the whole evaluation; a model whose `method` has no candidates argument (KNN) cannot be restricted."""
+    import inspect
+
+    from .catalogue import CandidateSet
+
+    if candidates is None:
+        return None
+    if "candidates" not in inspect.signature(getattr(model, method)).parameters:
+        raise CarcaHipError(f"evaluate_full: {type(model).__name__}.{method} takes no candidate set (candidates= is "
+                            "CARCA's; pass candidates=None)")
+    if not isinstance(candidates, CandidateSet):
+        if not isinstance(candidates, torch.Tensor):
+            raise CarcaHipError("evaluate_full: candidates must be None, a CandidateSet or a 1-D integer / bool tensor")
+        with torch.no_grad():
+            n_items = model.embeds.item_table().shape[0]  # (the table the calls below score against, cached)
+        candidates = CandidateSet(candidates, n_items, device=device)
+    return candidates.to(device)
+
+
+def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candidates=None) -> Tuple[float, float]:
     """(HR@k, NDCG@k) with the positive o_x[:, 0] ranked against EVERY item of the catalogue instead of the loader's
     sampled negatives (full-ranking protocol; Krichene & Rendle, KDD 2020).  Per batch: model.recommend (CARCA.recommend or
     KNN.recommend) with the positive's context o_c[:, 0] (data.py:185) and the profile's items minus the positive
     excluded; the positive's rank is its position in the top-k list (ties: the smaller id first).  Same loaders as
-    evaluate(); one host sync at the end."""
+    evaluate(); one host sync at the end.
+    candidates: None, or the item set S the ranking is restricted to (catalogue.CandidateSet, or a raw tensor normalised
+    once here; CARCA only): the positive is ranked among S, and a user whose positive is not in S is left out of the
+    sums and of the user count (membership is tested on the device, no extra sync)."""
     model = model.eval().to(device)
+    cand = _candidate_set(model, "recommend", candidates, device)
     sums = torch.zeros(3, dtype=torch.float32, device=device)
     with torch.no_grad():
         for batch in loader:
             p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
             pos = o_x[:, :1].to(torch.int64)
             excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
-            _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl)
+            if cand is None:
+                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl)
+                users = ids.shape[0]
+            else:  # (a positive outside S is never in the list: it only has to leave the user count)
+                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl, candidates=cand)
+                users = cand.contains(pos).sum()
             hit = ids == pos
             rank = torch.arange(k, device=ids.device, dtype=torch.float32).expand_as(ids)
             sums[0] += hit.sum()
             sums[1] += (hit.to(torch.float32) / torch.log2(rank + 2.0)).sum()
-            sums[2] += ids.shape[0]
+            sums[2] += users
     hr, ndcg, users = (float(v) for v in sums.cpu())
     if torch.device(device).type == "cuda":
         ops.poll_errors()
@@ -166,21 +196,28 @@ def _check_ks(ks):
     return ks
 
 
-def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5, 10, 20, 50)) -> dict:
+def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5, 10, 20, 50), candidates=None) -> dict:
     """evaluate_full's protocol -- the positive o_x[:, 0] with its context o_c[:, 0] against every item, the profile's
     items other than the positive excluded -- in one pass for every cutoff: the positive's exact rank comes from
     model.rank_items (CARCA.rank_items or KNN.rank_items: a count over the catalogue, no top-k list), so any k >= 1 is
     allowed.  Returns {"HR@k", "NDCG@k" for k in ks, "MRR", "mean_rank", "users"} (full_rank_metrics).  Same loaders as
-    evaluate(); sums stay on the device, one host sync at the end."""
+    evaluate(); sums stay on the device, one host sync at the end.
+    candidates: as evaluate_full's: the positive's rank is its rank among S, and a user whose positive is not in S is left
+    out of the sums and of "users"."""
     ks = _check_ks(ks)
     model = model.eval().to(device)
+    cand = _candidate_set(model, "rank_items", candidates, device)
     sums = torch.zeros(2 * len(ks) + 3, dtype=torch.float64, device=device)
     with torch.no_grad():
         for batch in loader:
             p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
             pos = o_x[:, :1].to(torch.int64)
             excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
-            _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl)
+            if cand is None:
+                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl)
+            else:
+                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl, candidates=cand)
+                ranks = torch.where(cand.contains(pos), ranks, torch.full_like(ranks, -1))  # (_rank_sums skips them)
             sums += _rank_sums(ranks, ks)
     out = _metrics_from_sums(sums, ks)
     if torch.device(device).type == "cuda":

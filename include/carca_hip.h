@@ -850,6 +850,33 @@ typedef struct CarcaRankDesc {
 } CarcaRankDesc;
 int carca_rank_items(const CarcaRankDesc* desc, void* stream);
 
+/* ---- top-k and exact ranks among a candidate set ("among THESE items": in stock, one category, cold items; full-ranking
+ * metrics over a target item set) ------------------------------------------------------------
+ * CarcaCandidates is one set S of item ids shared by the batch: ids [n] int32 on the device, ASCENDING and DISTINCT (the
+ * caller's contract: positions then order as ids do, so ties still go to the smaller id), every id in [1, n_items).  An id
+ * outside [1, n_items) in the list is treated as not live and is never read out of bounds.  n = 0 is legal (no sweep is
+ * launched).  The descriptors are carca_recommend's and carca_rank_items' own, and carca_recommend / carca_rank_items are
+ * the same implementation over the whole catalogue: the logit of a (user, item) pair does not depend on the position that
+ * holds the item, so scores and the item order are bit-identical to the unrestricted calls'.
+ *
+ * carca_recommend_among: the k best items of S minus the excluded ids per user, in carca_recommend's order, padded with
+ * id 0 and score 0.  The logit scratch is [B, n], indexed by position; exclusion finds an excluded id's position by binary
+ * search; selection keys on the position and writes ids[position].
+ *
+ * carca_rank_items_among: ranks[u][j] = number of eligible items OF S (in S, not excluded) that order strictly before
+ * items[u][j]; a target outside S, an excluded or a repeated one still gets the position it would take; id 0 or an id
+ * outside [0, n_items): rank -1 and score 0.  scores as carca_rank_items.  The counting sweep runs over S; the correction
+ * subtracts only the distinct excluded ids that S holds.
+ *
+ * Cost falls with n: the sweep's grid, the scratch and the selection cover n positions, not n_items.  Errors as the
+ * unrestricted calls, and CARCA_ERR_BADARG for a null list, n < 0, or null ids with n > 0. */
+typedef struct CarcaCandidates {
+  const int32_t* ids; /* [n] ascending, distinct, in [1, n_items) */
+  int n;
+} CarcaCandidates;
+int carca_recommend_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
+int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* candidates, void* stream);
+
 /* ---- KNN baseline: full-catalogue top-k and exact ranks (replace KNN.forward over the catalogue as target groups:
  * knn.py:13-19 over the candidate lists of data.py:180-185, ranked as train.py:15-32 does) ------
  * The catalogue is the rows of the attribute table [n_items, ld_table] (fp32, F features).  For user u and item i >= 1:

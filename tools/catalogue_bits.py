@@ -10,8 +10,11 @@ normalised and not) with and without a context matrix (AllEmbedding, IdEmbedding
 tile; more users than user chunks; k = 1, 10, 128; lists of 1, 101 and 128 ids holding id 0, out-of-range, repeated and
 excluded ids; exclude = "profile", None and a [B, 1100] tensor with zeros and duplicates; fewer eligible items than k;
 KNN in table mode on a multi-hot table (i8) and on real-valued tables (fp32, F % 4 != 0 too) and in dense mode; the C2
-shapes of tools/bench_recommend.py and tools/bench_knn_catalogue.py.
-usage: python tools/catalogue_bits.py [--package-root DIR] [--out listing.txt]"""
+shapes of tools/bench_recommend.py and tools/bench_knn_catalogue.py.  Every CARCA case ends with the calls restricted to
+candidate sets (lines named .../among-...): a tenth of the catalogue, a set of 257 ids (one past a
+tile; the whole catalogue where it is smaller) and the empty set, drawn after everything else so that the unrestricted
+lines keep their inputs; --no-candidates leaves them out, for a tree from before the candidate sets.
+usage: python tools/catalogue_bits.py [--package-root DIR] [--no-candidates] [--out listing.txt]"""
 import argparse
 import hashlib
 import os
@@ -19,6 +22,7 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--no-candidates", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.package_root))
@@ -93,8 +97,9 @@ def _exclude(g, B, n_items, lists):
     return ex
 
 
-def _calls(name, model, prof, ctx, g, B, n_items, p_x):
-    """The six calls of a case: k = 1 / 10 / 128 and N = 1 / 101 / 128 against the three kinds of exclusion."""
+def _calls(name, model, prof, ctx, g, B, n_items, p_x, among=False):
+    """The six calls of a case: k = 1 / 10 / 128 and N = 1 / 101 / 128 against the three kinds of exclusion; with `among`,
+    four more per candidate set."""
     lists = {N: _lists(g, B, N, n_items, p_x) for N in (1, 101, 128)}
     ex = _exclude(g, B, n_items, lists[101]).cuda()
     out = []
@@ -105,6 +110,16 @@ def _calls(name, model, prof, ctx, g, B, n_items, p_x):
         for N, e, tag in ((1, "profile", "profile"), (101, ex, "tensor"), (128, None, "none")):
             s, r = model.rank_items(prof, ctx, lists[N].cuda(), exclude=e)
             out += [(f"{name}/rank-N{N}-{tag}/scores", _sha(s)), (f"{name}/rank-N{N}-{tag}/ranks", _sha(r))]
+        for c in (max(1, n_items // 10), min(257, n_items - 1), 0) if among else ():
+            S = (torch.randperm(n_items - 1, generator=g)[:c] + 1).cuda()  # (unsorted: the call normalises it)
+            for k, e, tag in ((10, ex, "tensor"), (128, "profile", "profile")):
+                s, i = model.recommend(prof, ctx, k=k, exclude=e, candidates=S)
+                out += [(f"{name}/among-{c}/recommend-k{k}-{tag}/scores", _sha(s)),
+                        (f"{name}/among-{c}/recommend-k{k}-{tag}/ids", _sha(i))]
+            for N, e, tag in ((1, "profile", "profile"), (101, ex, "tensor")):
+                s, r = model.rank_items(prof, ctx, lists[N].cuda(), exclude=e, candidates=S)
+                out += [(f"{name}/among-{c}/rank-N{N}-{tag}/scores", _sha(s)),
+                        (f"{name}/among-{c}/rank-N{N}-{tag}/ranks", _sha(r))]
     return out
 
 
@@ -125,7 +140,8 @@ def carca_case(seed, name, d, H, emb, dec, flag, L, B, n_items, n_attrs, g_dim, 
     p_x = _profile(g, B, L, n_items)
     p_c = torch.rand(B, L, n_ctx, generator=g) * (p_x != 0).unsqueeze(-1)
     ctx = torch.rand(B, n_ctx, generator=g).cuda() if n_ctx else None
-    return _calls("carca/" + name, model, (p_x.cuda(), None, p_c.cuda()), ctx, g, B, n_items, p_x)
+    return _calls("carca/" + name, model, (p_x.cuda(), None, p_c.cuda()), ctx, g, B, n_items, p_x,
+                  among=not args.no_candidates)
 
 
 def knn_case(seed, name, kind, n_items, F, B, L, dense):
