@@ -851,7 +851,7 @@ extern "C" int carca_layernorm_bwd(const float* dy, int ld_dy, const float* x, i
   const bool vec = ld_dy % 4 == 0 && ld_x % 4 == 0 && ld_dx % 4 == 0 && (!addend || ld_add % 4 == 0) &&
                    ((d + 3) & ~3) <= ld_dy && ((d + 3) & ~3) <= ld_x && (!addend || ((d + 3) & ~3) <= ld_add) &&
                    ncols_out % 4 == 0 && (size_t)rows * (size_t)max(max(ld_dy, ld_x), max(ld_dx, ld_add)) < (1u << 29) &&
-                   carca_tuning(6) != 1;
+                   carca_tuning(CARCA_TUNE_ROUND1_PATHS) != 1;
   if (vec) {
     const int nb = min((rows + 31) / 32, carca_num_cus());
     hipLaunchKernelGGL(layernorm_bwd_pairs_kernel<4>, dim3(nb), dim3(256), 0, stream, dy, ld_dy, x, ld_x, gamma, rows, d,

@@ -92,7 +92,7 @@ extern "C" int carca_sa_block_bwd(const CarcaSaBwdDesc* D, CarcaWgradDesc* wgrad
   int rc;
   // Without dropout the two row chains run as ONE launch each (row_chain.hip) around the attention core: 3 launches per
   // block instead of 6 (tuning key 6 = 1 or 2: the launch-per-step path below).
-  if (!drop && dpi == dpo && dpi <= 96 && carca_tuning(6) == 0) {  // (dpi = 128: 16 waves leave 128 registers, the chain kernel would spill)
+  if (!drop && dpi == dpo && dpi <= 96 && carca_tuning(CARCA_TUNE_ROUND1_PATHS) == 0) {  // (dpi = 128: 16 waves leave 128 registers, the chain kernel would spill)
     if ((rc = carca_sa_ffn_chain_bwd(D->dy, D->h1, D->r, D->w2_t, D->w1_t, D->ln2_w, rows, d, dpi, D->residual, dh1pre, dr,
                                      D->g_ln2_w, D->g_ln2_b, stream)))
       return rc;

@@ -217,12 +217,54 @@ __device__ __forceinline__ void carca_warm_kernargs() {
   asm volatile("" ::"s"(w));
 }
 
-// tuning knobs (api.hip): small integers a tuning run selects with carca_set_tuning(); 0 = shipped choice.  ONE meaning
-// per key (include/carca_hip.h lists them); keys 3..7 are used by number.
-enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRAD_SLOTS = 2, CARCA_TUNE_DETERMINISTIC = 8,
+// tuning knobs (api.hip): small integers a tuning run selects with carca_set_tuning(); 0 = shipped choice.  The numbers are
+// the wire values that tests/ and tools/ pass (include/carca_hip.h lists them).  Key 5 has two readers.
+enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRAD_SLOTS = 2,
+       CARCA_TUNE_WGRAD_PLAIN_STORE = 3,   // tiled weight gradient: plain stores instead of atomics (timing; wrong results)
+       CARCA_TUNE_WGRAD_MIN_CHUNKS = 4,    // tiled weight gradient: minimum 32-row chunks per row split
+       CARCA_TUNE_WGRAD_GROUP_SLOTS = 5,   // grouped weight gradient: row-split slot target per product ...
+       CARCA_TUNE_N96S_DIAG = 5,           // ... and gemm_rows_n96s_kernel's timing experiments (bit mask; wrong results)
+       CARCA_TUNE_ROUND1_PATHS = 6,        // 1: materialised V in the scoring kernel, per-op SelfAttentionBlock paths
+       CARCA_TUNE_SCORE_LAYOUT = 7,        // scoring kernel layout
+       CARCA_TUNE_DETERMINISTIC = 8,
        CARCA_TUNE_STAMPS = 9, CARCA_TUNE_CU_CAP = 10, CARCA_TUNE_SK_DON = 11, CARCA_TUNE_SK_SPIN_LOG2 = 12,
        CARCA_TUNE_SK_WITHHOLD = 13, CARCA_TUNE_XS_OPT = 14, CARCA_TUNE_DIAG = 15, CARCA_TUNE_SPLIT_GEMM = 16,
+       CARCA_TUNE_SKC_OV_TEAM = 17,        // gemm_rows_skc_kernel: 1 + what owning a row block costs a team, in K steps
+       CARCA_TUNE_SKC_OV_LONE = 18,        // ... and a lone workgroup
+       CARCA_TUNE_SKC_MIN_STEPS = 19,      // ... and the K steps below which the product stays off that kernel
        CARCA_TUNE_FEAT_DEDUP = 20, CARCA_TUNE_COUNT = 24 };
+// Values of key 0 (CARCA_TUNE_GEMM_VARIANT): A/B switches of the row GEMMs, the weight-gradient GEMMs and the gather, one
+// at a time -- which is why 158 exists.  A value with two meanings switches both.
+enum {
+  CARCA_GV_AUTO = 0,
+  CARCA_GV_TILED = 1,            // rows: the 128 x 96 tiled kernel (never narrow, never one block per CU)
+  CARCA_GV_PER_CU = 2,           // rows: force the one-block-per-CU choice; weight gradient: force the persistent kernel
+  CARCA_GV_PER_CU_STAMPS = 3,    // = 2 + in-kernel phase stamps, both directions
+  CARCA_GV_NO_BUFFER_LOADS = 4,  // rows and tiled weight gradient: no buffer loads; weight gradient: never the persistent kernel
+  CARCA_GV_WGRAD_TILED = 5,      // weight gradient: never the persistent kernel
+  CARCA_GV_NO_GROUP = 6,         // rows and weight gradients: never share a launch between products
+  CARCA_GV_PER_CU_128 = 7,       // rows: 384 x 128 tiles where the tiled kernel would run
+  CARCA_GV_NO_PASSENGER = 8,     // the item-row gather never rides in the feature GEMM's launch
+  CARCA_GV_WIDE64 = 9,           // narrow rows: 64 x 96 tiles, prefetch depth 4 ...
+  CARCA_GV_WIDE64_PF2 = 10,      // ... and 2
+  CARCA_GV_N96 = 11,             // narrow rows: the 80 x 96 kernel wherever it applies ...
+  CARCA_GV_NO_N96 = 12,          // ... and never
+  CARCA_GV_WGRAD_EQUAL_ITEMS = 13,   // persistent weight gradient: equal item counts
+  CARCA_GV_WGRAD_ATOMIC_FLUSH = 14,  // persistent weight gradient: atomic flush instead of partial-tile slots
+  CARCA_GV_NO_STREAM_K = 15,     // feature GEMM: one tile per workgroup, no hand-over of partial tiles
+  CARCA_GV_WGRAD_FLAT_GROUPS = 16,   // persistent weight gradient: consecutive workgroups, no per-XCD groups
+  CARCA_GV_GATHER_ROW_PER_WAVE = 18,  // the gather's own launch: one row per wave
+  CARCA_GV_OWN_GATHER = 19,      // the gather keeps its own launch beside the stream-K kernels; AND tiled weight gradient:
+  CARCA_GV_WPART_ATOMICS = 19,   // row splits combine by atomics instead of partial tiles
+  CARCA_GV_SPLIT_NO_DMA = 21,    // split-precision kernel: register-staged, no LDS-DMA
+  CARCA_GV_WGRAD_NO_COMPACT = 22,  // persistent weight gradient: masked rows stay in the row table
+  CARCA_GV_SK_EVERY_ROW = 23,    // feature GEMM: gemm_rows_sk_kernel over every row instead of gemm_rows_skc_kernel
+  CARCA_GV_NO_CUS = 24,          // short-K streaming kernel (gemm_rows_cus_kernel): never ...
+  CARCA_GV_CUS = 25,             // ... and wherever it is correct
+  CARCA_GV_NO_N96S = 26,         // persistent narrow-output kernel (gemm_rows_n96s_kernel): never ...
+  CARCA_GV_N96S = 27,            // ... and wherever it is correct
+  CARCA_GV_NO_STREAM_K_NO_PASSENGER = 158,  // 15 + 8
+};
 int carca_tuning(int key);
 int carca_num_cus();  // compute units of the current device (cached)
 // True while `stream` is being captured into a hipGraph.

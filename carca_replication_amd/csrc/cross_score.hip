@@ -12,6 +12,7 @@
 //            sigmoid(w.o + b) (carca.py:339).  Pad targets (id 0) attend nothing.
 #include <hip/hip_ext.h>
 #include "attn_common.h"
+#include "gemm_host.h"
 #include "cross_fold.h"
 #include "../../include/carca_hip.h"
 
@@ -818,11 +819,8 @@ int launch_fold_nw(const FoldArgs& fa, int B, hipStream_t stream) {
     }
     attr_set = true;
   }
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))  // (timing events bound to this dispatch: carca_forward's ev[2], ev[3])
-    hipExtLaunchKernelGGL(kern, dim3(B * fa.nparts), dim3(NW * 64), lds_bytes, stream, e0, e1, 0, fa);
-  else
-    hipLaunchKernelGGL(kern, dim3(B * fa.nparts), dim3(NW * 64), lds_bytes, stream, fa);
+  // (timing events bound to this dispatch: carca_forward's ev[2], ev[3])
+  carca_launch(kern, dim3(B * fa.nparts), dim3(NW * 64), lds_bytes, stream, true, fa);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -840,7 +838,7 @@ int launch_fold(FoldArgs& fa, int B, hipStream_t stream) {
   // two workgroups started together stay in lockstep -- the launch got longer by exactly the delay.)
   if (fa.nparts == 1 && (tune == 3 || (tune == 0 && B > num_cus)))
     return launch_fold_nw<DPI, DHP, NH, 8, false>(fa, B, stream);
-  if (carca_tuning(7) == 1) return launch_fold_nw<DPI, DHP, NH, 16, false>(fa, B, stream);
+  if (carca_tuning(CARCA_TUNE_SCORE_LAYOUT) == 1) return launch_fold_nw<DPI, DHP, NH, 16, false>(fa, B, stream);
   return launch_fold_nw<DPI, DHP, NH, 16, true>(fa, B, stream);
 }
 
@@ -867,13 +865,9 @@ int launch_cross_nw(const float* p_raw, int ldp, const int32_t* p_ids, float* p_
     }
     attr_set = true;
   }
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))  // (timing events bound to this dispatch: carca_forward's ev[2], ev[3])
-    hipExtLaunchKernelGGL(kern, dim3(B * nparts), dim3(NW * 64), lds_bytes, stream, e0, e1, 0, p_raw, ldp, p_ids, p_normed,
-                          groups, ldo, L, d, d / NH, w, residual, training, sv, dc, site, nparts, carca_debug_buffer());
-  else
-    hipLaunchKernelGGL(kern, dim3(B * nparts), dim3(NW * 64), lds_bytes, stream, p_raw, ldp, p_ids, p_normed, groups, ldo, L,
-                       d, d / NH, w, residual, training, sv, dc, site, nparts, carca_debug_buffer());
+  // (timing events bound to this dispatch: carca_forward's ev[2], ev[3])
+  carca_launch(kern, dim3(B * nparts), dim3(NW * 64), lds_bytes, stream, true, p_raw, ldp, p_ids, p_normed, groups, ldo, L, d,
+               d / NH, w, residual, training, sv, dc, site, nparts, carca_debug_buffer());
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -928,7 +922,7 @@ extern "C" int carca_cross_score_fwd(const float* p_raw, int ldp, const int32_t*
   gd.n = ngroups;
   CARCA_CHECK_ARG(!(drop && drop->p >= 1.0f), "cross_score_fwd: dropout p must be < 1");
   // eval mode (nothing saved, no dropout, no causal mask): the folded kernel (tuning key 6 = 1 forces the other one)
-  if (!save && !training && w->wu && w->cu && carca_tuning(6) != 1 && ldp % 4 == 0 && ldp >= dpi) {
+  if (!save && !training && w->wu && w->cu && carca_tuning(CARCA_TUNE_ROUND1_PATHS) != 1 && ldp % 4 == 0 && ldp >= dpi) {
     FoldArgs fa{};
     fa.p_raw = p_raw; fa.p_ids = p_ids; fa.p_normed = p_normed;
     for (int i = 0; i < ngroups; ++i) fa.g[i] = gd.g[i];
@@ -944,7 +938,7 @@ extern "C" int carca_cross_score_fwd(const float* p_raw, int ldp, const int32_t*
     // Persistent workgroups that pipeline their units of work (cross_stream.hip): every batch size where they are not
     // slower -- tuning key 7: 2 = never, 3 = at every batch size, 0 = above #CUs users.  It has no p_normed output and
     // no instantiation above d = 96: the per-user kernel below then runs.
-    const int t7 = carca_tuning(7);
+    const int t7 = carca_tuning(CARCA_TUNE_SCORE_LAYOUT);
     const int tune1 = carca_tuning(CARCA_TUNE_ATTN_VARIANT);
     // (... and from 48 target tiles per user on -- C5's 1 + 1000 candidates are 63 --: the per-user kernel fetches W_Q and the
     // target rows per (tile, head) job through the CU's load path, 53.4 us at C5 against 47.7 here; at 301 candidates 24.1

@@ -28,6 +28,7 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 #include "attn_common.h"
+#include "gemm_host.h"
 #include "cross_fold.h"
 #include "../../include/carca_hip.h"
 
@@ -624,11 +625,7 @@ int launch_stream(const FoldArgs& fa, int B, hipStream_t stream) {
       attr_set = true;
     }
     const int grid = min(B * fa.nparts, carca_num_cus());
-    hipEvent_t e0, e1;
-    if (carca_take_launch_events(&e0, &e1))
-      hipExtLaunchKernelGGL(kern, dim3(grid), dim3(XS_NW * 64), lds_bytes, stream, e0, e1, 0, fa);
-    else
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(XS_NW * 64), lds_bytes, stream, fa);
+    carca_launch(kern, dim3(grid), dim3(XS_NW * 64), lds_bytes, stream, true, fa);
     CARCA_LAUNCH_CHECK();
     return CARCA_OK;
   }

@@ -65,8 +65,8 @@ extern "C" int carca_embed_fwd(const CarcaRowSeg* segs, int nseg, int n_attrs, i
 
   ga.items_w = items_w; ga.zq = zq; ga.d = d; ga.ldz = ldz; ga.total_rows = total_rows; ga.scale = (float)sqrt((double)d);
   auto launch_gather = [&]() -> int {
-    const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);  // (18: one row per wave, 2048 blocks at most -- A/B switch)
-    if (variant == 18) {
+    const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);  // (one row per wave, 2048 blocks at most -- A/B switch)
+    if (variant == CARCA_GV_GATHER_ROW_PER_WAVE) {
       hipLaunchKernelGGL(gather_items_kernel<1>, dim3(min((total_rows + 3) / 4, 2048)), dim3(256), 0, stream, ga);
     } else {
       hipLaunchKernelGGL(gather_items_kernel<4>, dim3(min((total_rows + 15) / 16, 8192)), dim3(256), 0, stream, ga);

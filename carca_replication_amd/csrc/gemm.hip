@@ -1,28 +1,25 @@
-// Dense building blocks on v_mfma_f32_32x32x2_f32 (exact fp32):
+// The row GEMM on v_mfma_f32_32x32x2_f32 (exact fp32):
 //
 //   carca_gemm_rows   C[m][n]  = sum_k A[m][k] * Bt[n][k] (+ epilogue)     rows = users x slots
-//   carca_gemm_wgrad  dW[n][k] += sum_r dY[r][n] * X[r][k]                  contraction over rows
 //
 // gemm_rows is the kernel behind AllEmbedding's feats_embed / joint_embed (carca.py:86,89; 97% of
-// the model's flops at n_attrs = 4096) and every input-gradient product of the backward pass;
-// gemm_wgrad produces every weight gradient (the feats_embed one is as large as the forward GEMM).
+// the model's flops at n_attrs = 4096) and every input-gradient product of the backward pass.  (The weight gradients:
+// gemm_wgrad.hip and wgrad_cu.hip.)
 //
-// Kernels in this file (the launchers at the bottom pick one from the shape):
+// Kernels in this file (gemm_rows_choose + gemm_rows_dispatch at the bottom pick one from the shape):
 //   gemm_rows_cu_kernel      ONE 384 x 96 block per CU, hand-scheduled K step: the feature GEMM (see its own comment)
+//   gemm_rows_sk_kernel, gemm_rows_skc_kernel   the same tiles with stream-K hand-over of partial tiles (their own comments)
+//   gemm_rows_n96_kernel     one 80 x 96 block per CU: narrow outputs over about one round of rows
 //   gemm_rows_kernel<128,96> block tile 128 x 96, K step 32, 4 waves, wave w owns rows 32w..32w+31 x all 96 columns
 //                            (3 accumulator tiles), 3 blocks per CU: large products whose grid does not suit the
 //                            one-block-per-CU kernel
 //   gemm_rows_kernel<128,32> 32-column blocks + a 4-deep register prefetch ring: narrow outputs (joint embedding,
 //                            every d-wide product of the backward pass)
-//   gemm_wgrad_kernel        block tile 96 (n) x 128 (k), 32 rows per step; both operands are read from their
-//                            row-major LDS tiles TRANSPOSED (lane = n resp. k), so neither dY nor X is ever transposed
-//                            in memory; row splits combine through fp32 atomics.  gemm_wgrad_group_kernel runs several
-//                            such products in one launch.  (The feats_embed weight gradient: wgrad_cu.hip.)
 // Common: operands staged global -> registers -> LDS with rows padded to 36 floats (conflict-free 16-byte fragment
 // reads), buffer loads with 32-bit offsets wherever they provably fit, blocks that share an A row block numbered so
 // that they land on the same XCD (the A tile is fetched from HBM once and re-read from that XCD's L2).
-#include <hip/hip_ext.h>
-#include "carca_common.h"
+// The process-wide kernel error word (carca_kernel_error_word, carca_poll_errors) lives here too.
+#include "gemm_host.h"
 #include <type_traits>
 #include <vector>
 #include "../../include/carca_hip.h"
@@ -1810,260 +1807,13 @@ __global__ __launch_bounds__(768) void gemm_rows_n96_kernel(const GemmDev args) 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-struct WgradDev {
-  CarcaWgradDesc d;
-  int chunk_start[CARCA_MAX_SEGS + 1];  // 32-row chunks per segment, prefix sums
-  int nnb, nkb, nkb0, nsplit, chunks_per_split;
-  int diag_plain_store;  // diagnostic (tuning key 3): overwrite instead of atomicAdd, to time the kernel without atomics
-  // Row splits WITHOUT atomics: block (split, nb, kb) stores its 96 x 128 tile plainly, in register order, at
-  // part[((split * nnb + nb) * nkb + kb) * 12288 ..] and wgrad_part_reduce adds a tile's splits in order into dw.  (A/B at
-  // C2 with plain stores in place of the atomics, wrong results: train step -43 us -- an fp32 atomic costs ~5 ns and the
-  // thirteen d x d products + the joint-embedding dW issue 11 M of them per step.)  NULL = atomics (grad_add).
-  float* part;
-};
-
-template <int BNO, int BKO, int BR, bool BUF>
-__device__ __forceinline__ void wgrad_body(const WgradDev& args, int b) {
-  static_assert(BNO == 96 && BKO == 128 && BR == 32, "tile shape baked into the lane maps below");
-  constexpr int NT = 256;
-  __shared__ __attribute__((aligned(16))) float Ys[BR * BNO];  // dY tile [row][n]
-  __shared__ __attribute__((aligned(16))) float Xs[BR * BKO];  // X  tile [row][k]
-
-  const CarcaWgradDesc& D = args.d;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kb = b % args.nkb;
-  b /= args.nkb;
-  const int nb = b % args.nnb;
-  const int split = b / args.nnb;
-  const bool src1 = kb >= args.nkb0;  // this block's dW columns come from the second X source
-  const int n0 = nb * BNO, k0 = (src1 ? kb - args.nkb0 : kb) * BKO;
-  const int klen = src1 ? D.K1 : D.K;
-  const int ldx = src1 ? D.ld_x1 : D.ld_x;
-  const int c_begin = split * args.chunks_per_split;
-  const int c_end = min(c_begin + args.chunks_per_split, args.chunk_start[D.nseg]);
-  const bool n_full = n0 + BNO <= D.N, k_full = k0 + BKO <= klen;
-
-  constexpr int Y4 = BNO / 4, X4 = BKO / 4;                            // float4 per tile row
-  constexpr int Y_PER = BR * Y4 / NT, X_PER = BR * X4 / NT;            // 3, 4
-  f32x4 ry[Y_PER], rx[X_PER];
-
-  auto load_chunk = [&](int c) {
-    int s = 0;
-#pragma unroll
-    for (int i = 1; i < CARCA_MAX_SEGS; ++i)
-      if (i < D.nseg && c >= args.chunk_start[i]) s = i;
-    const CarcaWgradSeg sg = D.seg[s];
-    const int r0 = (c - args.chunk_start[s]) * BR;
-#pragma unroll
-    for (int i = 0; i < Y_PER; ++i) {
-      const int slot = tid + i * NT;
-      const int r = slot / Y4, c4 = slot - r * Y4;
-      const int row = r0 + r;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      bool ok = row < sg.rows;
-      if (ok && D.mask_rows) ok = sg.ids[row] != 0;
-      if (ok) {
-        const float* p = sg.dy + (size_t)row * D.ld_dy + n0 + c4 * 4;
-        if (n_full) {
-          if constexpr (BUF)
-            v = gload4(sg.dy, row * D.ld_dy + n0 + c4 * 4);
-          else
-            v = *reinterpret_cast<const f32x4_u*>(p);
-        } else {
-          const int nn = n0 + c4 * 4;
-          v[0] = nn + 0 < D.N ? p[0] : 0.f;
-          v[1] = nn + 1 < D.N ? p[1] : 0.f;
-          v[2] = nn + 2 < D.N ? p[2] : 0.f;
-          v[3] = nn + 3 < D.N ? p[3] : 0.f;
-        }
-      }
-      ry[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < X_PER; ++i) {
-      const int slot = tid + i * NT;
-      const int r = slot / X4, c4 = slot - r * X4;
-      const int row = r0 + r;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row < sg.rows) {
-        const int64_t bs = src1 ? sg.x1_bstride : sg.x_bstride;
-        const size_t roff = (!src1 && sg.x_gather) ? (size_t)sg.ids[row] * ldx
-                            : bs                    ? (size_t)(row / sg.T) * bs + (size_t)(row % sg.T) * ldx
-                                                    : (size_t)row * ldx;
-        const float* p = (src1 ? sg.x1 : sg.x) + roff + k0 + c4 * 4;
-        if (k_full) {
-          if constexpr (BUF)
-            v = gload4(src1 ? sg.x1 : sg.x, (int)roff + k0 + c4 * 4);
-          else
-            v = *reinterpret_cast<const f32x4_u*>(p);
-        } else {
-          const int kk = k0 + c4 * 4;
-          v[0] = kk + 0 < klen ? p[0] : 0.f;
-          v[1] = kk + 1 < klen ? p[1] : 0.f;
-          v[2] = kk + 2 < klen ? p[2] : 0.f;
-          v[3] = kk + 3 < klen ? p[3] : 0.f;
-        }
-      }
-      rx[i] = v;
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int i = 0; i < Y_PER; ++i) {
-      const int slot = tid + i * NT;
-      *reinterpret_cast<f32x4*>(&Ys[slot * 4]) = ry[i];
-    }
-#pragma unroll
-    for (int i = 0; i < X_PER; ++i) {
-      const int slot = tid + i * NT;
-      *reinterpret_cast<f32x4*>(&Xs[slot * 4]) = rx[i];
-    }
-  };
-
-  // wave w owns k columns 32w..32w+31 of the block's 128 and all three 32-wide n tiles
-  f32x16 acc[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  float bsum = 0.f;  // thread t < 96 of a kb == 0 block sums column n0 + t of dY
-
-  const int lr = lane & 31, lh = lane >> 5;
-  if (c_begin < c_end) {
-    load_chunk(c_begin);
-    store_chunk();
-  }
-  __syncthreads();
-  for (int c = c_begin; c < c_end; ++c) {
-    if (c + 1 < c_end) load_chunk(c + 1);
-    // D[m = n index][n = k index] = sum_r Ys[r][m] * Xs[r][n]:  A lane (i, kk) = Ys[2s + kk][i]
-#pragma unroll 4
-    for (int st = 0; st < BR / 2; ++st) {
-      const int r = 2 * st + lh;
-      const float xb = Xs[r * BKO + wave * 32 + lr];
-      const float y0 = Ys[r * BNO + lr], y1 = Ys[r * BNO + 32 + lr], y2 = Ys[r * BNO + 64 + lr];
-      acc[0] = mfma32(y0, xb, acc[0]);
-      acc[1] = mfma32(y1, xb, acc[1]);
-      acc[2] = mfma32(y2, xb, acc[2]);
-    }
-    if (D.db && kb == 0 && tid < BNO) {
-#pragma unroll 8
-      for (int r = 0; r < BR; ++r) bsum += Ys[r * BNO + tid];
-    }
-    __syncthreads();
-    if (c + 1 < c_end) {
-      store_chunk();
-      __syncthreads();
-    }
-  }
-
-  // D row (= n) = (reg&3) + 8*(reg>>2) + 4*(lane>>5), col (= k) = lane&31
-  const int k = k0 + wave * 32 + lr;
-  if (args.part) {
-    float* dst = args.part + ((size_t)(split * args.nnb + nb) * args.nkb + kb) * (BNO * BKO);
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[(t * 16 + r) * NT + tid] = acc[t][r];
-  } else if (k < klen) {
-    const int kcol = (src1 ? D.K : 0) + k;
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (n < D.N) {
-          if (args.diag_plain_store)
-            D.dw[(size_t)n * D.ldw + kcol] = acc[t][r];
-          else
-            grad_add(&D.dw[(size_t)n * D.ldw + kcol], acc[t][r]);
-        }
-      }
-  }
-  if (D.db && kb == 0 && tid < BNO && n0 + tid < D.N) grad_add(&D.db[n0 + tid], bsum);
-}
-
-template <int BNO, int BKO, int BR, bool BUF = false>
-__global__ __launch_bounds__(256) void gemm_wgrad_kernel(const WgradDev args) {
-  wgrad_body<BNO, BKO, BR, BUF>(args, blockIdx.x);
-}
-
-// Several independent products in ONE launch: the d x d weight gradients of a backward pass are ~20 us latency-bound
-// launches of ~100 blocks each; side by side they fill the chip and cost one launch.  Block -> (problem, local block).
-constexpr int WGRAD_GROUP_MAX = 32;
-struct WgradGroupIndex {
-  int n;
-  int block_start[WGRAD_GROUP_MAX + 1];
-};
-template <int BNO, int BKO, int BR>
-__global__ __launch_bounds__(256) void gemm_wgrad_group_kernel(const WgradDev* __restrict__ devs,
-                                                               const WgradGroupIndex idx) {
-  int p = 0;
-  for (int i = 1; i < idx.n; ++i)
-    if ((int)blockIdx.x >= idx.block_start[i]) p = i;
-  wgrad_body<BNO, BKO, BR, true>(devs[p], (int)blockIdx.x - idx.block_start[p]);
-}
-
-// dw tile (nb, kb) += its splits' partial tiles, in split order (fixed: bit-reproducible).  12 blocks of 256 threads per
-// tile; a thread takes four consecutive floats of the register-order tile: the same n, four consecutive k.
-__device__ __forceinline__ void wgrad_part_reduce_body(const WgradDev& g, int lb) {
-  const CarcaWgradDesc& D = g.d;
-  const int tile = lb / 12, sl = lb - tile * 12;
-  const int nb = tile / g.nkb, kb = tile - nb * g.nkb;
-  const int q = (sl * 256 + (int)threadIdx.x) * 4;  // 0 .. 12284
-  const int e = q >> 8, t = q & 255;
-  const int wave = t >> 6, lane = t & 63, lr = lane & 31, lh = lane >> 5;
-  const size_t tile_fl = 96 * 128;
-  // eight splits' loads in flight at a time (a plain loop waits for every load before it issues the next: 22 us for
-  // 40 MB); the additions stay in split order
-  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-  const float* base = g.part + ((size_t)nb * g.nkb + kb) * tile_fl + q;
-  const size_t step = (size_t)g.nnb * g.nkb * tile_fl;
-  int s = 0;
-  for (; s + 8 <= g.nsplit; s += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const f32x4*>(base + (size_t)(s + i) * step);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sum += v[i];
-  }
-  for (; s < g.nsplit; ++s) sum += *reinterpret_cast<const f32x4*>(base + (size_t)s * step);
-  const int tt = e >> 4, r = e & 15;
-  const int n = nb * 96 + tt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-  if (n >= D.N) return;
-  const bool src1 = kb >= g.nkb0;
-  const int k0 = (src1 ? kb - g.nkb0 : kb) * 128, klen = src1 ? D.K1 : D.K;
-  float* row = D.dw + (size_t)n * D.ldw + (src1 ? D.K : 0);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k = k0 + wave * 32 + lr + i;
-    if (k < klen) row[k] += sum[i];
-  }
-}
-__global__ __launch_bounds__(256) void wgrad_part_reduce_kernel(const WgradDev g) { wgrad_part_reduce_body(g, blockIdx.x); }
-__global__ __launch_bounds__(256) void wgrad_part_reduce_group_kernel(const WgradDev* __restrict__ devs,
-                                                                      const WgradGroupIndex idx) {
-  int p = 0;
-  for (int i = 1; i < idx.n; ++i)
-    if ((int)blockIdx.x >= idx.block_start[i]) p = i;
-  wgrad_part_reduce_body(devs[p], (int)blockIdx.x - idx.block_start[p]);
-}
-
 }  // namespace
 
 template <int BM, int BN, int BK, int PF, bool BUF = false>
 static int launch_gemm_rows(const CarcaGemmDesc* desc, hipStream_t stream) {
   GemmDev g{};
   g.d = *desc;
-  int rb = 0;
-  for (int s = 0; s < desc->nseg; ++s) {
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (desc->seg[s].rows + BM - 1) / BM;
-  }
-  g.rb_start[desc->nseg] = rb;
-  g.nrb = rb;
+  const int rb = carca_fill_row_blocks(g, BM);
   g.ncb = (desc->ncols_out + BN - 1) / BN;
   const int grid = rb * g.ncb;
   if (g_rows_log_on) {
@@ -2071,11 +1821,7 @@ static int launch_gemm_rows(const CarcaGemmDesc* desc, hipStream_t stream) {
     snprintf(nm, sizeof(nm), "gemm_rows_kernel<%d,%d,%d,%d,%d>", BM, BN, BK, PF, (int)BUF);
     carca_rows_log(nm, desc, grid);
   }
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))
-    hipExtLaunchKernelGGL((gemm_rows_kernel<BM, BN, BK, PF, BUF>), dim3(grid), dim3((BM / 32) * 64), 0, stream, e0, e1, 0, g);
-  else
-    hipLaunchKernelGGL((gemm_rows_kernel<BM, BN, BK, PF, BUF>), dim3(grid), dim3((BM / 32) * 64), 0, stream, g);
+  carca_launch(gemm_rows_kernel<BM, BN, BK, PF, BUF>, dim3(grid), dim3((BM / 32) * 64), 0, stream, true, g);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -2085,14 +1831,7 @@ static int launch_gemm_rows_cu(const CarcaGemmDesc* desc, hipStream_t stream, co
                                int* rode = nullptr) {
   GemmDev g{};
   g.d = *desc;
-  int rb = 0;
-  for (int s = 0; s < desc->nseg; ++s) {
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (desc->seg[s].rows + 383) / 384;
-  }
-  g.rb_start[desc->nseg] = rb;
-  g.nrb = rb;
+  const int rb = carca_fill_row_blocks(g, 384);
   g.ncb = (desc->ncols_out + 32 * TN - 1) / (32 * TN);
   g.dbg = carca_debug_buffer();
   g.diag = carca_tuning(CARCA_TUNE_DIAG);  // (bit 6: the general tail instead of the 8-wide context group -- A/B)
@@ -2109,11 +1848,7 @@ static int launch_gemm_rows_cu(const CarcaGemmDesc* desc, hipStream_t stream, co
     if (rode) *rode = 1;
   }
   if (g_rows_log_on) carca_rows_log(TN == 4 ? "gemm_rows_cu_kernel<0,4>" : "gemm_rows_cu_kernel<0,3>", desc, grid);
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))
-    hipExtLaunchKernelGGL((gemm_rows_cu_kernel<DBG, TN>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-  else
-    hipLaunchKernelGGL((gemm_rows_cu_kernel<DBG, TN>), dim3(grid), dim3(768), 0, stream, g);
+  carca_launch(gemm_rows_cu_kernel<DBG, TN>, dim3(grid), dim3(768), 0, stream, true, g);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -2163,26 +1898,34 @@ static int sk_check_error_word() {
 }
 extern "C" int carca_poll_errors(void) { return sk_check_error_word(); }
 
+// What the two stream-K launchers share, called once the product is theirs and before any scratch is taken: an earlier
+// launch's failure is reported here; then the error word, the bound on a taker's wait and the test-only withheld flag go
+// into the kernel's arguments.  1 = no error word to be had (not this kernel's product then).
+static int sk_handover_setup(GemmDev& g) {
+  g.sk_err = carca_kernel_error_word();
+  if (!g_sk_err_host) return 1;
+  if (int rc = sk_check_error_word()) return rc;
+  const int lg = carca_tuning(CARCA_TUNE_SK_SPIN_LOG2);
+  g.sk_spin = 1u << (lg > 0 && lg < 31 ? lg : 23);
+  g.sk_withhold = carca_tuning(CARCA_TUNE_SK_WITHHOLD);
+  return CARCA_OK;
+}
+
 static int launch_gemm_rows_sk(const CarcaGemmDesc* desc, hipStream_t stream, const CarcaGatherArgs* pas, int* rode) {
   const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  if (variant == 15 || variant == 158) return 1;  // (15: never -- A/B switch; 158: 15 + 8)
+  if (variant == CARCA_GV_NO_STREAM_K || variant == CARCA_GV_NO_STREAM_K_NO_PASSENGER) return 1;  // (never -- A/B switch)
   const int ncb = (desc->ncols_out + 95) / 96, nfull = ncb - 1;
   if (ncb < 2 || desc->ncols_out != desc->N) return 1;
   const int rem = desc->N - 96 * nfull, xc = rem - 64;
   if (xc < 1 || xc > 2) return 1;  // (the cheap tile is two MFMA column tiles + 1..2 VALU columns)
   if (desc->colvec || desc->pos || desc->gate_scale != 0.f || desc->add_table) return 1;
-  int rb = 0;
-  GemmDev g{};
-  g.d = *desc;
   for (int s = 0; s < desc->nseg; ++s) {
     const CarcaGemmSeg& sg = desc->seg[s];
     if (sg.add || sg.gate || sg.rowscale || sg.add_pos) return 1;  // (the VALU columns take the plain epilogue only)
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (sg.rows + 383) / 384;
   }
-  g.rb_start[desc->nseg] = rb;
-  g.nrb = rb;
+  GemmDev g{};
+  g.d = *desc;
+  const int rb = carca_fill_row_blocks(g, 384);
   g.ncb = ncb;
   int grid = rb * ncb;
   const int nfast = desc->K0 / 32, ntail = (desc->K0 + 31) / 32 - nfast + (desc->K1 + 31) / 32;
@@ -2198,26 +1941,15 @@ static int launch_gemm_rows_sk(const CarcaGemmDesc* desc, hipStream_t stream, co
   g.sk_don = don;
   // The item-row gather rides as workgroup `grid` on the CU the tiles leave idle (gather_rows_dma: ~100 us; the register
   // version measured ~540 us beside the tiles and was the launch's long pole: 0.640 ms per forward against 0.614).
-  // Tuning variant 19: the gather keeps its own launch (A/B switch).
-  if (pas && grid < carca_num_cus() && pas->d <= 128 && variant != 19 &&
+  // CARCA_GV_OWN_GATHER: the gather keeps its own launch (A/B switch).
+  if (pas && grid < carca_num_cus() && pas->d <= 128 && variant != CARCA_GV_OWN_GATHER &&
       4200.0 * (nfast - don + ntail) >= 1.25 * 20.0 * pas->total_rows) {  // (the tiles outlast the passenger, 20 ns per row, with a margin)
     g.has_pas = 1;
     g.pas = *pas;
     ++grid;
     if (rode) *rode = 1;
   }
-  if (!g_sk_err_host) {
-    if (hipHostMalloc((void**)&g_sk_err_host, sizeof(int), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return 1;
-    *g_sk_err_host = 0;
-    if (hipHostGetDevicePointer((void**)&g_sk_err_dev, g_sk_err_host, 0) != hipSuccess) g_sk_err_dev = nullptr;
-  }
-  if (int rc = sk_check_error_word()) return rc;
-  g.sk_err = g_sk_err_dev;
-  {
-    const int lg = carca_tuning(CARCA_TUNE_SK_SPIN_LOG2);
-    g.sk_spin = 1u << (lg > 0 && lg < 31 ? lg : 23);
-    g.sk_withhold = carca_tuning(CARCA_TUNE_SK_WITHHOLD);
-  }
+  if (int rc = sk_handover_setup(g)) return rc;
   // (a FIXED flag area in front: one buffer serves every shape launched on its stream, and what was cleared when it was
   // allocated must cover the flags of all of them -- one per partial tile, at most one workgroup per CU gives)
   const size_t n_part = (size_t)rb * nfull, flag_bytes = 4096;
@@ -2230,14 +1962,9 @@ static int launch_gemm_rows_sk(const CarcaGemmDesc* desc, hipStream_t stream, co
   g.sk_flag = (int*)buf;
   g.sk_part = (float*)(buf + flag_bytes);
   if (g_rows_log_on) carca_rows_log(xc == 1 ? "gemm_rows_sk_kernel<1>" : "gemm_rows_sk_kernel<2>", desc, grid);
-  hipEvent_t e0, e1;
-  const bool ev = carca_take_launch_events(&e0, &e1);
-  if (xc == 1) {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_sk_kernel<1>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_sk_kernel<1>), dim3(grid), dim3(768), 0, stream, g);
-  } else {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_sk_kernel<2>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_sk_kernel<2>), dim3(grid), dim3(768), 0, stream, g);
+  switch (xc) {
+    case 1: carca_launch(gemm_rows_sk_kernel<1>, dim3(grid), dim3(768), 0, stream, true, g); break;
+    default: carca_launch(gemm_rows_sk_kernel<2>, dim3(grid), dim3(768), 0, stream, true, g); break;
   }
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
@@ -2249,7 +1976,8 @@ static int launch_gemm_rows_sk(const CarcaGemmDesc* desc, hipStream_t stream, co
 static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, const CarcaGatherArgs* pas, int* rode,
                                 bool dedup = false) {
   const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  if (variant == 15 || variant == 158 || variant == 23) return 1;  // (23: gemm_rows_sk_kernel, every row -- A/B switch)
+  if (variant == CARCA_GV_NO_STREAM_K || variant == CARCA_GV_NO_STREAM_K_NO_PASSENGER || variant == CARCA_GV_SK_EVERY_ROW)
+    return 1;  // (A/B switches; the last: gemm_rows_sk_kernel, every row)
   if (!desc->mask_rows) return 1;  // (rows with id 0 may be left out only where the product masks them)
   const int ncb = (desc->ncols_out + 95) / 96, nfull = ncb - 1;
   if (ncb < 2 || desc->ncols_out != desc->N) return 1;
@@ -2270,7 +1998,7 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
   const int nfast = desc->K0 / 32;
   const int ncu = carca_num_cus();
   // (worth a persistent grid: at least most of a round of tiles if every row counted, and K long enough to share)
-  const int min_fast = carca_tuning(19) > 0 ? carca_tuning(19) : SKC_MIN_STEPS;  // (tuning key 19: the bound, A/B)
+  const int min_fast = carca_tuning(CARCA_TUNE_SKC_MIN_STEPS) > 0 ? carca_tuning(CARCA_TUNE_SKC_MIN_STEPS) : SKC_MIN_STEPS;
   if (nfast < min_fast || ((rows + 383) / 384) * ncb < ncu / 2 || ncu > 1024) return 1;
   // (what the kernel's LDS lists hold: 64-row chunks of all segments, and SKC_RB row blocks per workgroup's stretch)
   {
@@ -2289,22 +2017,11 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
   g.skc_cheap = xc == 2 ? 74 : (xc == 1 ? 71 : 68);  // (two MFMA column tiles of three + the VALU columns: 0.74 of a full step measured)
   {
     // owning a row block, in K steps (tuning keys 17 / 18: value - 1, so that 1 switches the correction off; A/B)
-    const int t = carca_tuning(17), tl = carca_tuning(18);
+    const int t = carca_tuning(CARCA_TUNE_SKC_OV_TEAM), tl = carca_tuning(CARCA_TUNE_SKC_OV_LONE);
     g.skc_ov = std::min(SKC_OV_MAX, t > 0 ? t - 1 : SKC_OV_TEAM);
     g.skc_ov_lone = std::min(SKC_OV_MAX, tl > 0 ? tl - 1 : SKC_OV_LONE);
   }
-  if (!g_sk_err_host) {
-    if (hipHostMalloc((void**)&g_sk_err_host, sizeof(int), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return 1;
-    *g_sk_err_host = 0;
-    if (hipHostGetDevicePointer((void**)&g_sk_err_dev, g_sk_err_host, 0) != hipSuccess) g_sk_err_dev = nullptr;
-  }
-  if (int rc = sk_check_error_word()) return rc;
-  g.sk_err = g_sk_err_dev;
-  {
-    const int lg = carca_tuning(CARCA_TUNE_SK_SPIN_LOG2);
-    g.sk_spin = 1u << (lg > 0 && lg < 31 ? lg : 23);
-    g.sk_withhold = carca_tuning(CARCA_TUNE_SK_WITHHOLD);
-  }
+  if (int rc = sk_handover_setup(g)) return rc;
   CarcaDedupRun dd;
   if (dedup) {
     if (int rc = carca_feat_dedup_prepare(desc, stream, &dd)) return rc;
@@ -2327,7 +2044,7 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
   // The gather rides (last workgroup: gather_rows_dma, ~20 ns per row measured beside the tiles: 392 us for C2's 19 k rows)
   // only under a product that lasts well beyond it even with half of its rows left out -- not at C2 (the kernel is ~480 us in
   // evaluation, ~330 us in training; riding measured 0.5653 ms per forward against 0.5637 with the gather's own 7 us launch).
-  if (pas && pas->d <= 128 && variant != 19 && 4200.0 * nfast * 0.5 >= 1.5 * 20.0 * pas->total_rows) {
+  if (pas && pas->d <= 128 && variant != CARCA_GV_OWN_GATHER && 4200.0 * nfast * 0.5 >= 1.5 * 20.0 * pas->total_rows) {
     g.has_pas = 1;
     g.pas = *pas;
     if (rode) *rode = 1;
@@ -2346,37 +2063,27 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
     carca_rows_log(dedup ? (xc == 0 ? "gemm_rows_skc_kernel<0>+dedup" : (xc == 1 ? "gemm_rows_skc_kernel<1>+dedup" : "gemm_rows_skc_kernel<2>+dedup"))
                          : (xc == 0 ? "gemm_rows_skc_kernel<0>" : (xc == 1 ? "gemm_rows_skc_kernel<1>" : "gemm_rows_skc_kernel<2>")),
                    desc, grid);
-  hipEvent_t e0, e1;
-  const bool ev_all = carca_take_launch_events(&e0, &e1);
-  if (dedup)
-    if (int rc = carca_feat_dedup_plan(&dd, stream, ev_all ? e0 : nullptr)) return rc;
-  const bool ev = ev_all && !dedup;
-  if (xc == 0) {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_skc_kernel<0>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_skc_kernel<0>), dim3(grid), dim3(768), 0, stream, g);
-  } else if (xc == 1) {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_skc_kernel<1>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_skc_kernel<1>), dim3(grid), dim3(768), 0, stream, g);
-  } else {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_skc_kernel<2>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_skc_kernel<2>), dim3(grid), dim3(768), 0, stream, g);
+  // dedup: the pair of timing events is taken here, once -- its start goes to the plan launch, its stop to the expand launch,
+  // and the product between them is not timed on its own
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (dedup) {
+    if (!carca_take_launch_events(&e0, &e1)) e0 = e1 = nullptr;
+    if (int rc = carca_feat_dedup_plan(&dd, stream, e0)) return rc;
+  }
+  switch (xc) {
+    case 0: carca_launch(gemm_rows_skc_kernel<0>, dim3(grid), dim3(768), 0, stream, !dedup, g); break;
+    case 1: carca_launch(gemm_rows_skc_kernel<1>, dim3(grid), dim3(768), 0, stream, !dedup, g); break;
+    default: carca_launch(gemm_rows_skc_kernel<2>, dim3(grid), dim3(768), 0, stream, !dedup, g); break;
   }
   CARCA_LAUNCH_CHECK();
-  if (dedup) return carca_feat_dedup_expand(&dd, stream, ev_all ? e1 : nullptr);
+  if (dedup) return carca_feat_dedup_expand(&dd, stream, e1);
   return CARCA_OK;
 }
 
 static int launch_gemm_rows_n96(const CarcaGemmDesc* desc, hipStream_t stream) {
   GemmDev g{};
   g.d = *desc;
-  int rb = 0;
-  for (int s = 0; s < desc->nseg; ++s) {
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (desc->seg[s].rows + n96::BM - 1) / n96::BM;
-  }
-  g.rb_start[desc->nseg] = rb;
-  g.nrb = rb;
+  const int rb = carca_fill_row_blocks(g, n96::BM);
   g.ncb = 1;
   g.diag = carca_tuning(CARCA_TUNE_DIAG);
   constexpr size_t lds_bytes = sizeof(float) * 2 * (n96::A_BUF + n96::B_BUF);
@@ -2390,11 +2097,7 @@ static int launch_gemm_rows_n96(const CarcaGemmDesc* desc, hipStream_t stream) {
     attr_set = true;
   }
   if (g_rows_log_on) carca_rows_log("gemm_rows_n96_kernel", desc, rb);
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))
-    hipExtLaunchKernelGGL(gemm_rows_n96_kernel, dim3(rb), dim3(768), lds_bytes, stream, e0, e1, 0, g);
-  else
-    hipLaunchKernelGGL(gemm_rows_n96_kernel, dim3(rb), dim3(768), lds_bytes, stream, g);
+  carca_launch(gemm_rows_n96_kernel, dim3(rb), dim3(768), lds_bytes, stream, true, g);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -2424,7 +2127,7 @@ static int gemm_rows_choose(const CarcaGemmDesc* desc, GemmChoice* choice, bool*
   // Narrow outputs (the joint embedding, every d-wide product of the backward pass) give too few 128 x 96 blocks
   // to fill 256 CUs and leave one long MFMA chain per wave: 32-column blocks triple the wave count instead
   // (the A tile is re-read from L2 by the three column blocks of a row block, which share an XCD).
-  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);  // 0 auto, 1 force 128x96, 2 force one-block-per-CU, 3 = 2 + stamps, 4 = no buffer loads
+  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);  // (CARCA_GV_*, carca_common.h)
   // do all operand offsets fit 32 bits of bytes?  (buffer loads; the gather table's size is only known when stated)
   const uint64_t lim = 1ull << 30;  // elements
   bool fits = (uint64_t)(desc->N - 1) * desc->ldb0 + desc->K0 < lim &&
@@ -2443,19 +2146,20 @@ static int gemm_rows_choose(const CarcaGemmDesc* desc, GemmChoice* choice, bool*
     fits = last0 + desc->K0 < lim && last1 + desc->K1 < lim;
     rb384 += (sg.rows + 383) / 384;
   }
-  if (variant == 4) fits = false;
+  if (variant == CARCA_GV_NO_BUFFER_LOADS) fits = false;
   if (fits_out) *fits_out = fits;
-  const bool narrow = variant != 1 && rb128 * ((desc->ncols_out + 95) / 96) < 384;
+  const bool narrow = variant != CARCA_GV_TILED && rb128 * ((desc->ncols_out + 95) / 96) < 384;
   if (narrow) {
     *choice = fits ? GEMM_NARROW_BUF : GEMM_NARROW;
-    if (fits && (variant == 9 || variant == 10)) *choice = variant == 9 ? GEMM_WIDE64 : GEMM_WIDE64_PF2;
+    if (fits && (variant == CARCA_GV_WIDE64 || variant == CARCA_GV_WIDE64_PF2))
+      *choice = variant == CARCA_GV_WIDE64 ? GEMM_WIDE64 : GEMM_WIDE64_PF2;
     // one 80 x 96 block per CU: narrow output over ONE k-source with a K worth pipelining, rows that fill the chip in about
-    // one round, every operand row 16-byte aligned (variant 11 forces it where it applies, 12 forbids it)
+    // one round, every operand row 16-byte aligned (CARCA_GV_N96 forces it where it applies, CARCA_GV_NO_N96 forbids it)
     // (a product with a gathered addend -- the joint embedding over q's columns, K0 = g = 450 at C2 -- comes with rows
     // that are only 8-byte aligned and a K that is no multiple of 4: the kernel's loads take any dword alignment and its
     // last stage shifts / masks by element; everybody else keeps the 16-byte conditions the kernel was measured under)
     const bool loose = desc->add_table != nullptr && desc->K0 >= 4;
-    if (fits && variant != 12 && desc->K1 == 0 && desc->N > 64 && desc->ncols_out <= 96 &&
+    if (fits && variant != CARCA_GV_NO_N96 && desc->K1 == 0 && desc->N > 64 && desc->ncols_out <= 96 &&
         (loose || (desc->K0 % 4 == 0 && desc->lda0 % 4 == 0 && desc->ldb0 % 4 == 0 && ((uintptr_t)desc->bt0 & 15) == 0))) {
       bool ok = true;
       int rb80 = 0;
@@ -2465,13 +2169,14 @@ static int gemm_rows_choose(const CarcaGemmDesc* desc, GemmChoice* choice, bool*
         rb80 += (sg.rows + n96::BM - 1) / n96::BM;
       }
       const int cus = carca_num_cus();
-      if (ok && (variant == 11 || (variant == 0 && desc->K0 >= 256 && rb80 > cus / 2 && rb80 <= cus))) *choice = GEMM_N96;
+      if (ok && (variant == CARCA_GV_N96 || (variant == CARCA_GV_AUTO && desc->K0 >= 256 && rb80 > cus / 2 && rb80 <= cus)))
+        *choice = GEMM_N96;
     }
     return CARCA_OK;
   }
   // One 384 x 96 block per CU when the grid fills the chip's 256 CUs about as well as the 128 x 96 blocks (3 per CU)
   // would: compare rounds x tiles per block.
-  if (fits && desc->K0 >= 64 && variant != 1) {
+  if (fits && desc->K0 >= 64 && variant != CARCA_GV_TILED) {
     const int ncb = (desc->ncols_out + 95) / 96, ncb128 = (desc->ncols_out + 127) / 128;
     const long units_cu = (long)((rb384 * ncb + 255) / 256) * 36, units_3 = (long)((rb128 * ncb + 255) / 256) * 12;
     const long units_cu128 = (long)((rb384 * ncb128 + 255) / 256) * 48;  // 384 x 128 tiles: 48 32x32 tiles per block
@@ -2479,11 +2184,12 @@ static int gemm_rows_choose(const CarcaGemmDesc* desc, GemmChoice* choice, bool*
     // MFMA peak on the feature GEMM -- so a round-up that costs it a few per cent more units is still a win: n_attrs =
     // 512, N = 1001, B = 512 gives 1008 against 996 units and ran 141.7 k users/s tiled between 148 k at B = 256 and
     // 157 k at B = 1024, both one-block-per-CU)
-    if (variant == 3 || variant == 2 || (units_cu * 10 <= units_3 * 11 && units_cu <= units_cu128)) {
-      *choice = variant == 3 ? GEMM_CU_STAMPS : GEMM_CU;
+    if (variant == CARCA_GV_PER_CU_STAMPS || variant == CARCA_GV_PER_CU ||
+        (units_cu * 10 <= units_3 * 11 && units_cu <= units_cu128)) {
+      *choice = variant == CARCA_GV_PER_CU_STAMPS ? GEMM_CU_STAMPS : GEMM_CU;
       return CARCA_OK;
     }
-    if (variant == 7 || (variant == 0 && units_cu128 < units_cu && units_cu128 * 10 <= units_3 * 11)) {  // (7: force 384 x 128)
+    if (variant == CARCA_GV_PER_CU_128 || (variant == CARCA_GV_AUTO && units_cu128 < units_cu && units_cu128 * 10 <= units_3 * 11)) {
       *choice = GEMM_CU128;
       return CARCA_OK;
     }
@@ -2492,41 +2198,54 @@ static int gemm_rows_choose(const CarcaGemmDesc* desc, GemmChoice* choice, bool*
   return CARCA_OK;
 }
 
-extern "C" int carca_gemm_rows(const CarcaGemmDesc* desc, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// The one route of a row product, behind all three entry points: choose, then try the kernels in order (1 = not mine).
+//   ga / rode   the passenger entry: the item-row gather may ride in the launch (*rode tells whether it did)
+//   dedup       the evaluation entry: first the product over one representative per group of equal attribute rows
+// Where the entry points differed before they shared this function, they still do; each difference is a commented
+// condition below.  Whether they are intended is open.
+static int gemm_rows_dispatch(const CarcaGemmDesc* desc, hipStream_t stream, const CarcaGatherArgs* ga, int* rode, bool dedup) {
   GemmChoice c;
   bool fits = false;
   if (int rc = gemm_rows_choose(desc, &c, &fits)) return rc;
-  if (desc->N <= 96) {  // (a narrow output over many rows per CU: gemm_stream.hip)
-    const int rc = carca_gemm_rows_n96s_try(desc, fits, stream);
+  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
+  const bool passenger = rode != nullptr, per_cu = c == GEMM_CU || c == GEMM_CU128;
+  if (variant == CARCA_GV_NO_PASSENGER || variant == CARCA_GV_NO_STREAM_K_NO_PASSENGER) ga = nullptr;  // (A/B switch)
+  // (tuning key 20 = 1 switches the dedup off; deterministic mode and the split-precision kernel keep their own paths)
+  if (dedup && per_cu && carca_tuning(CARCA_TUNE_FEAT_DEDUP) != 1 && carca_tuning(CARCA_TUNE_DETERMINISTIC) == 0 &&
+      carca_tuning(CARCA_TUNE_SPLIT_GEMM) == 0) {
+    const int rc = launch_gemm_rows_skc(desc, stream, nullptr, nullptr, true);
     if (rc != 1) return rc;
   }
-  if ((carca_tuning(CARCA_TUNE_SPLIT_GEMM) & 16) && fits && c != GEMM_CU) {
-    // (key 16, bit 4: the split-precision kernel wherever its own conditions hold, whatever the grid -- how the fixture-sized
-    // parity tests reach it)
-    const int rc = carca_gemm_rows_split_try(desc, stream);
-    if (rc != 1) return rc;
+  // passenger + GEMM_CU / GEMM_CU128: n96s and the forced split are not tried (as before; whether intended is open)
+  if (!(passenger && per_cu)) {
+    if (desc->N <= 96) {  // (a narrow output over many rows per CU: gemm_stream.hip)
+      const int rc = carca_gemm_rows_n96s_try(desc, fits, stream);
+      if (rc != 1) return rc;
+    }
+    if ((carca_tuning(CARCA_TUNE_SPLIT_GEMM) & 16) && fits && c != GEMM_CU) {
+      // (key 16, bit 4: the split-precision kernel wherever its own conditions hold, whatever the grid -- how the fixture-sized
+      // parity tests reach it)
+      const int rc = carca_gemm_rows_split_try(desc, stream);
+      if (rc != 1) return rc;
+    }
   }
   switch (c) {
     case GEMM_NARROW_BUF: return launch_gemm_rows<128, 32, 32, 4, true>(desc, stream);
     case GEMM_NARROW: return launch_gemm_rows<128, 32, 32, 4>(desc, stream);
-    case GEMM_CU: {
-      int rc = carca_gemm_rows_split_try(desc, stream);  // (opt-in, tuning key 16; 1 = not asked for / not its product)
-      if (rc != 1) return rc;
-      rc = launch_gemm_rows_skc(desc, stream, nullptr, nullptr);
-      if (rc != 1) return rc;
-      rc = launch_gemm_rows_sk(desc, stream, nullptr, nullptr);
-      if (rc != 1) return rc;
-      rc = carca_gemm_rows_stream_try(desc, fits, stream);  // (short K, many tiles per CU: gemm_stream.hip)
-      return rc == 1 ? launch_gemm_rows_cu<0>(desc, stream) : rc;
+    case GEMM_CU:
+    case GEMM_CU128: {  // (384 x 128 tiles fill one round where 96-wide ones would not -- unless the rows with id 0 can go)
+      const bool wide = c == GEMM_CU128;
+      // (the gather keeps its own launch beside the split-precision and the streaming kernel: rode stays 0)
+      int rc = 1;
+      // GEMM_CU128: the opt-in split-precision kernel (tuning key 16) and gemm_rows_sk_kernel are not tried (as before)
+      if (!wide) rc = carca_gemm_rows_split_try(desc, stream);
+      if (rc == 1) rc = launch_gemm_rows_skc(desc, stream, ga, rode);
+      if (rc == 1 && !wide) rc = launch_gemm_rows_sk(desc, stream, ga, rode);
+      if (rc == 1) rc = carca_gemm_rows_stream_try(desc, fits, stream);  // (short K, many tiles per CU: gemm_stream.hip)
+      if (rc == 1) rc = wide ? launch_gemm_rows_cu<0, 4>(desc, stream, ga, rode) : launch_gemm_rows_cu<0, 3>(desc, stream, ga, rode);
+      return rc;
     }
     case GEMM_CU_STAMPS: return launch_gemm_rows_cu<1>(desc, stream);
-    case GEMM_CU128: {  // (384 x 128 tiles fill one round where 96-wide ones would not -- unless the rows with id 0 can go)
-      int rc = launch_gemm_rows_skc(desc, stream, nullptr, nullptr);
-      if (rc != 1) return rc;
-      rc = carca_gemm_rows_stream_try(desc, fits, stream);
-      return rc == 1 ? launch_gemm_rows_cu<0, 4>(desc, stream) : rc;
-    }
     case GEMM_WIDE64: return launch_gemm_rows<64, 96, 32, 4, true>(desc, stream);
     case GEMM_WIDE64_PF2: return launch_gemm_rows<64, 96, 32, 2, true>(desc, stream);
     case GEMM_N96: return launch_gemm_rows_n96(desc, stream);
@@ -2535,46 +2254,19 @@ extern "C" int carca_gemm_rows(const CarcaGemmDesc* desc, void* stream_) {
   }
 }
 
+extern "C" int carca_gemm_rows(const CarcaGemmDesc* desc, void* stream_) {
+  return gemm_rows_dispatch(desc, (hipStream_t)stream_, nullptr, nullptr, false);
+}
+
 // The feature product of an EVALUATION forward (no gradient): over one representative row per group of equal attribute
-// rows where it runs on gemm_rows_skc_kernel (feat_dedup.hip), else carca_gemm_rows.  Tuning key 20 = 1 switches it off;
-// deterministic mode and the split-precision kernel keep their own paths.
+// rows where it runs on gemm_rows_skc_kernel (feat_dedup.hip), else as carca_gemm_rows.
 int carca_gemm_rows_feat_dedup(const CarcaGemmDesc* desc, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GemmChoice c;
-  bool fits = false;
-  if (int rc = gemm_rows_choose(desc, &c, &fits)) return rc;
-  if ((c == GEMM_CU || c == GEMM_CU128) && carca_tuning(CARCA_TUNE_FEAT_DEDUP) != 1 &&
-      carca_tuning(CARCA_TUNE_DETERMINISTIC) == 0 && carca_tuning(CARCA_TUNE_SPLIT_GEMM) == 0) {
-    const int rc = launch_gemm_rows_skc(desc, stream, nullptr, nullptr, true);
-    if (rc != 1) return rc;
-  }
-  return carca_gemm_rows(desc, stream_);
+  return gemm_rows_dispatch(desc, (hipStream_t)stream_, nullptr, nullptr, true);
 }
 
 int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* ga, int* rode, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   *rode = 0;
-  GemmChoice c;
-  bool fits = false;
-  if (int rc = gemm_rows_choose(desc, &c, &fits)) return rc;
-  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 8 || carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 158) ga = nullptr;  // (8: never let the gather ride -- A/B switch)
-  if (c == GEMM_CU) {
-    int rc = carca_gemm_rows_split_try(desc, stream);  // (the gather keeps its own launch beside this kernel: rode stays 0)
-    if (rc != 1) return rc;
-    rc = launch_gemm_rows_skc(desc, stream, ga, rode);
-    if (rc != 1) return rc;
-    rc = launch_gemm_rows_sk(desc, stream, ga, rode);
-    if (rc != 1) return rc;
-    rc = carca_gemm_rows_stream_try(desc, fits, stream);  // (the gather keeps its own launch beside it: rode stays 0)
-    return rc == 1 ? launch_gemm_rows_cu<0, 3>(desc, stream, ga, rode) : rc;
-  }
-  if (c == GEMM_CU128) {
-    int rc = launch_gemm_rows_skc(desc, stream, ga, rode);
-    if (rc != 1) return rc;
-    rc = carca_gemm_rows_stream_try(desc, fits, stream);
-    return rc == 1 ? launch_gemm_rows_cu<0, 4>(desc, stream, ga, rode) : rc;
-  }
-  return carca_gemm_rows(desc, stream_);
+  return gemm_rows_dispatch(desc, (hipStream_t)stream_, ga, rode, false);
 }
 
 // n independent products; those that select the narrow buffer-load kernel share launches (GEMM_GROUP_MAX per launch),
@@ -2601,21 +2293,14 @@ extern "C" int carca_gemm_rows_group(const CarcaGemmDesc* descs, int n, void* st
   for (int i = 0; i < n; ++i) {
     GemmChoice c;
     if (int rc = gemm_rows_choose(&descs[i], &c)) return rc;
-    if (c != GEMM_NARROW_BUF || carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 6) {  // (variant 6: never group -- A/B switch)
+    if (c != GEMM_NARROW_BUF || carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_NO_GROUP) {  // (A/B switch)
       if (int rc = carca_gemm_rows(&descs[i], stream_)) return rc;
       continue;
     }
     GemmDev& g = grp.g[grp.n];
     g = GemmDev{};
     g.d = descs[i];
-    int rb = 0;
-    for (int s = 0; s < descs[i].nseg; ++s) {
-      if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-      g.rb_start[s] = rb;
-      rb += (descs[i].seg[s].rows + BM - 1) / BM;
-    }
-    g.rb_start[descs[i].nseg] = rb;
-    g.nrb = rb;
+    const int rb = carca_fill_row_blocks(g, BM);
     g.ncb = (descs[i].ncols_out + BN - 1) / BN;
     grp.block_start[grp.n] = blocks;
     blocks += rb * g.ncb;
@@ -2623,212 +2308,4 @@ extern "C" int carca_gemm_rows_group(const CarcaGemmDesc* descs, int n, void* st
       if (int rc = flush()) return rc;
   }
   return flush();
-}
-
-int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream);  // wgrad_cu.hip
-
-static int wgrad_check(const CarcaWgradDesc* desc) {
-  CARCA_CHECK_ARG(desc && desc->nseg >= 1 && desc->nseg <= CARCA_MAX_SEGS, "gemm_wgrad: bad segment count");
-  CARCA_CHECK_ARG(desc->dw && desc->N >= 1 && desc->K >= 1 && desc->K1 >= 0 && desc->ldw >= desc->K + desc->K1 &&
-                      desc->ld_dy >= desc->N && desc->ld_x >= desc->K && (desc->K1 == 0 || desc->ld_x1 >= desc->K1),
-                  "gemm_wgrad: bad geometry");
-  for (int s = 0; s < desc->nseg; ++s) {
-    const CarcaWgradSeg& sg = desc->seg[s];
-    CARCA_CHECK_ARG(sg.rows >= 1 && sg.dy && sg.x && !(desc->mask_rows && !sg.ids) && (desc->K1 == 0 || sg.x1),
-                    "gemm_wgrad: segment %d malformed", s);
-    CARCA_CHECK_ARG(sg.T >= 1 || (!sg.x_bstride && !sg.x1_bstride), "gemm_wgrad: segment %d needs T >= 1", s);
-    CARCA_CHECK_ARG(!(sg.x_gather && !sg.ids), "gemm_wgrad: segment %d gathers without ids", s);
-  }
-  return CARCA_OK;
-}
-
-// tiling / row splits of the tiled kernel for one product; returns the grid size; *fits: buffer loads are safe
-static int wgrad_prepare(const CarcaWgradDesc* desc, WgradDev& g, bool* fits_out, int slot_budget = 0) {
-  constexpr int BNO = 96, BKO = 128, BR = 32;
-  g = WgradDev{};
-  g.d = *desc;
-  int chunks = 0;
-  for (int s = 0; s < desc->nseg; ++s) {
-    const CarcaWgradSeg& sg = desc->seg[s];
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.chunk_start[s] = chunks;
-    chunks += (sg.rows + BR - 1) / BR;
-  }
-  g.chunk_start[desc->nseg] = chunks;
-  g.nnb = (desc->N + BNO - 1) / BNO;
-  g.nkb0 = (desc->K + BKO - 1) / BKO;
-  g.nkb = g.nkb0 + (desc->K1 + BKO - 1) / BKO;
-  // row splits: fill the chip's 4 x 256 resident slots in ONE round (119 registers -> 4 blocks per CU;
-  // measured at C2: 512 slots 1017 us, 768 972, 1024 809, 1536 865), but keep >= 2 chunks (64 rows) per split
-  const int tiles = g.nnb * g.nkb;
-  // Products of a few tiles (joint embedding: 5) pay for every split with a full tile of atomics: 384 slots there
-  // (N = 90, K = 540, 19328 rows: 1024 slots 74.5 us, 768 65.8, 640 61.6, 512 59.6, 384 57.5, 256 67.6)
-  const int slots = slot_budget > 0 ? slot_budget
-                    : carca_tuning(CARCA_TUNE_WGRAD_SLOTS) > 0 ? carca_tuning(CARCA_TUNE_WGRAD_SLOTS)
-                    : tiles >= 64 ? 1024 : 640;  // (640 since the splits end in plain stores: 384 / 512 / 640 / 768 / 1024 -> train
-                                                 // step 1.749 / 1.743 / 1.737 / 1.740 / 1.736 ms, tools/ab_train.py "2=...")
-  int nsplit = tiles >= slots ? 1 : slots / tiles;
-  const int min_chunks = carca_tuning(4) > 0 ? carca_tuning(4) : 2;  // (measured on the d x d products: 4 -> 21 us, 2 -> 18 us, 1 -> 23 us)
-  nsplit = max(1, min(nsplit, (chunks + min_chunks - 1) / min_chunks));
-  g.diag_plain_store = carca_tuning(3);
-  g.chunks_per_split = (chunks + nsplit - 1) / nsplit;
-  g.nsplit = (chunks + g.chunks_per_split - 1) / g.chunks_per_split;
-  // buffer loads when every operand offset provably fits 32 bits of bytes (a gather table's size must be stated)
-  const uint64_t lim = 1ull << 30;
-  bool fits = carca_tuning(CARCA_TUNE_GEMM_VARIANT) != 4;
-  for (int s = 0; s < desc->nseg && fits; ++s) {
-    const CarcaWgradSeg& sg = desc->seg[s];
-    const int T = sg.T >= 1 ? sg.T : 1;
-    const uint64_t ub = (uint64_t)((sg.rows - 1) / T), ut = (uint64_t)(T - 1);
-    const uint64_t lx = sg.x_gather ? (sg.x_gather > 1 ? (uint64_t)(sg.x_gather - 1) * desc->ld_x : lim)
-                        : sg.x_bstride ? ub * sg.x_bstride + ut * desc->ld_x
-                                       : (uint64_t)(sg.rows - 1) * desc->ld_x;
-    const uint64_t lx1 = desc->K1 == 0 ? 0
-                         : sg.x1_bstride ? ub * sg.x1_bstride + ut * desc->ld_x1
-                                         : (uint64_t)(sg.rows - 1) * desc->ld_x1;
-    fits = lx + desc->K < lim && lx1 + desc->K1 < lim && (uint64_t)sg.rows * desc->ld_dy < lim;
-  }
-  *fits_out = fits;
-  return tiles * g.nsplit;
-}
-
-// Partial tiles of the row splits (WgradDev.part): stream scratch (carca_common.h) -- the product's kernel writes them, its
-// reduce launch reads them, the next product on the stream is ordered behind both; inside a hipGraph capture the capture
-// gets storage of its own.  Tuning variant 19 = atomics (A/B).
-namespace {
-float* wpart_take(size_t floats, hipStream_t stream) {
-  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 19 || carca_tuning(3) != 0) return nullptr;
-  if (carca_stream_capturing(stream)) return (float*)carca_capture_alloc(stream, floats * sizeof(float), false, nullptr);
-  return (float*)carca_stream_scratch(stream, CARCA_SCRATCH_WPART, floats * sizeof(float));
-}
-}  // namespace
-
-extern "C" int carca_gemm_wgrad(const CarcaWgradDesc* desc, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (int rc = wgrad_check(desc)) return rc;
-  // the big product (dW of feats_embed) goes to the persistent one-block-per-CU kernel; tuning variant 4 / 5 = never
-  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  if (variant != 4 && variant != 5) {
-    const int r = carca_wgrad_cu_try(desc, stream);
-    if (r != 1) return r;
-  }
-  constexpr int BNO = 96, BKO = 128, BR = 32;
-  WgradDev g;
-  bool fits = false;
-  const int grid = wgrad_prepare(desc, g, &fits);
-  const int tiles = g.nnb * g.nkb;
-  if (g.nsplit > 1) g.part = wpart_take((size_t)g.nsplit * tiles * BNO * BKO, stream);  // (one split: nothing to combine)
-  if (fits)
-    hipLaunchKernelGGL((gemm_wgrad_kernel<BNO, BKO, BR, true>), dim3(grid), dim3(256), 0, stream, g);
-  else
-    hipLaunchKernelGGL((gemm_wgrad_kernel<BNO, BKO, BR>), dim3(grid), dim3(256), 0, stream, g);
-  if (g.part) hipLaunchKernelGGL(wgrad_part_reduce_kernel, dim3(tiles * 12), dim3(256), 0, stream, g);
-  CARCA_LAUNCH_CHECK();
-  return CARCA_OK;
-}
-
-// Grouped launch: the kernel reads its descriptors from pinned, device-mapped host memory that THIS thread writes, so a
-// slot may only be rewritten once the launch that reads it has finished: every slot carries an event recorded behind its
-// launch, and a launch takes the first slot whose event has completed (hipEventQuery -- the host never waits; while none
-// has, the pool grows: its size follows the number of launches in flight).  Products that are big enough for the
-// persistent kernel, or whose offsets do not fit the buffer-load path, are issued one by one instead.
-namespace {
-struct GroupSlot {
-  WgradDev* host;  // [WGRAD_GROUP_MAX] pinned, mapped into the device's address space (no copy command: a small async H2D
-  WgradDev* dev;   // copy turned out to stall the issuing thread until the stream had drained)
-  hipEvent_t ev;
-  bool used;
-};
-std::vector<GroupSlot> g_group_slots;
-int group_slot_take() {
-  int found = -1;
-  for (size_t i = 0; i < g_group_slots.size() && found < 0; ++i)
-    if (!g_group_slots[i].used || hipEventQuery(g_group_slots[i].ev) == hipSuccess) found = (int)i;
-  (void)hipGetLastError();  // (a query of a pending event leaves hipErrorNotReady behind: not the next launch's error)
-  if (found >= 0) return found;
-  GroupSlot sl{};
-  if (hipHostMalloc((void**)&sl.host, sizeof(WgradDev) * WGRAD_GROUP_MAX, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&sl.dev, sl.host, 0) != hipSuccess ||
-      hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) != hipSuccess)
-    return -1;
-  g_group_slots.push_back(sl);
-  return (int)g_group_slots.size() - 1;
-}
-}  // namespace
-
-extern "C" int carca_gemm_wgrad_group(const CarcaWgradDesc* descs, int n, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  CARCA_CHECK_ARG(descs && n >= 1, "gemm_wgrad_group: no products");
-  for (int i = 0; i < n; ++i)
-    if (int rc = wgrad_check(&descs[i])) return rc;
-  constexpr int BNO = 96, BKO = 128, BR = 32;
-  const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  int done = 0;
-  const bool capturing = carca_stream_capturing(stream);  // (hipGraph capture: storage of its own, see carca_common.h)
-  while (done < n) {
-    int slot = -1;
-    WgradDev *host, *dev;
-    if (capturing) {
-      host = (WgradDev*)carca_capture_alloc(stream, sizeof(WgradDev) * WGRAD_GROUP_MAX, true, (void**)&dev);
-      if (!host) return CARCA_ERR_BADARG;
-    } else {
-      slot = group_slot_take();
-      if (slot < 0) {
-        carca_set_error("gemm_wgrad_group: cannot allocate a descriptor slot");
-        return CARCA_ERR_BADARG;
-      }
-      host = g_group_slots[slot].host;
-      dev = g_group_slots[slot].dev;
-    }
-    WgradGroupIndex idx{}, ridx{};
-    int blocks = 0, rblocks = 0;
-    size_t part_floats = 0;
-    while (done < n && idx.n < WGRAD_GROUP_MAX) {
-      bool fits = false;
-      WgradDev g;
-      // row-split budget per product (tuning key 5; 0 = the single-product default).  A/B at C2, interleaved in one
-      // process (tools/ab_train.py): ungrouped 2.341 ms/step, grouped 2.229, grouped with 64 / 85 / 128 slots per
-      // product 2.223 / 2.263 / 2.220 -- the budget does not matter, the single launch does
-      // Second look with the kernel trace (tools/train_trace.sh, 13 products of a C2 backward pass in one launch):
-      // 1024 slots per product (100 two-chunk splits each) 105 us, 64 -> 72 us, 48 -> 73, 40 -> 76, 32 -> 76, 24 -> 92,
-      // 16 -> 108: every split ends with a 96 x 128 tile of atomics, so fewer, longer splits win until the chip runs dry
-      // (with partial tiles instead of atomics: 32 -> 1.766 ms per train step, 64 -> 1.744, 96 -> 1.742, 128 -> 1.752)
-      const int budget = carca_tuning(5) > 0 ? carca_tuning(5) : 96;
-      const int grid = wgrad_prepare(&descs[done], g, &fits, budget);
-      const bool big = (long)descs[done].N * (descs[done].K + descs[done].K1) > 96 * 1024;  // single-product path decides
-      if (!fits || big || variant == 6) {  // (variant 6: never group -- A/B switch)
-        if (int rc = carca_gemm_wgrad(&descs[done], stream_)) return rc;
-        ++done;
-        continue;
-      }
-      host[idx.n] = g;
-      idx.block_start[idx.n] = blocks;
-      ridx.block_start[idx.n] = rblocks;
-      blocks += grid;
-      rblocks += g.nnb * g.nkb * 12;
-      part_floats += (size_t)g.nsplit * g.nnb * g.nkb * BNO * BKO;
-      ++idx.n;
-      ++done;
-    }
-    if (idx.n == 0) continue;
-    idx.block_start[idx.n] = blocks;
-    ridx.n = idx.n;
-    ridx.block_start[idx.n] = rblocks;
-    float* part = wpart_take(part_floats, stream);
-    if (part) {  // every product its own stretch of the slot
-      size_t at = 0;
-      for (int i = 0; i < idx.n; ++i) {
-        host[i].part = part + at;
-        at += (size_t)host[i].nsplit * host[i].nnb * host[i].nkb * BNO * BKO;
-      }
-    }
-    hipLaunchKernelGGL((gemm_wgrad_group_kernel<BNO, BKO, BR>), dim3(blocks), dim3(256), 0, stream, dev, idx);
-    if (part) hipLaunchKernelGGL(wgrad_part_reduce_group_kernel, dim3(rblocks), dim3(256), 0, stream, dev, ridx);
-    if (slot >= 0) {
-      (void)hipEventRecord(g_group_slots[slot].ev, stream);
-      g_group_slots[slot].used = true;
-    }
-    CARCA_LAUNCH_CHECK();
-  }
-  return CARCA_OK;
 }

@@ -24,7 +24,7 @@
 // behind the fragment read, once per (32 rows x 16 k), reused over its three column tiles.  W_f is split ONCE per weight
 // version into packed planes (carca_split_pack) laid out in the order a workgroup stages them.
 #include <hip/hip_ext.h>
-#include "carca_common.h"
+#include "gemm_host.h"
 #include "../../include/carca_hip.h"
 #include <type_traits>
 
@@ -647,14 +647,7 @@ int carca_gemm_rows_split_try(const CarcaGemmDesc* desc, hipStream_t stream) {
     if (desc->seg[s].add || desc->seg[s].gate || desc->seg[s].rowscale || desc->seg[s].add_pos) return 1;
   SplitDev g{};
   g.d = *desc;
-  int rb = 0;
-  for (int s = 0; s < desc->nseg; ++s) {
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (desc->seg[s].rows + SP_BM - 1) / SP_BM;
-  }
-  g.rb_start[desc->nseg] = rb;
-  g.nrb = rb;
+  const int rb = carca_fill_row_blocks(g, SP_BM);
   g.ncb = (desc->ncols_out + SP_BN - 1) / SP_BN;
   if (desc->ncols_out != desc->N && (desc->ncols_out + SP_BN - 1) / SP_BN != (desc->N + SP_BN - 1) / SP_BN) return 1;
   const SplitBinding& b = g_split_bound;
@@ -673,20 +666,15 @@ int carca_gemm_rows_split_try(const CarcaGemmDesc* desc, hipStream_t stream) {
   g.header = (const float*)packed;
   g.wp = (const uint16_t*)(packed + SP_HEADER);
   const int grid = rb * g.ncb;
-  hipEvent_t e0, e1;
-  const bool ev = carca_take_launch_events(&e0, &e1);
   // the LDS-DMA kernel where every row of k-source 0 is whole 16-byte groups at 16-byte addresses and K0 whole K steps;
-  // tuning variant 21 = the register-staged kernel everywhere (A/B)
+  // CARCA_GV_SPLIT_NO_DMA = the register-staged kernel everywhere (A/B)
   const int diag = carca_tuning(CARCA_TUNE_DIAG);
-  bool dma = desc->K0 % SP_BK == 0 && desc->lda0 % 4 == 0 && carca_tuning(CARCA_TUNE_GEMM_VARIANT) != 21;
+  bool dma = desc->K0 % SP_BK == 0 && desc->lda0 % 4 == 0 && carca_tuning(CARCA_TUNE_GEMM_VARIANT) != CARCA_GV_SPLIT_NO_DMA;
   for (int s = 0; s < desc->nseg && dma; ++s)
     dma = ((uintptr_t)desc->seg[s].a0 & 15) == 0 && desc->seg[s].a0_bstride % 4 == 0;
   carca_rows_log(dma ? (mode == 1 ? "gemm_rows_split_dma_kernel<bf16x3>" : "gemm_rows_split_dma_kernel<fp16x2>")
                      : (mode == 1 ? "gemm_rows_split_kernel<bf16x3>" : "gemm_rows_split_kernel<fp16x2>"), desc, grid);
-  auto launch = [&](auto kernel) {
-    if (ev) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(768), 0, stream, g);
-  };
+  auto launch = [&](auto kernel) { carca_launch(kernel, dim3(grid), dim3(768), 0, stream, true, g); };
 #define SPLIT_CASE(D_)                                                                                          \
   case D_:                                                                                                      \
     if (dma) mode == 1 ? launch(gemm_rows_split_dma_kernel<1, D_>) : launch(gemm_rows_split_dma_kernel<2, D_>); \

@@ -21,7 +21,7 @@
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <type_traits>
-#include "carca_common.h"
+#include "gemm_host.h"
 #include "../../include/carca_hip.h"
 
 namespace {
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(768) void gemm_rows_cus_kernel(const StreamDev args
 // CARCA_OK = launched; 1 = not this kernel's product (the caller goes on to gemm_rows_cu_kernel)
 int carca_gemm_rows_stream_try(const CarcaGemmDesc* desc, bool fits32, hipStream_t stream) {
   const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  if (variant == 24 || !fits32) return 1;  // (24: never -- A/B switch)
+  if (variant == CARCA_GV_NO_CUS || !fits32) return 1;  // (never -- A/B switch)
   if (desc->K0 % 64 != 0 || desc->K0 < 128) return 1;  // (an even number of K steps, at least four)
   if (desc->K1 < 4 || desc->K1 > 8 || !desc->bt1) return 1;  // (the context item: one 8-k group, two 16-byte groups per row)
   if (desc->ncols_out != desc->N || desc->N <= 96) return 1;
@@ -372,28 +372,23 @@ int carca_gemm_rows_stream_try(const CarcaGemmDesc* desc, bool fits32, hipStream
   const int xc = rem == 96 ? 0 : (rem > 64 ? rem - 64 : 0);
   if (rem != 96 && (rem <= 32 || xc > 2)) return 1;
   const int nfull = rem == 96 ? ncb : ncb - 1;
-  StreamDev g{};
-  g.d = *desc;
-  int rb = 0;
   for (int s = 0; s < desc->nseg; ++s) {
     const CarcaGemmSeg& sg = desc->seg[s];
     if (sg.add || sg.gate || sg.rowscale || sg.add_pos || sg.a0_gather || (desc->mask_rows && !sg.ids)) return 1;
     if (sg.a0_bstride || sg.a1_bstride) return 1;  // (dense rows only: a row's offset is row x lda)
     if ((uint64_t)sg.rows * (uint64_t)desc->ldc * 4ull >= (1ull << 31)) return 1;  // (the epilogue's store offsets are signed 32-bit scalars)
-    if (g.d.seg[s].T < 1) g.d.seg[s].T = 1;
-    g.rb_start[s] = rb;
-    rb += (sg.rows + 383) / 384;
   }
-  for (int s = desc->nseg; s <= CARCA_MAX_SEGS; ++s) g.rb_start[s] = rb;
-  g.nrb = rb;
+  StreamDev g{};
+  g.d = *desc;
+  const int rb = carca_fill_row_blocks(g, 384, true);  // (the entries behind nseg repeat the total, as this kernel has always had them)
   g.nfull = nfull;
   const int ncu = carca_num_cus();
   const int nfast = desc->K0 / 32;
   // worth it: several tiles per workgroup (a single round belongs to the one-tile kernels and their stream-K relatives)
-  // and a K short enough that the per-tile costs matter (tuning variant 25 forces the kernel wherever it is correct)
+  // and a K short enough that the per-tile costs matter (CARCA_GV_CUS forces the kernel wherever it is correct)
   // (B = 256 at C5's other dimensions, 505 tiles: 152 against 168 us on the one-tile kernel; the CLI's default shape, 303 tiles:
   // 139 against 113 -- the bound sits between them)
-  if (variant != 25 && ((long)rb * ncb * 4 < 7l * ncu || nfast >= 64)) return 1;
+  if (variant != CARCA_GV_CUS && ((long)rb * ncb * 4 < 7l * ncu || nfast >= 64)) return 1;
   // Everybody in teams on the full column blocks, the narrow block's tiles behind them (StreamDev): the smallest common end T
   // (in 1/100 of a full tile's time) for which the narrow tiles all find a place.  C5: 64 teams of four, 31 of them six row
   // blocks and 33 five; T = 6.74 tiles -- one narrow tile behind six full ones, two behind five -- where separate workgroups
@@ -419,17 +414,10 @@ int carca_gemm_rows_stream_try(const CarcaGemmDesc* desc, bool fits32, hipStream
     }
   }
   carca_rows_log(xc == 0 ? "gemm_rows_cus_kernel<0>" : (xc == 1 ? "gemm_rows_cus_kernel<1>" : "gemm_rows_cus_kernel<2>"), desc, grid);
-  hipEvent_t e0, e1;
-  const bool ev = carca_take_launch_events(&e0, &e1);
-  if (xc == 0) {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_cus_kernel<0>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_cus_kernel<0>), dim3(grid), dim3(768), 0, stream, g);
-  } else if (xc == 1) {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_cus_kernel<1>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_cus_kernel<1>), dim3(grid), dim3(768), 0, stream, g);
-  } else {
-    if (ev) hipExtLaunchKernelGGL((gemm_rows_cus_kernel<2>), dim3(grid), dim3(768), 0, stream, e0, e1, 0, g);
-    else hipLaunchKernelGGL((gemm_rows_cus_kernel<2>), dim3(grid), dim3(768), 0, stream, g);
+  switch (xc) {
+    case 0: carca_launch(gemm_rows_cus_kernel<0>, dim3(grid), dim3(768), 0, stream, true, g); break;
+    case 1: carca_launch(gemm_rows_cus_kernel<1>, dim3(grid), dim3(768), 0, stream, true, g); break;
+    default: carca_launch(gemm_rows_cus_kernel<2>, dim3(grid), dim3(768), 0, stream, true, g); break;
   }
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
@@ -826,7 +814,7 @@ __global__ __launch_bounds__(768) void gemm_rows_n96s_kernel(const N96sDev args)
 int carca_gemm_rows_n96s_try(const CarcaGemmDesc* desc, bool fits32, hipStream_t stream) {
   using namespace n96s;
   const int variant = carca_tuning(CARCA_TUNE_GEMM_VARIANT);
-  if (variant == 26 || !fits32) return 1;  // (26: never -- A/B switch)
+  if (variant == CARCA_GV_NO_N96S || !fits32) return 1;  // (never -- A/B switch)
   if (desc->K1 != 0 || desc->N <= 64 || desc->N > 96 || desc->ncols_out > 96 || desc->K0 < 4 * BK) return 1;
   if (desc->colvec) return 1;
   N96sDev g{};
@@ -845,12 +833,12 @@ int carca_gemm_rows_n96s_try(const CarcaGemmDesc* desc, bool fits32, hipStream_t
   for (int s = desc->nseg; s <= CARCA_MAX_SEGS; ++s) g.row_start[s] = (int)rows;
   if (rows >= (1l << 30)) return 1;
   const int ncu = carca_num_cus();
-  // worth it: from 2.5 blocks per CU on (tuning variant 27 forces the kernel wherever it is correct).  Measured, interleaved A/B
+  // worth it: from 2.5 blocks per CU on (CARCA_GV_N96S forces the kernel wherever it is correct).  Measured, interleaved A/B
   // of the joint product: C5 (134,528 rows, 3.3 blocks per CU) 142 against 174 us on the tiled kernel; C3 (77,312 rows, 1.9
   // blocks per CU) 97 against 88 us -- a share's last, partial block costs its seven latency-bound steps whatever it holds
-  if (variant != 27 && rows < (long)ncu * BM * 5 / 2) return 1;
+  if (variant != CARCA_GV_N96S && rows < (long)ncu * BM * 5 / 2) return 1;
   const int grid = (int)std::min<long>(ncu, (rows + BM - 1) / BM);
-  const int diag = carca_tuning(5);
+  const int diag = carca_tuning(CARCA_TUNE_N96S_DIAG);
   static bool attr_set[128] = {false};
   auto launch = [&](auto kern) -> int {
     if (!attr_set[diag & 127]) {
@@ -861,11 +849,7 @@ int carca_gemm_rows_n96s_try(const CarcaGemmDesc* desc, bool fits32, hipStream_t
       }
       attr_set[diag & 127] = true;
     }
-    hipEvent_t e0, e1;
-    if (carca_take_launch_events(&e0, &e1))
-      hipExtLaunchKernelGGL(kern, dim3(grid), dim3(768), LDS_BYTES, stream, e0, e1, 0, g);
-    else
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(768), LDS_BYTES, stream, g);
+    carca_launch(kern, dim3(grid), dim3(768), LDS_BYTES, stream, true, g);
     return 0;
   };
   g.dbg = carca_debug_buffer();

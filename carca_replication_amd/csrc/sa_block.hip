@@ -9,6 +9,7 @@
 // block (carca.py:318), they carry LayerNorm(0) = beta forward and are never attended.
 #include <hip/hip_ext.h>
 #include "attn_common.h"
+#include "gemm_host.h"
 #include "../../include/carca_hip.h"
 
 namespace {
@@ -275,13 +276,9 @@ int launch_sa(const float* x, int ldx, const int32_t* ids, float* y, int ldy, in
   }
   const int tune = carca_tuning(CARCA_TUNE_ATTN_VARIANT);
   const int nparts = (L > 16 && tune != 1 && (tune == 2 || 2 * B <= num_cus)) ? 2 : 1;
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))  // (timing events bound to this dispatch: carca_forward's ev[4], ev[5])
-    hipExtLaunchKernelGGL((sa_block_kernel_w16<DPI, DHP, NH>), dim3(B * nparts), dim3(1024), lds_bytes, stream, e0, e1, 0, x,
-                          ldx, ids, y, ldy, L, d, d / NH, w, residual, sv, dc, site, carca_debug_buffer(), nparts);
-  else
-    hipLaunchKernelGGL((sa_block_kernel_w16<DPI, DHP, NH>), dim3(B * nparts), dim3(1024), lds_bytes, stream, x, ldx, ids,
-                       y, ldy, L, d, d / NH, w, residual, sv, dc, site, carca_debug_buffer(), nparts);
+  // (timing events bound to this dispatch: carca_forward's ev[4], ev[5])
+  carca_launch(sa_block_kernel_w16<DPI, DHP, NH>, dim3(B * nparts), dim3(1024), lds_bytes, stream, true, x, ldx, ids, y, ldy, L,
+               d, d / NH, w, residual, sv, dc, site, carca_debug_buffer(), nparts);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -308,7 +305,7 @@ extern "C" int carca_sa_block_eval(const float* x, int ldx, const int32_t* ids, 
   if (int rc = sa_check("sa_block_eval", x, ldx, ids, y, ldy, B, L, d, H, w, &dpi)) return rc;
   // (the eval kernel reads rows with 16-byte loads: padded internal buffers; anything else, and tuning key 6 = 1, takes
   // the training kernel without its extras)
-  if (ldx % 4 == 0 && ldx >= dpi && carca_tuning(6) != 1)
+  if (ldx % 4 == 0 && ldx >= dpi && carca_tuning(CARCA_TUNE_ROUND1_PATHS) != 1)
     return carca_sa_eval_launch(x, ldx, ids, y, ldy, B, L, d, H, w, residual, pads_uniform, (hipStream_t)stream_);
   return carca_sa_block_fwd(x, ldx, ids, y, ldy, B, L, d, H, w, residual, nullptr, nullptr, stream_);
 }
@@ -319,7 +316,7 @@ extern "C" int carca_sa_block_fwd(const float* x, int ldx, const int32_t* ids, f
   hipStream_t stream = (hipStream_t)stream_;
   int dpi;
   if (int rc = sa_check("sa_block_fwd", x, ldx, ids, y, ldy, B, L, d, H, w, &dpi)) return rc;
-  if (!save && !(drop && drop->p > 0.f) && ldx % 4 == 0 && ldx >= dpi && carca_tuning(6) != 1)
+  if (!save && !(drop && drop->p > 0.f) && ldx % 4 == 0 && ldx >= dpi && carca_tuning(CARCA_TUNE_ROUND1_PATHS) != 1)
     return carca_sa_eval_launch(x, ldx, ids, y, ldy, B, L, d, H, w, residual, 0, stream);
   int dhp, dpo;
   carca_padded_dims(d, H, &dpi, &dhp, &dpo);

@@ -16,6 +16,7 @@
 //   * the prologue's requests are branch-free buffer loads (counted waits), rows travel in pairs (16 B per lane).
 #include <hip/hip_ext.h>
 #include "attn_common.h"
+#include "gemm_host.h"
 #include "../../include/carca_hip.h"
 
 namespace {
@@ -367,11 +368,8 @@ int launch_sa_eval(SaEvalArgs& a, int B, hipStream_t stream) {
   // two workgroups per user while that still fits the chip in one round (tuning key 1: 1 = never, 2 = always)
   const int tune = carca_tuning(CARCA_TUNE_ATTN_VARIANT);
   a.nparts = (a.L > 16 && tune != 1 && (tune == 2 || 2 * B <= carca_num_cus())) ? 2 : 1;
-  hipEvent_t e0, e1;
-  if (carca_take_launch_events(&e0, &e1))  // (timing events bound to this dispatch: carca_forward's ev[4], ev[5])
-    hipExtLaunchKernelGGL(kern, dim3(B * a.nparts), dim3(1024), lds_bytes, stream, e0, e1, 0, a);
-  else
-    hipLaunchKernelGGL(kern, dim3(B * a.nparts), dim3(1024), lds_bytes, stream, a);
+  // (timing events bound to this dispatch: carca_forward's ev[4], ev[5])
+  carca_launch(kern, dim3(B * a.nparts), dim3(1024), lds_bytes, stream, true, a);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }

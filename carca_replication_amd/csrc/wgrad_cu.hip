@@ -598,22 +598,22 @@ int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream) {
   int ncu = g_num_cus;
   if (carca_tuning(CARCA_TUNE_CU_CAP) > 0 && carca_tuning(CARCA_TUNE_CU_CAP) < ncu) ncu = std::max(8, carca_tuning(CARCA_TUNE_CU_CAP) / 8 * 8);
   // worth it only when every CU gets a long run of chunks (pipeline fill + two flushes per block are overhead)
-  const bool forced = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 2 || carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 3;
+  const bool forced = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_PER_CU || carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_PER_CU_STAMPS;
   // (24 chunk-tiles per CU: the d x F product of the re-associated embedding backward, 26 per CU at C2, runs 2x faster
   // here than on the tile kernel; the joint-embedding dW, 5 per CU, does not)
   if (!forced && (total < (long)ncu * 24 || chunks < 8)) return 1;
   // groups of nnb workgroups (see WgradCuDev): per XCD as many whole groups as fit, the left-over slots group across XCDs
-  // (one n block: nothing to share -- consecutive workgroups take consecutive ranges, as before the groups; tuning variant 16
+  // (one n block: nothing to share -- consecutive workgroups take consecutive ranges, as before the groups; CARCA_GV_WGRAD_FLAT_GROUPS
   // forces that numbering for any nnb: A/B switch)
-  g.nxcd = (ncu % 8 == 0 && g.nnb <= ncu / 8 && g.nnb > 1 && carca_tuning(CARCA_TUNE_GEMM_VARIANT) != 16) ? 8 : 1;
+  g.nxcd = (ncu % 8 == 0 && g.nnb <= ncu / 8 && g.nnb > 1 && carca_tuning(CARCA_TUNE_GEMM_VARIANT) != CARCA_GV_WGRAD_FLAT_GROUPS) ? 8 : 1;
   const int per_xcd = ncu / g.nxcd;
   g.gpx = per_xcd / g.nnb;
   g.ngroups = g.nxcd * g.gpx + (g.nxcd * (per_xcd - g.gpx * g.nnb)) / g.nnb;
   if (g.ngroups < 1) return 1;  // (more n blocks than CUs: the tile kernel)
   // (g.ngroups stays the number of groups the chip can HOST; how many of them get units, and which, is the row-table
   // kernel's decision once it has counted the rows that take part: WgPlan)
-  g.slow_w = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 13 ? 256 : 264;  // (variant 13: equal item counts -- A/B switch)
-  g.compact = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 22 ? 0 : 1;       // (variant 22: masked rows stay in the table -- A/B switch)
+  g.slow_w = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_WGRAD_EQUAL_ITEMS ? 256 : 264;  // (A/B switch)
+  g.compact = carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_WGRAD_NO_COMPACT ? 0 : 1;  // (masked rows stay in the table -- A/B switch)
   const int grid = ncu;
   g.V = chunks * WG_BR;
   // k blocks a group's range can touch, for ANY number of chunks per k block c >= 1: a range holds at most
@@ -624,7 +624,7 @@ int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream) {
   // tile, 45 MB, ~14 us of reduce kernel against ~60 us of atomics).  A product of few tiles cut over all the groups (the
   // d x F product of the re-associated backward: 11 tiles, 23 partials each) keeps the atomics.
   const long n_tiles = (long)g.nkb * g.nnb, n_parts = (long)g.ngroups * g.nnb;
-  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 14 || n_parts > 8 * n_tiles) g.slots_pg = 0;
+  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_WGRAD_ATOMIC_FLUSH || n_parts > 8 * n_tiles) g.slots_pg = 0;
   const size_t part_floats = (size_t)g.ngroups * g.slots_pg * g.nnb * WG_BN * WG_BK;
   const size_t plan_ints = (sizeof(WgPlan) + 15) / 16 * 4;
   const size_t cnt_ints = ((size_t)2 * (g.ngroups + 1) + 2 * g.nkb + 5) / 4 * 4 + plan_ints;  // gbegin (8-byte entries) | klo | plan
@@ -642,7 +642,7 @@ int carca_wgrad_cu_try(const CarcaWgradDesc* desc, hipStream_t stream) {
   }
   hipLaunchKernelGGL(wgrad_rowtab_kernel, dim3(1), dim3(1024), 0, stream, g, tab);
   g.dbg = carca_debug_buffer();
-  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == 3 && g.dbg)
+  if (carca_tuning(CARCA_TUNE_GEMM_VARIANT) == CARCA_GV_PER_CU_STAMPS && g.dbg)
     hipLaunchKernelGGL(gemm_wgrad_cu_kernel<1>, dim3(grid), dim3(WG_NT), 0, stream, g);
   else
     hipLaunchKernelGGL(gemm_wgrad_cu_kernel<0>, dim3(grid), dim3(WG_NT), 0, stream, g);

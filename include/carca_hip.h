@@ -46,18 +46,35 @@ extern "C" {
 
 int carca_abi_version(void);
 /* Kernel-variant knobs for tuning runs and A/B tests (tools/, tests/); 0 = the shipped choice everywhere.
- *   key 0  row / weight-gradient GEMM: 1 force 128x96 tiles, 2 force the one-block-per-CU kernels, 3 = 2 + in-kernel
- *          stamps, 4 no buffer loads, 5 tiled weight gradient only, 6 never group weight gradients / row GEMMs,
- *          7 force the one-block-per-CU row GEMM with 384 x 128 tiles, 8 never let the item-row gather ride in the
- *          feature GEMM's launch, 15 the one-tile-per-workgroup feature GEMM (no hand-over of partial tiles), 19 the gather
- *          keeps its own launch beside the stream-K kernels, 21 split-precision kernel without LDS-DMA, 22 weight gradient
- *          over every row, 23 feature GEMM over every row (gemm_rows_sk_kernel instead of gemm_rows_skc_kernel, which
- *          leaves rows with id 0 out); any non-zero value also moves the narrow row products off their default kernel
+ *   key 0  row / weight-gradient GEMM and the item-row gather, ONE switch at a time (csrc/carca_common.h names them CARCA_GV_*);
+ *          any non-zero value also moves the narrow row products off their default kernel:
+ *            1 rows: force 128x96 tiles
+ *            2 rows: force the one-block-per-CU kernels; AND weight gradient: force the persistent kernel
+ *            3 = 2 + in-kernel stamps (both)
+ *            4 rows and tiled weight gradient: no buffer loads; weight gradient: never the persistent kernel
+ *            5 tiled weight gradient only          6 never group weight gradients / row GEMMs
+ *            7 rows: force the one-block-per-CU kernel with 384 x 128 tiles where the tiled kernel would run
+ *            8 never let the item-row gather ride in the feature GEMM's launch
+ *            9 / 10 narrow rows: 64 x 96 tiles with prefetch depth 4 / 2
+ *            11 / 12 narrow rows: the 80 x 96 kernel wherever it applies / never
+ *            13 persistent weight gradient: equal item counts     14 ... atomic flush instead of partial-tile slots
+ *            15 the one-tile-per-workgroup feature GEMM (no hand-over of partial tiles)
+ *            16 persistent weight gradient: consecutive workgroups instead of per-XCD groups
+ *            18 the gather's own launch: one row per wave
+ *            19 the gather keeps its own launch beside the stream-K kernels; AND tiled weight gradient: row splits
+ *            combine by atomics instead of partial tiles
+ *            21 split-precision kernel without LDS-DMA        22 persistent weight gradient over every row
+ *            23 feature GEMM over every row (gemm_rows_sk_kernel instead of gemm_rows_skc_kernel, which leaves rows
+ *            with id 0 out)
+ *            24 / 25 short-K streaming kernel (gemm_rows_cus_kernel): never / wherever it is correct
+ *            26 / 27 persistent narrow-output kernel (gemm_rows_n96s_kernel): never / wherever it is correct
+ *            158 = 15 + 8 (the key holds one value)
  *   key 1  attention kernels: 1 one workgroup per user, 2 always two, 3 one 8-wave workgroup per user (the variant
  *          for batches of more users than CUs, two workgroups resident per CU)
  *   key 2  weight gradient: row-split slot target      key 4  weight gradient: minimum 32-row chunks per split
  *   key 3  weight gradient: plain stores instead of atomics (timing diagnostic, wrong results)
- *   key 5  grouped weight gradient: row-split slot target per product
+ *   key 5  grouped weight gradient: row-split slot target per product; AND gemm_rows_n96s_kernel's timing experiments
+ *          (bit mask; WRONG results)
  *   key 6  1: the round-1 paths (materialised V in the scoring kernel, per-op SelfAttentionBlock backward)
  *   key 7  scoring kernel layout (1 one workgroup per user, 2 fold kernel, 3 persistent stream kernel)
  *   key 8  DETERMINISTIC MODE (1 = on): no fp32 atomics anywhere in the backward pass -- every accumulation into the
@@ -83,6 +100,8 @@ int carca_abi_version(void);
  *          2^11), three products, two fp32 accumulators -- |operands| < 65504 required.  Only where the one-workgroup-per-CU
  *          kernel would run; anything else keeps the fp32 kernels.  + 16: wherever the kernel's own conditions hold
  *          (K0 % 4 == 0, K1 <= 8, plain epilogue), whatever the grid -- for parity tests at fixture sizes.
+ *   key 17 / 18  gemm_rows_skc_kernel: 1 + the K steps that owning a row block costs a team / a lone workgroup (0 = built in)
+ *   key 19 gemm_rows_skc_kernel: K steps of k-source 0 below which the product stays off it (0 = 64)
  *   key 20 feature product of an evaluation forward (carca_forward without a backward's saves): 0 = over one representative
  *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests) */
 int carca_set_tuning(int key, int value);
