@@ -289,6 +289,12 @@ class SampledXentDesc(C.Structure):
                 ("dP", _fp), ("dTp", _fp), ("dS", _fp)]
 
 
+class FeatCache(C.Structure):  # CarcaFeatCache
+    _fields_ = [("p_c", _fp), ("a_c", _fp), ("state", _fp), ("table", _fp), ("n_rows", C.c_int32), ("ld_p", C.c_int32),
+                ("ld_a", C.c_int32)]
+
+
+
 SIGNATURES = {
     "carca_abi_version": (_i, []),
     "carca_set_tuning": (_i, [_i, _i]),
@@ -347,6 +353,9 @@ SIGNATURES = {
                                 _fp]),
     "carca_gemm_rows_log": (_i, [C.c_char_p, _i]),
     "carca_feat_dedup_rows_multiplied": (C.c_longlong, []),
+    "carca_feat_dedup_rows_computed": (C.c_longlong, []),
+    "carca_feat_cache_arm": (_i, [C.POINTER(FeatCache)]),
+    "carca_get_tuning": (_i, [_i]),
     "carca_mha_core_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, C.POINTER(Dropout),
                                  _fp, _fp]),
     "carca_mha_core_bwd_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp,

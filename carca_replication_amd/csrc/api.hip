@@ -109,6 +109,8 @@ extern "C" int carca_set_tuning(int key, int value) {
   return CARCA_OK;
 }
 
+extern "C" int carca_get_tuning(int key) { return key >= 0 && key < CARCA_TUNE_COUNT ? g_tuning[key] : -1; }
+
 extern "C" int carca_abi_version(void) { return CARCA_ABI_VERSION; }
 extern "C" const char* carca_last_error(void) { return g_err; }
 
@@ -466,8 +468,27 @@ bool carca_take_launch_events(hipEvent_t* start, hipEvent_t* stop) {
   return true;
 }
 
+// the per-item cache of the evaluation feature product, armed for this thread's next carca_forward
+static thread_local CarcaFeatCache g_armed_cache{};
+extern "C" int carca_feat_cache_arm(const CarcaFeatCache* cache) {
+  CARCA_CHECK_ARG(!cache || (cache->p_c && cache->state && cache->n_rows >= 1 && cache->ld_p >= 1 &&
+                             (!cache->a_c || cache->ld_a >= 1) && (cache->a_c || cache->table)),
+                  "feat_cache_arm: malformed cache descriptor");
+  g_armed_cache = cache ? *cache : CarcaFeatCache{};
+  return CARCA_OK;
+}
+bool carca_take_feat_cache(CarcaFeatCache* out) {
+  if (!g_armed_cache.state) return false;
+  *out = g_armed_cache;
+  g_armed_cache = CarcaFeatCache{};
+  return true;
+}
+
 extern "C" int carca_forward(const CarcaForwardDesc* D, void* const* ev, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  struct DisarmCache {  // (whatever this call does with it, the armed cache does not outlive it)
+    ~DisarmCache() { g_armed_cache = CarcaFeatCache{}; }
+  } disarm_cache;
   CARCA_CHECK_ARG(D && D->ngroups >= 1 && D->ngroups <= CARCA_MAX_GROUPS && D->n_blocks >= 0 &&
                       D->n_blocks <= CARCA_MAX_BLOCKS,
                   "forward: bad group / block count");

@@ -232,7 +232,9 @@ enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRA
        CARCA_TUNE_SKC_OV_TEAM = 17,        // gemm_rows_skc_kernel: 1 + what owning a row block costs a team, in K steps
        CARCA_TUNE_SKC_OV_LONE = 18,        // ... and a lone workgroup
        CARCA_TUNE_SKC_MIN_STEPS = 19,      // ... and the K steps below which the product stays off that kernel
-       CARCA_TUNE_FEAT_DEDUP = 20, CARCA_TUNE_COUNT = 24 };
+       CARCA_TUNE_FEAT_DEDUP = 20,
+       CARCA_TUNE_FEAT_CACHE = 21,         // 1: the evaluation dedup never uses a per-item cache of P rows (A/B, tests)
+       CARCA_TUNE_COUNT = 24 };
 // Values of key 0 (CARCA_TUNE_GEMM_VARIANT): A/B switches of the row GEMMs, the weight-gradient GEMMs and the gather, one
 // at a time -- which is why 158 exists.  A value with two meanings switches both.
 enum {
@@ -287,6 +289,8 @@ void* carca_capture_alloc(hipStream_t stream, size_t bytes, bool host_mapped, vo
 // is queued around it (an hipEventRecord is one: ~6 us of GPU time between two kernels each).
 void carca_arm_launch_events(void* start, void* stop);
 bool carca_take_launch_events(hipEvent_t* start, hipEvent_t* stop);  // true (and disarms) when armed
+// The per-item cache armed for this thread's next forward (carca_feat_cache_arm, api.hip): true (and disarms) when one is.
+bool carca_take_feat_cache(CarcaFeatCache* out);
 struct CarcaGemmDesc;
 // appends to the row-GEMM kernel log while carca_gemm_rows_log has it switched on (gemm.hip)
 void carca_rows_log(const char* kernel, const CarcaGemmDesc* d, int grid);
@@ -306,6 +310,11 @@ int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* 
 // representative row (-1: id 0) and its flag (1: a representative -- what gemm_rows_skc_kernel plans from), P
 // [R, ldp] (written at the representatives' rows), and wcb [K1 + 1][N]: W_c^T over b_f, written by the insert launch for
 // the expand launch (vec2: that one may use 8-byte accesses).
+// With a per-item cache of P rows (CarcaFeatCache, include/carca_hip.h; cache.state != null): rep of a row whose item's
+// entry is filled and carries the row's bytes is -2 - id (a hit: P comes from the cache); need [R] = flag && !hit is what
+// the product plans from instead of flag, cnt [1] the number of such rows (zeroed by the insert launch: the product
+// returns at once when it reads 0), and pub [R] the id a slot's owner publishes its P row (and attribute row) under in
+// the expand launch, 0 = none.  Without a cache need, pub and cnt are null and every launch is what it was.
 struct CarcaDedupRun {
   CarcaGemmDesc d;
   int nseg, R, vec, vec2, hbits;
@@ -317,6 +326,8 @@ struct CarcaDedupRun {
   float* P;
   float* wcb;
   int ldp;
+  CarcaFeatCache cache;
+  int *need, *pub, *cnt;
 };
 // 1 = not this product's path (nothing launched), CARCA_OK with *run filled, or an error
 int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, CarcaDedupRun* run);

@@ -22,6 +22,22 @@
 //                            are 8-byte aligned (g = 450: rows are never 16-byte aligned).
 // Results are the same bits run to run and in a graph replay (nothing depends on timing), and the same between a dense
 // batch and the attribute table (the same groups: equal ids carry equal bytes).
+//
+// With a per-item cache (CarcaFeatCache) P[i] outlives the batch: an evaluation epoch is hundreds of batches
+// over one catalogue and W_a is frozen for all of it.  The same four launches:
+//   2. a row whose item's entry is FILLED compares its bytes with the entry's copy of the attribute row it was computed
+//      from (dense batches; rows gathered from the cache's table need no compare): equal = a HIT, rep = -2 - id, nothing to
+//      multiply; different = the row goes on as if there were no cache (the entry is never overwritten).  g merges into
+//      its slot's owner r0 only on equal bytes and r0 hits only on the entry's bytes, so a member of a hit owner hits and
+//      a member that missed never merges into a hit owner.  The owner of a slot whose entry is EMPTY is marked for
+//      publishing.  need = flag && !hit is what launch 3 plans from, and their number goes to a device word;
+//   3. returns at its top where that word reads 0;
+//   4. takes P from the batch scratch or from the cache according to rep, and a wave copies each of its rows that is marked
+//      into the cache: the P row as loaded, the attribute row (dense), then state = 1.  Publishing writes only entries
+//      that were empty when launch 2 ran and hits read only entries that were filled then: nothing is read and written
+//      in one launch.
+// A row's P bits are then those of the batch that first computed it (another cut of the K sums; the same for equal call
+// sequences).
 #include <hip/hip_ext.h>
 
 #include <vector>
@@ -61,6 +77,7 @@ __global__ __launch_bounds__(256) void dedup_insert_kernel(const CarcaDedupRun a
       a.wcb[i] = k < K1 ? a.d.bt1[(size_t)n * a.d.ldb1 + k] : (k == K1 && a.d.bias ? a.d.bias[n] : 0.f);
     }
   }
+  if (g == 0 && a.cnt) a.cnt[0] = 0;  // (the resolve launch counts the rows the product has to multiply into it)
   if (g >= a.R) return;
   const int s = dd_seg(a, g);
   const int id = a.d.seg[s].ids[g - a.row0[s]];
@@ -78,64 +95,104 @@ __global__ __launch_bounds__(256) void dedup_insert_kernel(const CarcaDedupRun a
   a.slot[g] = h;
 }
 
-// one wave per row; VEC: every attribute row 16-byte aligned and K0 % 4 == 0
+// whether two rows of K 32-bit words differ, by one wave (integer compare: -0.0 / +0.0 and NaN payloads differ)
+// VEC: both rows 16-byte aligned and K % 4 == 0
+template <bool VEC>
+__device__ __forceinline__ bool dd_rows_differ(const unsigned* p, const unsigned* q, const int K, const int lane) {
+  bool diff = false;
+  if constexpr (VEC) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    // 4 KB of each row per round (4 loads per lane and row in flight), a vote after each
+    for (int k0 = 0; k0 < K && !diff; k0 += 1024) {
+      u4 x[4], y[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + (u * 64 + lane) * 4;
+        x[u] = k < K ? *reinterpret_cast<const u4*>(p + k) : u4{0, 0, 0, 0};
+        y[u] = k < K ? *reinterpret_cast<const u4*>(q + k) : u4{0, 0, 0, 0};
+      }
+      bool d = false;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) d = d || x[u][0] != y[u][0] || x[u][1] != y[u][1] || x[u][2] != y[u][2] || x[u][3] != y[u][3];
+      diff = __ballot(d) != 0;
+    }
+  } else {
+    for (int k0 = 0; k0 < K && !diff; k0 += 256) {
+      bool d = false;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * 64 + lane;
+        if (k < K) d = d || p[k] != q[k];
+      }
+      diff = __ballot(d) != 0;
+    }
+  }
+  return diff;
+}
+
+// one wave per row; VEC: every attribute row (the cache's copies included) 16-byte aligned and K0 % 4 == 0
 template <bool VEC>
 __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun a) {
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   if (g >= a.R) return;
   const int h = a.slot[g];
+  const bool cache = a.cache.state != nullptr;
   if (h < 0) {
     if (lane == 0) {
       a.rep[g] = -1;
       a.flag[g] = 0;
+      if (cache) {
+        a.need[g] = 0;
+        a.pub[g] = 0;
+      }
     }
     return;
   }
   const int r0 = (int)(0xFFFFFFFFu - a.val[h]);
+  const int s = dd_seg(a, g);
+  const CarcaGemmSeg& sg = a.d.seg[s];
+  // the cache entry of this row's item: ci > 0 where it has one, filled or empty
+  int ci = 0;
+  bool filled = false, hit = false, from_table = false;
+  if (cache) {
+    const int id = __builtin_amdgcn_readfirstlane(a.key[h]);
+    from_table = sg.a0_gather && sg.a0 == a.cache.table;
+    if (id > 0 && id < a.cache.n_rows && (a.cache.a_c || from_table)) {
+      ci = id;
+      filled = a.cache.state[id] == 1;
+    }
+    if (filled) {
+      if (a.cache.a_c) {
+        const unsigned* p = reinterpret_cast<const unsigned*>(dd_a0_row(a, s, g - a.row0[s]));
+        const unsigned* q = reinterpret_cast<const unsigned*>(a.cache.a_c + (size_t)ci * a.cache.ld_a);
+        hit = !dd_rows_differ<VEC>(p, q, a.d.K0, lane);
+      } else {
+        hit = true;  // (the table the entry was computed from, the same id: the same row)
+      }
+    }
+  }
   bool merge = false;
-  if (r0 != g) {
-    const int s = dd_seg(a, g), t = dd_seg(a, r0);
-    const CarcaGemmSeg &sg = a.d.seg[s], &tg = a.d.seg[t];
+  if (!hit && r0 != g) {
+    const int t = dd_seg(a, r0);
+    const CarcaGemmSeg& tg = a.d.seg[t];
     merge = sg.a0_gather && tg.a0_gather && sg.a0 == tg.a0;  // (one table, one id: one row)
     if (!merge) {
       const unsigned* p = reinterpret_cast<const unsigned*>(dd_a0_row(a, s, g - a.row0[s]));
       const unsigned* q = reinterpret_cast<const unsigned*>(dd_a0_row(a, t, r0 - a.row0[t]));
-      const int K = a.d.K0;
-      bool diff = false;
-      if constexpr (VEC) {
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        // 4 KB of each row per round (4 loads per lane and row in flight), a vote after each
-        for (int k0 = 0; k0 < K && !diff; k0 += 1024) {
-          u4 x[4], y[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int k = k0 + (u * 64 + lane) * 4;
-            x[u] = k < K ? *reinterpret_cast<const u4*>(p + k) : u4{0, 0, 0, 0};
-            y[u] = k < K ? *reinterpret_cast<const u4*>(q + k) : u4{0, 0, 0, 0};
-          }
-          bool d = false;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) d = d || x[u][0] != y[u][0] || x[u][1] != y[u][1] || x[u][2] != y[u][2] || x[u][3] != y[u][3];
-          diff = __ballot(d) != 0;
-        }
-      } else {
-        for (int k0 = 0; k0 < K && !diff; k0 += 256) {
-          bool d = false;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int k = k0 + u * 64 + lane;
-            if (k < K) d = d || p[k] != q[k];
-          }
-          diff = __ballot(d) != 0;
-        }
-      }
-      merge = !diff;
+      merge = !dd_rows_differ<VEC>(p, q, a.d.K0, lane);
     }
   }
   if (lane == 0) {
-    a.rep[g] = merge ? r0 : g;
-    a.flag[g] = merge ? 0 : 1;
+    // (a hit that does not own the slot counts as merged: its owner hit too unless the owner carries other bytes)
+    a.rep[g] = hit ? -2 - ci : (merge ? r0 : g);
+    a.flag[g] = hit ? (r0 == g ? 1 : 0) : (merge ? 0 : 1);
+    if (cache) {
+      const int need = !hit && !merge;
+      a.need[g] = need;
+      a.pub[g] = r0 == g && ci > 0 && !filled ? ci : 0;  // (the owner is its own representative: P[g] is computed)
+      if (need) atomicAdd(a.cnt, 1);
+    }
     if (r0 != g) a.slot[g] = -1;  // (the slot stays with its owner, the lowest row: the expand kernel clears it)
   }
 }
@@ -161,12 +218,15 @@ template <int VW>
 __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a) {
   typedef float vec __attribute__((ext_vector_type(VW)));
   typedef float f4 __attribute__((ext_vector_type(4)));
-  extern __shared__ f4 exp_lds[];  // the weight block [K1 + 1][N] | context values [EXP_ROWS][8] | representatives [EXP_ROWS]
+  // the weight block [K1 + 1][N] | context values [EXP_ROWS][8] | representatives [EXP_ROWS] | ids to publish under [EXP_ROWS]
+  extern __shared__ f4 exp_lds[];
   carca_warm_kernargs<sizeof(CarcaDedupRun)>();
   const int N = a.d.N, K1 = a.d.K1, nw4 = exp_wb_floats(K1, N) / 4;
   float* Ws = reinterpret_cast<float*>(exp_lds);
   float* cxs = Ws + nw4 * 4;
   int* reps = reinterpret_cast<int*>(cxs + EXP_ROWS * EXP_MAX_K1);
+  int* pubs = reps + EXP_ROWS;
+  const bool cache = a.cache.state != nullptr;
   const int tid = threadIdx.x, g0 = blockIdx.x * EXP_ROWS;
   // one round trip: the weight block, the rows' context values (thread = row, k), rep and slot (thread = row)
   f4 w[EXP_WB4];
@@ -188,9 +248,12 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
     cxs[tid] = cv;
   } else if (tid < EXP_ROWS * EXP_MAX_K1 + EXP_ROWS) {
     const int row = tid - EXP_ROWS * EXP_MAX_K1, g = g0 + row;
-    int u = -2;  // (-2: past the last row, -1: id 0 -- the resolve kernel wrote rep = -1 there and P has no such row)
+    // (-2: past the last row, -1: id 0 -- the resolve kernel wrote rep = -1 there and P has no such row; below -2: row
+    // -2 - u of the cache)
+    int u = -2, pb = 0;
     if (g < a.R) {
       u = a.rep[g];
+      if (cache) pb = a.pub[g];
       const int h = a.slot[g];
       if (h >= 0) {  // (nobody reads the table after the resolve kernel)
         a.key[h] = 0;
@@ -198,6 +261,7 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
       }
     }
     reps[row] = u;
+    pubs[row] = pb;
   }
 #pragma unroll
   for (int j = 0; j < EXP_WB4; ++j) {
@@ -208,25 +272,36 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int RW = EXP_ROWS / 4, CH = 4;  // rows per wave; 64-lane column chunks in flight per row
   const int nv = N / VW;                    // (VW = 2: N is even)
-  int u[RW];
+  int u[RW], pb[RW];
   vec* crow[RW];
+  const vec* prow[RW];
 #pragma unroll
   for (int i = 0; i < RW; ++i) {
     const int row = wave * RW + i;
     u[i] = __builtin_amdgcn_readfirstlane(reps[row]);
+    pb[i] = __builtin_amdgcn_readfirstlane(pubs[row]);
     const DdRowSeg sg = dd_row_seg(a, min(g0 + row, a.R - 1));
     crow[i] = reinterpret_cast<vec*>(sg.c + (size_t)sg.r * a.d.ldc);
+    prow[i] = reinterpret_cast<const vec*>(u[i] < -2 ? a.cache.p_c + (size_t)(-2 - u[i]) * a.cache.ld_p
+                                                    : a.P + (size_t)max(u[i], 0) * a.ldp);
   }
   const vec* Wv = reinterpret_cast<const vec*>(Ws);
   for (int c0 = 0; c0 < nv; c0 += CH * 64) {
     vec v[RW][CH];
 #pragma unroll
     for (int i = 0; i < RW; ++i) {
-      const vec* prow = reinterpret_cast<const vec*>(a.P + (size_t)max(u[i], 0) * a.ldp);
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         const int p = c0 + c * 64 + lane;
-        v[i][c] = u[i] >= 0 && p < nv ? prow[p] : vec(0.f);
+        v[i][c] = u[i] != -1 && u[i] != -2 && p < nv ? prow[i][p] : vec(0.f);
+      }
+      if (pb[i] > 0) {  // (a slot's owner whose item has an empty entry: its P row as loaded)
+        vec* pc = reinterpret_cast<vec*>(a.cache.p_c + (size_t)pb[i] * a.cache.ld_p);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int p = c0 + c * 64 + lane;
+          if (p < nv) pc[p] = v[i][c];
+        }
       }
     }
     // (k outermost: one read of W_c's row k and of the rows' context values serves all RW x CH accesses; per element
@@ -251,7 +326,27 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
       const vec b = Wv[K1 * nv + min(p, nv - 1)];
 #pragma unroll
       for (int i = 0; i < RW; ++i)
-        if (u[i] >= -1 && p < nv) crow[i][p] = u[i] >= 0 ? v[i][c] + b : vec(0.f);
+        if (u[i] != -2 && p < nv) crow[i][p] = u[i] != -1 ? v[i][c] + b : vec(0.f);
+    }
+  }
+  // publishing: the attribute row each marked row's P was computed from (dense batches), then the entry counts as filled
+  if (cache) {
+#pragma unroll 1
+    for (int i = 0; i < RW; ++i) {
+      if (pb[i] <= 0) continue;
+      if (a.cache.a_c) {
+        const int g = g0 + wave * RW + i, s = dd_seg(a, g);
+        const float* src = dd_a0_row(a, s, g - a.row0[s]);
+        float* dst = a.cache.a_c + (size_t)pb[i] * a.cache.ld_a;
+        if (a.vec) {
+          const f4* s4 = reinterpret_cast<const f4*>(src);
+          f4* d4 = reinterpret_cast<f4*>(dst);
+          for (int k = lane; k < a.d.K0 / 4; k += 64) d4[k] = s4[k];
+        } else {
+          for (int k = lane; k < a.d.K0; k += 64) dst[k] = src[k];
+        }
+      }
+      if (lane == 0) a.cache.state[pb[i]] = 1;
     }
   }
 }
@@ -259,10 +354,10 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
 // the last eager launch of this thread, for carca_feat_dedup_rows_multiplied: where its flags lie in the stream's scratch
 struct DdLast {
   hipStream_t stream;
-  size_t bytes, flag_off;
+  size_t bytes, flag_off, need_off;  // (need_off = flag_off without a cache: every flagged row is multiplied)
   int R;
 };
-thread_local DdLast g_dd_last{nullptr, 0, 0, 0};
+thread_local DdLast g_dd_last{nullptr, 0, 0, 0, 0};
 
 }  // namespace
 
@@ -298,12 +393,29 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
   bool vec2 = D.N % 2 == 0 && D.ldc % 2 == 0;
   for (int s = 0; s < D.nseg; ++s) vec2 = vec2 && ((uintptr_t)D.seg[s].c & 7) == 0;
   a.vec2 = vec2 ? 1 : 0;
+  const bool cap = carca_stream_capturing(stream);
+  // the per-item cache armed for this forward: never under capture (a replay would publish into memory the graph does not
+  // own) and never with tuning key 21 = 1
+  // ... and never while a knob of the product's kernel is off its default: a tuning or diagnostic run is about that
+  // kernel (stamps, hand-over bounds, a withheld flag), and a launch with nothing to multiply would tell it nothing
+  bool knobs = false;
+  for (int k : {CARCA_TUNE_GEMM_VARIANT, CARCA_TUNE_STAMPS, CARCA_TUNE_CU_CAP, CARCA_TUNE_SK_DON, CARCA_TUNE_SK_SPIN_LOG2,
+                CARCA_TUNE_SK_WITHHOLD, CARCA_TUNE_DIAG, CARCA_TUNE_SKC_OV_TEAM, CARCA_TUNE_SKC_OV_LONE,
+                CARCA_TUNE_SKC_MIN_STEPS})
+    knobs = knobs || carca_tuning(k) != 0;
+  CarcaFeatCache fc;
+  const bool cached = carca_take_feat_cache(&fc) && !cap && !knobs && carca_tuning(CARCA_TUNE_FEAT_CACHE) != 1 &&
+                      fc.ld_p >= D.N && (!fc.a_c || fc.ld_a >= D.K0);
+  if (cached) {
+    a.cache = fc;
+    if (fc.a_c && (((uintptr_t)fc.a_c & 15) != 0 || fc.ld_a % 4 != 0)) a.vec = 0;
+    if (((uintptr_t)fc.p_c & 7) != 0 || fc.ld_p % 2 != 0) a.vec2 = 0;
+  }
   // the table (zeroed when allocated, kept clean by the expand kernel) and the per-launch arrays + weight block + P
   const size_t hbytes = (size_t)2 * sizeof(int) << hb;
-  const size_t ibytes = ((size_t)3 * R * sizeof(int) + 255) / 256 * 256;
+  const size_t ibytes = ((size_t)(cached ? 5 * R + 1 : 3 * R) * sizeof(int) + 255) / 256 * 256;
   const size_t wbytes = ((size_t)exp_wb_floats(D.K1, D.N) * sizeof(float) + 255) / 256 * 256;
   const size_t bytes = ibytes + wbytes + (size_t)R * a.ldp * sizeof(float);
-  const bool cap = carca_stream_capturing(stream);
   char* ht = (char*)(cap ? carca_capture_alloc(stream, hbytes, false, nullptr, hbytes)
                          : carca_stream_scratch(stream, CARCA_SCRATCH_DEDUP_HASH, hbytes, hbytes));
   char* buf = (char*)(cap ? carca_capture_alloc(stream, bytes, false, nullptr)
@@ -314,9 +426,15 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
   a.slot = (int*)buf;
   a.rep = a.slot + R;
   a.flag = a.rep + R;
+  if (cached) {
+    a.need = a.flag + R;
+    a.pub = a.need + R;
+    a.cnt = a.pub + R;
+  }
   a.wcb = (float*)(buf + ibytes);
   a.P = (float*)(buf + ibytes + wbytes);
-  g_dd_last = cap ? DdLast{nullptr, 0, 0, 0} : DdLast{stream, bytes, (size_t)2 * R * sizeof(int), a.R};
+  g_dd_last = cap ? DdLast{nullptr, 0, 0, 0, 0}
+                  : DdLast{stream, bytes, (size_t)2 * R * sizeof(int), (size_t)(cached ? 3 : 2) * R * sizeof(int), a.R};
   return CARCA_OK;
 }
 
@@ -341,7 +459,7 @@ int carca_feat_dedup_plan(const CarcaDedupRun* run, hipStream_t stream, hipEvent
 int carca_feat_dedup_expand(const CarcaDedupRun* run, hipStream_t stream, hipEvent_t stop) {
   const CarcaDedupRun& a = *run;
   const dim3 ge((a.R + EXP_ROWS - 1) / EXP_ROWS);
-  const size_t lds = ((size_t)exp_wb_floats(a.d.K1, a.d.N) + EXP_ROWS * EXP_MAX_K1 + EXP_ROWS) * sizeof(float);
+  const size_t lds = ((size_t)exp_wb_floats(a.d.K1, a.d.N) + EXP_ROWS * EXP_MAX_K1 + 2 * EXP_ROWS) * sizeof(float);
   auto kern = a.vec2 ? dedup_expand_kernel<2> : dedup_expand_kernel<1>;
   if (stop)
     hipExtLaunchKernelGGL(kern, ge, dim3(256), lds, stream, nullptr, stop, 0, a);
@@ -351,20 +469,26 @@ int carca_feat_dedup_expand(const CarcaDedupRun* run, hipStream_t stream, hipEve
   return CARCA_OK;
 }
 
-// Rows the product of this thread's last eager dedup launch multiplied (its flagged rows), read back after the launch's
-// stream has drained; -1: no such launch (none yet, or the last one was captured).  For tests: a table that is not handed
-// back clean shows here (rows that no longer merge), never in q.
-extern "C" long long carca_feat_dedup_rows_multiplied(void) {
+// Rows of this thread's last eager dedup launch with a set entry in the int array at `off` of its scratch, read back after
+// the launch's stream has drained; -1: no such launch (none yet, or the last one was captured).
+static long long dd_count_last(size_t DdLast::*off) {
   const DdLast l = g_dd_last;
   if (!l.R) return -1;
   // (the same request as the launch's: the stream's buffer as it stands, not a pointer kept past a release)
   const char* buf = (const char*)carca_stream_scratch(l.stream, CARCA_SCRATCH_DEDUP, l.bytes);
   if (!buf) return -1;
   std::vector<int> flag(l.R);
-  if (hipMemcpyAsync(flag.data(), buf + l.flag_off, (size_t)l.R * sizeof(int), hipMemcpyDeviceToHost, l.stream) != hipSuccess ||
+  if (hipMemcpyAsync(flag.data(), buf + l.*off, (size_t)l.R * sizeof(int), hipMemcpyDeviceToHost, l.stream) != hipSuccess ||
       hipStreamSynchronize(l.stream) != hipSuccess)
     return -1;
   long long n = 0;
   for (int f : flag) n += f != 0;
   return n;
 }
+
+// The launch's flagged rows: one per group of equal attribute rows of the batch, whether the product multiplied it or the
+// cache supplied it (a hit that does not own its id's slot counts as merged).  For tests: a table that is not handed
+// back clean shows here (rows that no longer merge), never in q.
+extern "C" long long carca_feat_dedup_rows_multiplied(void) { return dd_count_last(&DdLast::flag_off); }
+// ... and the rows the product multiplied: the flagged rows that no cache entry served.
+extern "C" long long carca_feat_dedup_rows_computed(void) { return dd_count_last(&DdLast::need_off); }

@@ -76,6 +76,9 @@ struct GemmDev {
   // are those with keep[s][row] != 0 instead of ids != 0, and the rows left out are not cleared (nothing reads them)
   int keep_on;
   const int32_t* keep[CARCA_MAX_SEGS];
+  // ... and, where a per-item cache may have served every row, the number of rows with keep != 0 (device word written by
+  // the launch in front; null: not counted): the kernel returns at its top when it reads 0
+  const int* keep_count;
 };
 
 
@@ -1109,6 +1112,9 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
   __shared__ int Cp[SKC_CH];        // kept rows before each 64-row chunk of its segment (+ the segment's total)
   __shared__ int Pc[8 * SKC_RB + 4];  // this workgroup's pieces (step 5)
   carca_warm_kernargs<sizeof(GemmDev)>();
+  // (nothing to multiply: every workgroup reads the same word and leaves before the prologue, the hand-over flags and any
+  // clearing -- keep_on launches clear nothing)
+  if (args.keep_count && *args.keep_count == 0) return;
   if (args.dbg && (threadIdx.x & 63) == 0) args.dbg[65536 + 4096 + blockIdx.x * 16 + (threadIdx.x >> 6)] = wall_clock64();
   const CarcaGemmDesc& D = args.d;
   const int id = blockIdx.x, nblk = gridDim.x - args.has_pas;
@@ -2037,8 +2043,9 @@ static int launch_gemm_rows_skc(const CarcaGemmDesc* desc, hipStream_t stream, c
       g.d.seg[s].c = dd.P + (size_t)dd.row0[s] * dd.ldp;
       g.d.seg[s].a1 = nullptr;
       g.d.seg[s].a1_bstride = 0;
-      g.keep[s] = dd.flag + dd.row0[s];
+      g.keep[s] = (dd.need ? dd.need : dd.flag) + dd.row0[s];  // (with a cache: the flagged rows no entry served)
     }
+    g.keep_count = dd.cnt;
   }
   int grid = ncu;
   // The gather rides (last workgroup: gather_rows_dma, ~20 ns per row measured beside the tiles: 392 us for C2's 19 k rows)

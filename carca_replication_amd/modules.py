@@ -225,6 +225,23 @@ def _drop_tables(state: dict) -> dict:
     return state
 
 
+# the per-item cache of the evaluation feature product (AllEmbedding.feat_cache): what its tensors may take, in bytes
+FEAT_CACHE_BUDGET = 2 << 30
+
+
+def feat_cache_bytes(n_items: int, n_attrs_dense: int, g: int) -> int:
+    """P_c [n_items, g] + A_c [n_items, n_attrs] (dense batches; 0 columns on the table path), fp32."""
+    return n_items * (n_attrs_dense + g) * 4
+
+
+def feat_cache_key(epoch: int, W: Tensor, table: Optional[Tensor], n_attrs: int, stream: int) -> tuple:
+    """What a filled entry depends on besides its own attribute row: W_a's version (with the epoch every training forward
+    advances: not every optimizer bumps _version), which attribute table the rows come from, and the stream the fills
+    and the reads are ordered on.  The bias and the context columns are not part of P."""
+    return (epoch, W.data_ptr(), W._version, None if table is None else (id(table), table.data_ptr(), table._version),
+            int(n_attrs), stream)
+
+
 class AllEmbedding(Embedding):
     def __init__(self, n_items: int, d: int, g: int, n_ctx: int, n_attrs: int, enc: Encoding):
         super().__init__()
@@ -249,6 +266,7 @@ class AllEmbedding(Embedding):
         state.pop("_fold_train", None)
         state.pop("_wf_t", None)
         state.pop("_ztab_cache", None)
+        state.pop("_feat_cache", None)
         return _drop_tables(state)
 
     def register_attr_table(self, attrs: Optional[Tensor]) -> None:
@@ -302,6 +320,51 @@ class AllEmbedding(Embedding):
         (zt,) = ops.gemm_rows([dict(a0=E)], Wj[:, :d], d, d, d, alpha=float(d) ** 0.5)
         self.__dict__["_ztab_cache"] = (key, zt)
         return zt
+
+    def feat_cache(self, n_attrs: int, table: Optional[Tensor]):
+        """The per-item cache of the evaluation feature product's attribute part, P[i] = attrs[i] W_a^T, as the
+        _lib.FeatCache the next carca_forward is armed with, or None where the forward runs without one.
+
+        Three tensors owned by this module, allocated on the first eligible call and kept out of pickles: P_c
+        [n_items, g], state [n_items] (0 empty, 1 filled) and, for dense batches (table None), A_c [n_items, n_attrs], the
+        attribute row each entry was computed from -- the kernels compare a batch row's bytes with it before they use
+        an entry.  The kernels fill entries; this function empties them all (one memset of state) whenever the key
+        changes: (_WEIGHT_EPOCH, data_ptr, _version) of feats_embed.weight, the identity and version of the attribute
+        table, n_attrs, the stream.  None: under stream capture, on any stream but the one the cache was created on, with
+        tuning key 21 = 1, and where the tensors would exceed FEAT_CACHE_BUDGET bytes."""
+        W = self.feats_embed.weight
+        g, n_items = W.shape[0], self.items_embed.num_embeddings
+        dense = table is None
+        # (where the product can run over distinct rows at all: gemm_rows_skc_kernel's K and N, csrc/gemm.hip)
+        if n_attrs < 2048 or g <= 96 or ops.get_tuning(ops.TUNE_FEAT_CACHE) == 1:
+            return None
+        if feat_cache_bytes(n_items, n_attrs if dense else 0, g) > FEAT_CACHE_BUDGET:
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        stream = ops._stream()
+        c = self.__dict__.get("_feat_cache")
+        if c is not None and (c["P"].device != W.device or c["P"].shape != (n_items, g)):
+            c = None  # (the module moved or changed shape: a new cache)
+        if c is not None and c["stream"] != stream:
+            return None
+        if c is None:
+            c = dict(stream=stream, key=None, A=None, table=None, dirty=False,
+                     P=torch.empty(n_items, g, dtype=torch.float32, device=W.device),
+                     state=torch.zeros(n_items, dtype=torch.int32, device=W.device))
+            self.__dict__["_feat_cache"] = c
+        if dense and (c["A"] is None or c["A"].shape[1] != n_attrs):
+            c["A"] = torch.empty(n_items, n_attrs, dtype=torch.float32, device=W.device)
+        key = feat_cache_key(_WEIGHT_EPOCH[0], W, table, n_attrs, stream)
+        if c["key"] != key:
+            if c["dirty"]:  # (entries filled under another key: all empty again, the data stays)
+                c["state"].zero_()
+            c["key"], c["table"], c["dirty"] = key, table, True  # (the table is referenced: its id cannot be reused)
+        fc = _lib.FeatCache()
+        fc.p_c, fc.state, fc.n_rows, fc.ld_p = c["P"].data_ptr(), c["state"].data_ptr(), n_items, g
+        fc.a_c, fc.ld_a = (c["A"].data_ptr(), n_attrs) if dense else (None, 0)
+        fc.table = None if dense else table.data_ptr()
+        return fc
 
     def _pos(self, T: int) -> Optional[Tensor]:
         return _position_table(self.enc, T)
@@ -1445,7 +1508,14 @@ class CARCA(_PackedModule, Model):
                          cw=D.ca, m_embed=m_embed, p_emb=p_emb, keep=(keep, D))
         ev = (C.c_void_p * len(events))(*events) if events is not None else None
         D.n_events = len(events) if events is not None else 0
-        _lib.check(_lib.load().carca_forward(C.byref(D), ev, ops._stream()), "forward")
+        lib = _lib.load()
+        if train is None and not self.training and D.fold_wc is None and isinstance(emb, AllEmbedding):
+            # (evaluation: P rows of items an earlier batch multiplied come from the module's per-item cache)
+            # (dense as soon as one segment brings its attribute rows: their bytes are then compared, gathered rows included)
+            fc = emb.feat_cache(n_attrs, table if all(sg[1] is None for sg in segs) else None)
+            if fc is not None:
+                _lib.check(lib.carca_feat_cache_arm(C.byref(fc)), "feat_cache_arm")
+        _lib.check(lib.carca_forward(C.byref(D), ev, ops._stream()), "forward")
         return ys
 
     def forward_nograd(self, profile, targets, trace: Optional[dict] = None) -> List[Tensor]:

@@ -1283,9 +1283,24 @@ def gemm_rows_log(on: Optional[bool] = None) -> str:
 
 
 def feat_dedup_rows_multiplied() -> int:
-    """Rows the feature product of the calling thread's last eager "+dedup" launch multiplied (waits for its stream);
-    -1 when there was none or the last one was captured."""
+    """Rows of the calling thread's last eager "+dedup" launch that represent a distinct attribute row of their batch,
+    multiplied or taken from the per-item cache (waits for its stream); -1 when there was none or the last one was
+    captured."""
     return int(_lib.load().carca_feat_dedup_rows_multiplied())
+
+
+def feat_dedup_rows_computed() -> int:
+    """Rows of that launch the product really multiplied: the rows of feat_dedup_rows_multiplied() that no entry of the
+    per-item cache (AllEmbedding.feat_cache) served.  Equal to it without a cache."""
+    return int(_lib.load().carca_feat_dedup_rows_computed())
+
+
+TUNE_FEAT_CACHE = 21  # 1: the evaluation dedup never uses the per-item cache of P rows (A/B, tests)
+
+
+def get_tuning(key: int) -> int:
+    """carca_get_tuning: the value set_tuning last gave `key`."""
+    return int(_lib.load().carca_get_tuning(int(key)))
 
 
 def set_feature_gemm_precision(mode: str, force: bool = False) -> None:

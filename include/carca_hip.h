@@ -103,7 +103,8 @@ int carca_abi_version(void);
  *   key 17 / 18  gemm_rows_skc_kernel: 1 + the K steps that owning a row block costs a team / a lone workgroup (0 = built in)
  *   key 19 gemm_rows_skc_kernel: K steps of k-source 0 below which the product stays off it (0 = 64)
  *   key 20 feature product of an evaluation forward (carca_forward without a backward's saves): 0 = over one representative
- *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests) */
+ *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests)
+ *   key 21 1 = the per-item cache of that product (carca_feat_cache_arm) is never used (A/B, tests) */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
@@ -497,10 +498,37 @@ int carca_mha_core(const float* q, int ldq, const float* k, const float* v, int 
  * carca_gemm_rows_log(buf, cap) copies the log (NUL-terminated) and returns its length.  tools/bench_configs.py names each
  * configuration's dominant kernel with it. */
 int carca_gemm_rows_log(char* out /*or NULL*/, int cap);
-/* Rows the feature product of the calling thread's last eager "+dedup" launch multiplied (one per group of equal attribute
- * rows), read back once the launch's stream has drained; -1 when there was none or the last one was captured.  A hash
- * table that a launch did not hand back clean shows here -- rows stop merging -- and never in the results. */
+/* Rows of the calling thread's last eager "+dedup" launch that represent a distinct attribute row of their batch (one per
+ * group of equal attribute rows), whether the product multiplied them or a per-item cache (below) supplied them; read back
+ * once the launch's stream has drained; -1 when there was none or the last one was captured.  A hash table that a
+ * launch did not hand back clean shows here -- rows stop merging -- and never in the results.  (Under a cache, rows
+ * that hit and do not own their id's table slot count as merged: where an id's lowest row carries other bytes than the
+ * cache while later rows carry the cache's, those later rows are not counted.) */
 long long carca_feat_dedup_rows_multiplied(void);
+/* ... and the rows of that launch the product really multiplied: those of the count above that no cache entry served. */
+long long carca_feat_dedup_rows_computed(void);
+/* A per-item cache of the evaluation feature product's attribute part, P[i] = attrs[i] W_a^T (feat_dedup.hip; DESIGN.md
+ * 4f), indexed by item id.  The "+dedup" launches fill it lazily -- a slot's owner row publishes its P row (and, for dense
+ * batches, the attribute row it was computed from) into an EMPTY entry -- and later launches take a filled entry's row
+ * instead of multiplying, after comparing the batch row's bytes with a_c (dense batches) or without a compare where the
+ * rows are gathered from `table` by id.  A filled entry is never overwritten; the owner of the memory empties the cache
+ * (zeroes `state`) whenever W_a or the table may have changed.  All device memory, valid until the launches have run.
+ *   p_c [n_rows, ld_p] (ld_p >= g), a_c [n_rows, ld_a] (ld_a >= n_attrs) or NULL (table batches only),
+ *   state [n_rows] int32: 0 empty, 1 filled, table: the attribute table a_c == NULL stands for, or NULL. */
+typedef struct {
+  float* p_c;
+  float* a_c;
+  int32_t* state;
+  const float* table;
+  int32_t n_rows, ld_p, ld_a;
+} CarcaFeatCache;
+/* Arms `cache` (copied) for the calling thread's NEXT carca_forward, which hands it to its "+dedup" launches if it has any
+ * and disarms it in every case; NULL disarms.  Ignored (the parent launches, nothing read or written) under stream
+ * capture, with tuning key 21 = 1, and while a knob of the product's kernel (keys 0, 9 - 13, 15, 17 - 19) is off its
+ * default: such a run is about that kernel. */
+int carca_feat_cache_arm(const CarcaFeatCache* cache /*or NULL*/);
+/* The value carca_set_tuning last gave `key` (0 = the shipped choice); -1 for a key outside the table. */
+int carca_get_tuning(int key);
 /* carca_mha_core with nn.Dropout on the weights (carca.py:258): W * keep / (1 - p) multiplies v, w_out stays pre-dropout
  * (carca.py:262-263); element (b, h, t, j) of site drop->site, keep-mask written to keep_out [B, H, Tq, Tk] (uint8,
  * or NULL).  drop NULL or p = 0: carca_mha_core.  The attention of profiles longer than the fused kernels' 64 slots
