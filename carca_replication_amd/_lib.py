@@ -19,9 +19,9 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "catalogue_sweep.h", "xent_tile.h"]
+           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -289,6 +289,16 @@ class SampledXentDesc(C.Structure):
                 ("dP", _fp), ("dTp", _fp), ("dS", _fp)]
 
 
+class SampledBceDesc(C.Structure):
+    """CarcaSampledBceDesc (carca_sampled_bce_fwd / _bwd)."""
+    _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp),
+                ("ld_p", C.c_int32), ("Tp", _fp), ("ld_tp", C.c_int32), ("C", _fp), ("ld_c", C.c_int32), ("pos", _fp),
+                ("S", _fp), ("ld_s", C.c_int32), ("s_ids", _fp), ("beta", C.c_float), ("splits_samples", C.c_int32),
+                ("samples_per_split", C.c_int32), ("splits_rows", C.c_int32), ("scratch", _fp),
+                ("scratch_floats", C.c_int64), ("zpos", _fp), ("br", _fp), ("gsum", _fp), ("row_loss", _fp),
+                ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dTp", _fp), ("dC", _fp), ("dS", _fp)]
+
+
 class FeatCache(C.Structure):  # CarcaFeatCache
     _fields_ = [("p_c", _fp), ("a_c", _fp), ("state", _fp), ("table", _fp), ("n_rows", C.c_int32), ("ld_p", C.c_int32),
                 ("ld_a", C.c_int32)]
@@ -385,6 +395,8 @@ SIGNATURES = {
     "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
     "carca_sampled_xent_bwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
+    "carca_sampled_bce_fwd": (_i, [C.POINTER(SampledBceDesc), _fp]),
+    "carca_sampled_bce_bwd": (_i, [C.POINTER(SampledBceDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                      _fp]),
 }

@@ -301,3 +301,110 @@ def sampled_softmax_loss(model, profile, pos: Tensor, samples: Tensor, log_q: Te
     if model._composed(profile, [profile]):
         return _sampled_composed_loss(model, profile, pos, samples, log_q)
     return _SampledFn.apply(model, tuple(profile), pos, samples, log_q, *cached_parameters(model))
+
+
+# ---- BCE against K shared negatives, gBCE ------------------------------------------------------
+def _context_rows(model, pos_ctx: Tensor):
+    """C [B L, d] = M c_r, the context's share of e(i, c) = T[i] + M c, as a differentiable function of the embedding's
+    weights (M = W_jq W_f[:, n_attrs:] for AllEmbedding, W_j W_f[:, n_attrs:] for AttrCtxEmbedding), so that the loss's dC
+    reaches them: two row products of autograd._LinearFn, c W_f,ctx^T then W_jq^T, without the biases (they are T's).
+    None for an embedding without a context term.  (Not context_matrix(): that one is cached and detached.)"""
+    from .autograd import _LinearFn
+    from .modules import AllEmbedding, _FeatsEmbedding
+
+    emb = model.embeds
+    n_ctx = pos_ctx.shape[-1]
+    if n_ctx == 0:
+        return None
+    if isinstance(emb, AllEmbedding):
+        w_jq = emb.joint_embed.weight[:, emb.d:]
+    elif isinstance(emb, _FeatsEmbedding) and emb._use_ctx:
+        w_jq = emb.joint_embed.weight
+    else:
+        return None
+    w_f = emb.feats_embed.weight
+    g, F = w_f.shape
+    # the context block of W_f and the context rows, zero-padded to a multiple of 4 columns (the row product's 16-byte
+    # operand rows); the pad is differentiable, so dW_f lands in the block's columns
+    pad = -n_ctx % 4
+    w_c = torch.nn.functional.pad(w_f[:, F - n_ctx:], (0, pad))
+    c = torch.nn.functional.pad(pos_ctx.reshape(-1, n_ctx).to(torch.float32), (0, pad))
+    zero = lambda n: torch.zeros(n, dtype=torch.float32, device=c.device)  # noqa: E731
+    q = _LinearFn.apply(c, w_c, zero(g))
+    return _LinearFn.apply(q, w_jq, zero(emb.d))
+
+
+def _bce_segments(model, profile, pos, pos_ctx, samples):
+    """_sampled_segments with the positives' own context: [(profile), (samples [1, K], zero context), (positives [B, L],
+    pos_ctx)]."""
+    segs, n_items = _sampled_segments(model, profile, pos, samples)
+    tp, a_p, _, tgt = segs[2]
+    segs[2] = (tp, a_p, pos_ctx.to(torch.float32).contiguous(), tgt)
+    return segs, n_items
+
+
+class _SampledBceFn(torch.autograd.Function):
+    """The fused route of the gBCE loss: _SampledFn's, with the rows' context share C as one more differentiable input."""
+
+    @staticmethod
+    def forward(ctx, model, profile, pos, pos_ctx, samples, beta, Cr, *params):
+        segs, n_items = _bce_segments(model, profile, pos, pos_ctx, samples)
+        rows, (es_s, es_p), st = _profile_forward(model, segs)
+        dpi, K = st["dpi"], segs[1][0].shape[1]
+        S, Tp = es_s.view(K, dpi), es_p.view(-1, dpi)
+        pos32, s32 = ops._ids32(pos.reshape(-1)), ops._ids32(samples.reshape(-1))
+        d = model.embeds.d
+        C2 = ops._xent_operand(Cr.detach(), d, "sampled_bce_loss") if Cr is not None else None
+        loss, saved, _ = ops.sampled_bce_fwd(rows, Tp, C2, pos32, S, s32, n_items, beta, d)
+        ctx.model, ctx.params = model, params
+        ctx.st = dict(st, S=S, Tp=Tp, C=C2, sb=(pos32, s32, n_items, beta), saved=saved)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        st, d = ctx.st, ctx.model.embeds.d
+        out = {}
+
+        def loss_bwd():
+            pos32, s32, n_items, beta = st["sb"]
+            dP, dTp, dS, dC = ops.sampled_bce_bwd(st["rows"], st["Tp"], st["C"], pos32, st["S"], s32, n_items, beta,
+                                                  st["saved"], g.detach(), d)
+            out["dC"] = dC
+            return dP, [dS, dTp]
+
+        grads = _profile_backward(ctx.model, ctx.params, st, loss_bwd)
+        ctx.st = None
+        dC = out["dC"][:, :d] if out["dC"] is not None else None
+        return (None, None, None, None, None, None, dC) + grads
+
+
+def _bce_composed_loss(model, profile, pos, pos_ctx, samples, beta, Cr) -> Tensor:
+    segs, n_items = _bce_segments(model, profile, pos, pos_ctx, samples)
+    p_n, (S, Tp) = _composed_rows(model, profile, segs, "sampled_bce_loss")
+    d = model.embeds.d
+    return ops.sampled_bce(p_n.reshape(-1, d), Tp.reshape(-1, d), pos.reshape(-1), S.reshape(-1, d), samples.reshape(-1),
+                           n_items, beta, C=Cr)
+
+
+def sampled_bce_loss(model, profile, pos: Tensor, pos_ctx: Tensor, samples: Tensor, t: float = 0.75) -> Tensor:
+    from .modules import cached_parameters, note_training_forward
+
+    what = "sampled_bce_loss"
+    _check(model, profile, pos, what)
+    ops._need_cuda(samples, pos_ctx)
+    if samples.is_floating_point() or samples.numel() < 1:
+        raise CarcaHipError(f"{what}: samples must be a non-empty integer tensor of item ids")
+    p_c = profile[2]
+    if pos_ctx.dim() != 3 or tuple(pos_ctx.shape[:2]) != tuple(pos.shape) or pos_ctx.shape[2] != p_c.shape[-1]:
+        raise CarcaHipError(f"{what}: pos_ctx must be [B, L, n_ctx] = {tuple(pos.shape) + (p_c.shape[-1],)}, got "
+                            f"{tuple(pos_ctx.shape)}")
+    if pos_ctx.requires_grad:
+        raise CarcaHipError("gradients with respect to the input tensors (ids/attrs/ctx) are not produced")
+    emb = model.embeds
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    beta = ops.sampled_bce_beta(samples.numel(), n_items, t)  # (t outside [0, 1]: ValueError)
+    note_training_forward()  # packed-weight caches: see modules._WEIGHT_EPOCH
+    Cr = _context_rows(model, pos_ctx)
+    if model._composed(profile, [profile]):
+        return _bce_composed_loss(model, profile, pos, pos_ctx, samples, beta, Cr)
+    return _SampledBceFn.apply(model, tuple(profile), pos, pos_ctx, samples, beta, Cr, *cached_parameters(model))

@@ -1,5 +1,6 @@
 // The tile skeleton of the softmax cross-entropy kernels: catalogue_xent.hip (the classes are the whole catalogue,
 // DESIGN.md section 13) and sampled_xent.hip (the classes are K shared samples with the logQ correction, section 14).
+// sampled_bce.hip (a sigmoid loss over K shared samples, section 16) runs on it too, with its own per-logit rule.
 //
 // A workgroup of four waves owns 64 rows of one operand (the "own" tile, staged once in LDS) and streams 64-row tiles of
 // the other through LDS.  Wave w owns own rows 16w .. 16w+15; lane l holds column r16 = l & 15 and the stream rows
@@ -253,12 +254,13 @@ __global__ __launch_bounds__(256) void cx_reduce_kernel(const float* __restrict_
 // ids, bias, lse, grad, per_split); the rest is what the launch sequences need beside them.
 struct XentCall {
   XentTile A;
-  const char* op;       // "catalogue_xent" / "sampled_xent"
+  const char* op;       // "catalogue_xent" / "sampled_xent" / "sampled_bce"
   const char* classes;  // what a class is called in messages
   float* scratch;
   int64_t scratch_floats;
   int splits_n, splits_rows;  // class splits (FWD / DP), row splits (DT)
   int extra_dp;               // dP partials written after the class splits' (sampled: the positive term)
+  int share_partials;         // backward: the class operand's partials reuse the dP partials' words (see XentLayout)
   float* row_loss;
   float* loss;
   float* dP;  // [R, ld_p]
@@ -267,7 +269,9 @@ struct XentCall {
 
 // scratch layout in 4-byte words (mirrored by ops._xent_plan): the row lists, nv, then the forward's (max, sum-exp) per
 // split and valid row, or the backward's dP partials [splits_n + extra_dp][R][ldo] and, with more than one row split,
-// the class operand's partials [splits_rows][n][ldo]
+// the class operand's partials [splits_rows][n][ldo].  The dP partials are summed into dP before the class operand's tile
+// launches (one stream), so with share_partials the second set starts where the first does and the scratch is the larger
+// of the two, not their sum.
 struct XentLayout {
   int64_t ridx, rpos, nv, part, part2, total;
 };
@@ -282,8 +286,10 @@ inline XentLayout xt_layout(const XentCall& C, bool bwd) {
     L.part2 = L.part + cx_r64((int64_t)C.splits_n * R);
     L.total = L.part2 + cx_r64((int64_t)C.splits_n * R);
   } else {
-    L.part2 = L.part + cx_r64((int64_t)(C.splits_n + C.extra_dp) * R * ldo);
-    L.total = L.part2 + (C.splits_rows > 1 ? cx_r64((int64_t)C.splits_rows * C.A.n * ldo) : 0);
+    const int64_t dp = cx_r64((int64_t)(C.splits_n + C.extra_dp) * R * ldo);
+    const int64_t dt = C.splits_rows > 1 ? cx_r64((int64_t)C.splits_rows * C.A.n * ldo) : 0;
+    L.part2 = C.share_partials ? L.part : L.part + dp;
+    L.total = C.share_partials ? L.part + (dp > dt ? dp : dt) : L.part2 + dt;
   }
   return L;
 }

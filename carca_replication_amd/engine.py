@@ -55,8 +55,11 @@ def _row_exchange_len(p_x, o_x, global_batch: Optional[int]) -> Optional[int]:
     return per_rank * (p_x.shape[1] + o_x.shape[1])
 
 
-LOSSES = ("bce", "softmax", "sampled_softmax")
+LOSSES = ("bce", "softmax", "sampled_softmax", "sampled_bce")
+SAMPLED_LOSSES = ("sampled_softmax", "sampled_bce")  # the losses that read a sampler
 SAMPLED_DEFAULT_K = 8192  # samples per step of the default (uniform) proposal
+SAMPLED_BCE_DEFAULT_K = 256  # the same for loss="sampled_bce"
+SAMPLED_BCE_T = 0.75  # gBCE's calibration parameter t (beta = 1 - t (1 - K / (n_items - 1))), the paper's default
 
 
 def train_step(model, optim, batch, sharded: bool = False, global_batch: Optional[int] = None,
@@ -71,6 +74,10 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
     section 14), drawn by the step from `sampler` (sampling.ItemSampler; None = uniform with K = min(8192, n_items - 1));
     the optimizer is told the rows p_x, the positives and the samples, so a touched-row Adam table stays sparse.  Not
     built for sharded steps.
+    "sampled_bce" = the reference's sigmoid objective against K negatives shared by the batch with gBCE's weight on the
+    positive's term (CARCA.sampled_bce_loss with t = SAMPLED_BCE_T), drawn by the step from `sampler`
+    (a uniform sampling.ItemSampler; None = K = min(256, n_items - 1); one built with counts raises ValueError: beta
+    assumes a uniform proposal); rows announced as for "sampled_softmax".  Not built for sharded steps.
 
     With sharded=True the batch holds THIS rank's users; the loss is normalised by the global mask
     count and gradients are summed over ranks, which reproduces the single-process step exactly.
@@ -80,8 +87,10 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
     """
     if loss not in LOSSES:
         raise ValueError(f"train_step: loss must be one of {LOSSES}, got {loss!r}")
-    if sampler is not None and loss != "sampled_softmax":
-        raise ValueError(f'train_step: a sampler is only read by loss="sampled_softmax", got loss={loss!r}')
+    if sampler is not None and loss not in SAMPLED_LOSSES:
+        raise ValueError(f'train_step: a sampler is only read by loss="sampled_softmax" and "sampled_bce", got loss={loss!r}')
+    if loss == "sampled_bce":
+        _check_uniform(sampler, "train_step")
     batch = as_batch7(batch)
     if loss == "softmax":
         if sharded:
@@ -91,6 +100,10 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
         if sharded:
             raise CarcaHipError('train_step: loss="sampled_softmax" is not built for sharded steps')
         return _sampled_softmax_step(model, optim, batch, sampler)
+    if loss == "sampled_bce":
+        if sharded:
+            raise CarcaHipError('train_step: loss="sampled_bce" is not built for sharded steps')
+        return _sampled_bce_step(model, optim, batch, sampler)
     p_x, o_x = batch[0], batch[3]
     gathered = None
     if not (sharded and cdist._active()):
@@ -190,17 +203,51 @@ def _softmax_step(model, optim, batch) -> torch.Tensor:
 _SAMPLERS: dict = {}
 
 
-def default_sampler(model, device) -> "ItemSampler":
-    """The uniform proposal over the model's catalogue with K = min(SAMPLED_DEFAULT_K, n_items - 1) (one per catalogue
-    size and device)."""
+def default_sampler(model, device, k: int = SAMPLED_DEFAULT_K) -> "ItemSampler":
+    """The uniform proposal over the model's catalogue with K = min(k, n_items - 1) (one per catalogue size, device and
+    K; k: SAMPLED_DEFAULT_K for the sampled softmax, SAMPLED_BCE_DEFAULT_K for the sampled BCE)."""
     from .sampling import ItemSampler
 
     emb = model.embeds
     n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
-    key = (n_items, str(device))
+    key = (n_items, str(device), int(k))
     if key not in _SAMPLERS:
-        _SAMPLERS[key] = ItemSampler(n_items, min(SAMPLED_DEFAULT_K, n_items - 1), device=device)
+        _SAMPLERS[key] = ItemSampler(n_items, min(int(k), n_items - 1), device=device)
     return _SAMPLERS[key]
+
+
+def _check_uniform(sampler, who: str) -> None:
+    """loss="sampled_bce": gBCE's beta is derived for a uniform proposal; a sampler built with counts is refused."""
+    if sampler is not None and getattr(sampler, "_cdf", None) is not None:
+        raise ValueError(f'{who}: loss="sampled_bce" needs a uniform sampler (ItemSampler without counts): the weight of '
+                         "the positive's term assumes the sampling rate K / (n_items - 1)")
+
+
+def _mark_sampled_rows(model, optim, p_x, pos, samples) -> None:
+    """Tell a touched-row optimizer the item rows a sampled step's gradient lives in: the profile's, the positives' and
+    the samples' (ids outside [1, n_items) as the loss embeds them: row 0)."""
+    tables = _sparse_tables(model, p_x, pos)
+    if tables and hasattr(optim, "mark_rows"):
+        n_items = model.embeds.items_embed.num_embeddings
+        s = samples.reshape(-1)
+        s = torch.where((s >= 1) & (s < n_items), s, torch.zeros_like(s))
+        for w, ids in tables.items():
+            optim.mark_rows(w, torch.cat([ids, s.to(ids.dtype)]))
+
+
+def _sampled_bce_step(model, optim, batch, sampler) -> torch.Tensor:
+    p_x, p_a, p_c, o_x, _, o_c = batch[:6]
+    half = o_x.shape[1] // 2
+    pos, pos_ctx = o_x[:, :half], o_c[:, :half]  # train.py:86-88: the positive half, with its context
+    if sampler is None:
+        sampler = default_sampler(model, p_x.device, SAMPLED_BCE_DEFAULT_K)
+    samples = sampler.sample()
+    optim.zero_grad(set_to_none=True)
+    loss = model.sampled_bce_loss((p_x, p_a, p_c), pos, pos_ctx, samples, t=SAMPLED_BCE_T)
+    loss.backward()
+    _mark_sampled_rows(model, optim, p_x, pos, samples)
+    optim.step()
+    return loss.detach()
 
 
 def _sampled_softmax_step(model, optim, batch, sampler) -> torch.Tensor:
@@ -212,14 +259,7 @@ def _sampled_softmax_step(model, optim, batch, sampler) -> torch.Tensor:
     optim.zero_grad(set_to_none=True)
     loss = model.sampled_softmax_loss((p_x, p_a, p_c), pos, samples, sampler.log_q())
     loss.backward()
-    # the item table's gradient lives in the rows of the profile, the positives and the samples
-    tables = _sparse_tables(model, p_x, pos)
-    if tables and hasattr(optim, "mark_rows"):
-        n_items = model.embeds.items_embed.num_embeddings
-        s = samples.reshape(-1)
-        s = torch.where((s >= 1) & (s < n_items), s, torch.zeros_like(s))  # (as the loss embeds them)
-        for w, ids in tables.items():
-            optim.mark_rows(w, torch.cat([ids, s.to(ids.dtype)]))
+    _mark_sampled_rows(model, optim, p_x, pos, samples)
     optim.step()
     return loss.detach()
 

@@ -1305,6 +1305,19 @@ class CARCA(_PackedModule, Model):
 
         return sampled_softmax_loss(self, profile, pos, samples, log_q)
 
+    def sampled_bce_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor, pos_ctx: Tensor,
+                         samples: Tensor, t: float = 0.75) -> Tensor:
+        """Binary cross-entropy against K negatives shared by every slot, gBCE (Petrov & Macdonald, gSASRec; DESIGN.md
+        section 16): pos = o_x[:, :L], pos_ctx = o_c[:, :L], `samples` K ids drawn uniformly.  Each valid slot pays
+        beta softplus(-z+) for its positive (embedded with pos_ctx) and softplus(z_k) for every sample that is an item and not
+        its positive, the sample embedded with the SLOT's context as the reference's negatives are (data.py); scalar mean
+        over the valid slots.  beta = 1 - t (1 - K / (n_items - 1)): t = 0 is plain BCE over K negatives, t = 1 fully
+        calibrated; t outside [0, 1] raises ValueError.  Same decoders, embeddings, dropout and errors as
+        catalogue_softmax_loss."""
+        from .catalogue_xent import sampled_bce_loss
+
+        return sampled_bce_loss(self, profile, pos, pos_ctx, samples, t)
+
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items; DESIGN.md 10, 11) -
     def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
                   exclude="profile", candidates=None) -> Tuple[Tensor, Tensor]:

@@ -1352,13 +1352,15 @@ CX_MAX_SPLITS = 256
 CX_WAVES_PER_CU = 4  # the split counts aim at this many workgroups per CU
 
 
-def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: int) -> Tuple[int, int, int, int, int]:
+def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: int,
+               share_partials: bool = False) -> Tuple[int, int, int, int, int]:
     """(class splits, classes per split, row splits, forward scratch, backward scratch) of either loss, the layout
     csrc/xent_tile.h checks.  The classes are split so that the forward's and dP's (row block x class split) grid has about
     CX_WAVES_PER_CU workgroups per CU, the rows of the class gradient's (class block x row split) grid likewise.  Scratch in
     4-byte words: 2 ceil64(R) + 64 of row lists, then the forward's (max, sum-exp) partials, or the backward's dP partials
     [class splits + extra_dp_partials, R, ld] and, with more than one row split, the class gradient's
-    [row splits, n_classes, ld], ld = round_up(d, 4)."""
+    [row splits, n_classes, ld], ld = round_up(d, 4); with share_partials the two sets share their words (the larger
+    of the two, not the sum: XentCall::share_partials)."""
     r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
     ldo = (d + 3) // 4 * 4
     target = CX_WAVES_PER_CU * max(1, int(n_cus))
@@ -1370,7 +1372,8 @@ def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: in
     s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_class_blocks)))
     head = 2 * r64(R) + 64
     fwd = head + 2 * r64(s_c * R)
-    bwd = head + r64((s_c + extra_dp_partials) * R * ldo) + (r64(s_r * n_classes * ldo) if s_r > 1 else 0)
+    dp, dt = r64((s_c + extra_dp_partials) * R * ldo), (r64(s_r * n_classes * ldo) if s_r > 1 else 0)
+    bwd = head + (max(dp, dt) if share_partials else dp + dt)
     return s_c, per, s_r, fwd, bwd
 
 
@@ -1612,3 +1615,145 @@ def sampled_xent(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, l
     _need_cuda(P, Tp, pos, S, s_ids, log_q)
     pos32, s32, bp, bs = sampled_xent_corrections(pos, s_ids, log_q)
     return _SampledXentFn.apply(P, Tp, S, pos32, s32, bp, bs, log_q.numel())
+
+
+# --------------------------------------------------------------------------------------------------
+# binary cross-entropy against K shared negatives, gBCE (carca_sampled_bce_fwd / _bwd)
+# --------------------------------------------------------------------------------------------------
+def sampled_bce_plan(R: int, K: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_sampled_bce_fwd / _bwd (pure: no device): _xent_plan with the K samples as the classes
+    and one more dP partial, as sampled_xent_plan.  Returns the split counts and the scratch each call needs, in 4-byte
+    words: the row lists, then the forward's (sum softplus, sum sigmoid) partials, or the backward's dP partials
+    [splits_samples + 1, R, ld] (the last: the positive's and the context's terms) or, where larger, the dS partials
+    [splits_rows, K, ld] of more than one row split, in the same words (dP is complete before dS starts),
+    ld = round_up(d, 4)."""
+    if R < 1 or K < 1 or d < 1:
+        raise CarcaHipError("sampled_bce_plan: R, K and d must be positive")
+    s_s, per, s_r, fwd, bwd = _xent_plan(R, K, d, n_cus, 1, share_partials=True)
+    return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+
+
+def sampled_bce_beta(K: int, n_items: int, t: float) -> float:
+    """gBCE's weight of the positive's term (Petrov & Macdonald, gSASRec): beta = 1 - t (1 - alpha) with the sampling
+    rate alpha = K / (n_items - 1); t = 0 is plain BCE over K negatives, t = 1 fully calibrated."""
+    if not 0.0 <= float(t) <= 1.0:
+        raise ValueError(f"sampled_bce: t must lie in [0, 1], got {t}")
+    if K < 1 or n_items < 2:
+        raise ValueError(f"sampled_bce: K >= 1 and n_items >= 2 are needed, got K = {K}, n_items = {n_items}")
+    alpha = min(1.0, K / (n_items - 1))
+    return 1.0 - float(t) * (1.0 - alpha)
+
+
+def _sb_desc(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int, beta: float,
+             d: int, scratch_key: str, keep: list):
+    R, K = P.shape[0], S.shape[0]
+    if pos.numel() != R or s_ids.numel() != K:
+        raise CarcaHipError(f"sampled_bce: pos must have {R} entries and s_ids {K}, got {pos.numel()} and {s_ids.numel()}")
+    pos, s_ids = _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1))
+    keep += [pos, s_ids]
+    D = _lib.SampledBceDesc()
+    D.R, D.K, D.n_items, D.d, D.beta = R, K, int(n_items), d, float(beta)
+    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
+    if Cr is not None:
+        D.C, D.ld_c = Cr.data_ptr(), Cr.stride(0)
+    D.pos, D.s_ids = pos.data_ptr(), s_ids.data_ptr()
+    plan = sampled_bce_plan(R, K, d, num_cus())
+    return _xent_splits(D, plan, ("splits_samples", "samples_per_split", "splits_rows"), scratch_key, P.device, keep)
+
+
+def sampled_bce_fwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int,
+                    beta: float, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Mean BCE against K shared negatives (include/carca_hip.h: carca_sampled_bce_fwd) of rows P [R, ld_p] with positives
+    Tp [R, ld_tp], the shared samples S [K, ld_s] and the rows' context share Cr [R, ld_c] or None (first d columns, unit
+    column stride; ld_p, ld_tp, ld_s multiples of 4): pos [R] and s_ids [K] int32, beta the positive's weight.  Returns
+    (loss [1], saved [3, R] = (zpos, br, gsum) for the backward, row_loss [R]); no host wait."""
+    _need_cuda(P, Tp, pos, S, s_ids, *(() if Cr is None else (Cr,)))
+    keep: list = []
+    D = _sb_desc(P, Tp, Cr, pos, S, s_ids, n_items, beta, d, "scratch_fwd", keep)
+    saved = torch.empty(3, P.shape[0], dtype=torch.float32, device=P.device)
+    row_loss = torch.empty(P.shape[0], dtype=torch.float32, device=P.device)
+    loss = torch.empty(1, dtype=torch.float32, device=P.device)
+    D.zpos, D.br, D.gsum = saved[0].data_ptr(), saved[1].data_ptr(), saved[2].data_ptr()
+    D.row_loss, D.loss = row_loss.data_ptr(), loss.data_ptr()
+    _lib.check(_lib.load().carca_sampled_bce_fwd(C.byref(D), _stream()), "sampled_bce_fwd")
+    return loss, saved, row_loss
+
+
+def sampled_bce_bwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int,
+                    beta: float, saved: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
+    """(dP [R, ld_p], dTp [R, ld_tp], dS [K, ld_s], dC [R, ld_c] or None) of sampled_bce_fwd's loss scaled by grad [1]
+    (device), from the forward's saved [3, R]; zeros past d."""
+    _need_cuda(P, Tp, pos, S, s_ids, saved, grad, *(() if Cr is None else (Cr,)))
+    keep: list = []
+    D = _sb_desc(P, Tp, Cr, pos, S, s_ids, n_items, beta, d, "scratch_bwd", keep)
+    g = _f32(grad.reshape(1))
+    R = P.shape[0]
+    if saved.shape != (3, R) or saved.dtype != torch.float32 or not saved.is_contiguous():
+        raise CarcaHipError(f"sampled_bce_bwd: saved must be the forward's contiguous fp32 [3, {R}], got {tuple(saved.shape)}")
+    row_loss = torch.empty(R, dtype=torch.float32, device=P.device)  # (the descriptor's forward output: not read here)
+    dP = torch.empty(R, P.stride(0), dtype=torch.float32, device=P.device)
+    dTp = torch.empty(R, Tp.stride(0), dtype=torch.float32, device=P.device)
+    dS = torch.empty(S.shape[0], S.stride(0), dtype=torch.float32, device=P.device)
+    dC = torch.empty(R, Cr.stride(0), dtype=torch.float32, device=P.device) if Cr is not None else None
+    D.zpos, D.br, D.gsum = saved[0].data_ptr(), saved[1].data_ptr(), saved[2].data_ptr()
+    D.row_loss, D.grad = row_loss.data_ptr(), g.data_ptr()
+    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
+    if dC is not None:
+        D.dC = dC.data_ptr()
+    _lib.check(_lib.load().carca_sampled_bce_bwd(C.byref(D), _stream()), "sampled_bce_bwd")
+    return dP, dTp, dS, dC
+
+
+class _SampledBceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, Tp, S, Cr, pos32, s32, n_items, beta):
+        d = P.shape[1]
+        P2, Tp2, S2 = (_xent_operand(x.detach(), d, "sampled_bce") for x in (P, Tp, S))
+        C2 = _xent_operand(Cr.detach(), d, "sampled_bce") if Cr is not None else None
+        loss, saved, _ = sampled_bce_fwd(P2, Tp2, C2, pos32, S2, s32, n_items, beta, d)
+        ctx.save_for_backward(P2, Tp2, S2, pos32, s32, saved, *(() if C2 is None else (C2,)))
+        ctx.d, ctx.n_items, ctx.beta = d, n_items, beta
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        P2, Tp2, S2, pos32, s32, saved, *rest = ctx.saved_tensors
+        C2 = rest[0] if rest else None
+        d = ctx.d
+        dP, dTp, dS, dC = sampled_bce_bwd(P2, Tp2, C2, pos32, S2, s32, ctx.n_items, ctx.beta, saved, g.detach(), d)
+        return dP[:, :d], dTp[:, :d], dS[:, :d], (dC[:, :d] if dC is not None else None), None, None, None, None
+
+
+def sampled_bce(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int, beta: float,
+                C: Optional[Tensor] = None) -> Tensor:  # noqa: N803
+    """Mean binary cross-entropy against K negatives shared by the batch (gBCE), differentiable in P, Tp, S and C
+    (DESIGN.md section 16):
+
+        sum over valid r of ( beta softplus(-P[r] . Tp[r]) + sum_{k in N_r} softplus(P[r] . S[k] + P[r] . C[r]) ) / n_valid
+        N_r = {k : s_k in [1, n_items), s_k != pos[r]}
+
+    P [R, d], Tp [R, d] (the rows of the positives, their context included), S [K, d] (the rows of the K samples, zero
+    context) and C [R, d] (the rows' context share M c_r; None: no context term) fp32; pos [R], s_ids [K] integer; beta in
+    [0, 1] the positive's weight (sampled_bce_beta).  Row r is valid iff pos[r] lies in [1, n_items); a sample id outside
+    [1, n_items) contributes nothing; a batch without a valid row gives 0.  Fused HIP kernels: no [R, K] buffer."""
+    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
+        raise CarcaHipError(f"sampled_bce: expected P [R, d], Tp [R, d], S [K, d]; got {tuple(P.shape)}, "
+                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
+    if C is not None and tuple(C.shape) != tuple(P.shape):
+        raise CarcaHipError(f"sampled_bce: C must have the shape of P {tuple(P.shape)}, got {tuple(C.shape)}")
+    if pos.numel() != P.shape[0] or s_ids.numel() != S.shape[0]:
+        raise CarcaHipError(f"sampled_bce: pos must have R = {P.shape[0]} entries and s_ids K = {S.shape[0]}; got "
+                            f"{pos.numel()} and {s_ids.numel()}")
+    if S.shape[0] < 1:
+        raise CarcaHipError("sampled_bce: at least one sample is needed")
+    if pos.is_floating_point() or s_ids.is_floating_point():
+        raise CarcaHipError("sampled_bce: pos and s_ids must be integer tensors")
+    ops_f = (P, Tp, S) + (() if C is None else (C,))
+    if any(x.dtype != torch.float32 for x in ops_f):
+        raise CarcaHipError(f"sampled_bce: P, Tp, S and C must be float32, got {', '.join(str(x.dtype) for x in ops_f)}")
+    if int(n_items) < 2:
+        raise CarcaHipError(f"sampled_bce: n_items must be at least 2, got {n_items}")
+    if not 0.0 <= float(beta) <= 1.0:
+        raise CarcaHipError(f"sampled_bce: beta must lie in [0, 1], got {beta}")
+    _need_cuda(*ops_f, pos, s_ids)
+    return _SampledBceFn.apply(P, Tp, S, C, _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1)), int(n_items), float(beta))

@@ -236,16 +236,20 @@ def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_l
       restored and the epoch count continues after the stored one, with the stored best NDCG as the bar to beat;
     resume_trusted: the file named by `resume` may be a whole-module pickle as the reference writes them (train.py:124):
       load_checkpoint(allow_pickle=True) -- unpickling executes code from the file, so only for files the caller trusts;
-    loss: "bce" (the reference's objective), "softmax" (full-catalogue softmax cross-entropy, engine.train_step) or
-      "sampled_softmax" (softmax over K shared samples with the logQ correction); the softmax losses not with
-      graphed=True.  Validation and test stay the reference's sampled HR / NDCG either way;
-    sampler: loss="sampled_softmax" only: the proposal the samples are drawn from (sampling.ItemSampler; None = uniform,
-      K = min(8192, n_items - 1))."""
+    loss: "bce" (the reference's objective), "softmax" (full-catalogue softmax cross-entropy, engine.train_step),
+      "sampled_softmax" (softmax over K shared samples with the logQ correction) or "sampled_bce" (the sigmoid objective
+      against K shared negatives, gBCE); only "bce" with graphed=True.  Validation and test stay
+      the reference's sampled HR / NDCG either way;
+    sampler: the sampled losses only: the proposal the samples are drawn from (sampling.ItemSampler; None = uniform,
+      K = min(8192, n_items - 1) for "sampled_softmax", min(256, n_items - 1) for "sampled_bce", which takes a uniform
+      sampler only)."""
     objective = loss  # (`loss` names the validation loss below, as in the reference's loop)
     if objective not in engine.LOSSES:
         raise ValueError(f"train: loss must be one of {engine.LOSSES}, got {objective!r}")
-    if sampler is not None and objective != "sampled_softmax":
-        raise ValueError(f'train: a sampler is only read by loss="sampled_softmax", got loss={objective!r}')
+    if sampler is not None and objective not in engine.SAMPLED_LOSSES:
+        raise ValueError(f'train: a sampler is only read by loss="sampled_softmax" and "sampled_bce", got loss={objective!r}')
+    if objective == "sampled_bce":
+        engine._check_uniform(sampler, "train")
     if graphed and objective != "bce":
         raise CarcaHipError(f'train: graphed=True captures the BCE step only; loss="{objective}" runs eagerly '
                            '(graphed=False)')

@@ -1072,6 +1072,57 @@ typedef struct CarcaSampledXentDesc {
 int carca_sampled_xent_fwd(const CarcaSampledXentDesc* desc, void* stream);
 int carca_sampled_xent_bwd(const CarcaSampledXentDesc* desc, void* stream);
 
+/* ---- binary cross-entropy against K shared negatives (gBCE) for the dot decoders -------------
+ * P [R, ld_p] profile rows, Tp [R, ld_tp] the rows of their positives (context included), S [K, ld_s] the rows of K
+ * samples shared by every row (zero context), C [R, ld_c] the rows' context share M c_r, or NULL (d features; ld_p, ld_tp,
+ * ld_s multiples of 4, ld_c >= d; P and S 16-byte aligned), pos [R] and s_ids [K] int32.  Row r is VALID iff pos[r] lies
+ * in [1, n_items).  Sample k is a negative of row r iff s_ids[k] lies in [1, n_items) and differs from pos[r] (accidental
+ * hits removed; duplicates each count).  With sp = softplus, z(r, +) = P[r] . Tp[r] and z(r, k) = P[r] . S[k] + br[r]:
+ *   carca_sampled_bce_fwd: zpos[r] = z(r, +), br[r] = P[r] . C[r] (0 without C), gsum[r] = G_r = sum over the negatives k
+ *     of r of sigmoid(z(r, k)), row_loss[r] = beta sp(-zpos[r]) + sum over the negatives of sp(z(r, k)) (all 0 for a row
+ *     that is not valid), loss[0] = sum of row_loss / n_valid (0 when no row is valid);
+ *   carca_sampled_bce_bwd: with zpos, br and gsum from the forward and the upstream scale grad[0],
+ *     G[r, k] = sigmoid(z(r, k)) on the negatives (else 0), gp = -beta sigmoid(-zpos[r]):
+ *     dP  = grad / n_valid (G S + gp Tp + G_r C), dTp = grad / n_valid gp P, dC = grad / n_valid G_r P (0 for rows that
+ *     are not valid), dS = grad / n_valid G^T P (0 for samples that are no class); every output 0 past d.
+ * The softplus is max(x, 0) + log(1 + exp(-|x|)): no overflow.  Products in exact-fp32 MFMA; the logit tiles are
+ * recomputed, never stored.  Splits and scratch as carca_sampled_xent_* (ops.sampled_bce_plan gives the sizes): 2
+ * ceil64(R) + 64 words of row lists, then the forward's 2 ceil64(splits_samples R) (sum sp, sum sigmoid) partials, or the
+ * backward's ceil64((splits_samples + 1) R ld) dP partials or, where larger (splits_rows > 1), ceil64(splits_rows K ld)
+ * dS partials in the same words (dP is complete before dS starts), ld = round_up(d, 4).  No float atomics: the same
+ * call gives the same bits.  CARCA_ERR_UNSUPPORTED: d > 256.
+ * CARCA_ERR_BADARG: null pointers, strides, beta outside [0, 1], split counts outside 1..256, samples_per_split *
+ * splits_samples < K, scratch too small, C without dC in the backward. */
+typedef struct CarcaSampledBceDesc {
+  int R, K, n_items, d;
+  const float* P;
+  int ld_p;
+  const float* Tp;
+  int ld_tp;
+  const float* C;        /* [R, ld_c] or NULL */
+  int ld_c;
+  const int32_t* pos;    /* [R] */
+  const float* S;
+  int ld_s;
+  const int32_t* s_ids;  /* [K] */
+  float beta;            /* weight of the positive's term */
+  int splits_samples, samples_per_split, splits_rows;
+  float* scratch;
+  int64_t scratch_floats;
+  float* zpos;       /* [R]: forward output, backward input */
+  float* br;         /* [R]: forward output, backward input */
+  float* gsum;       /* [R]: forward output, backward input */
+  float* row_loss;   /* [R] forward */
+  float* loss;       /* [1] forward */
+  const float* grad; /* [1] backward: upstream scale of loss */
+  float* dP;         /* [R, ld_p] backward */
+  float* dTp;        /* [R, ld_tp] backward */
+  float* dC;         /* [R, ld_c] backward (with C) */
+  float* dS;         /* [K, ld_s] backward */
+} CarcaSampledBceDesc;
+int carca_sampled_bce_fwd(const CarcaSampledBceDesc* desc, void* stream);
+int carca_sampled_bce_bwd(const CarcaSampledBceDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
