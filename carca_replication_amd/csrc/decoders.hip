@@ -15,13 +15,19 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
                                                             int ldy, int rows, int d, const float* __restrict__ w,
                                                             const float* __restrict__ b) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float fd = (float)d;
   for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
     const float* xr = x + (size_t)row * ldx;
-    float v0 = lane < d ? xr[lane] : 0.f, v1 = lane + 64 < d ? xr[lane + 64] : 0.f;
-    row_layernorm(v0, v1, lane, d, w, b);
+    const float v0 = lane < d ? xr[lane] : 0.f, v1 = lane + 64 < d ? xr[lane + 64] : 0.f;
+    // The mean is a true division, not a product with a rounded 1 / d: one ulp of the mean is multiplied by rstd, up to
+    // 316 on a row of (nearly) equal entries -- 5e-5 of output where the exact answer is the bias.
+    const float mean = wave_sum(v0 + v1) / fd;
+    const float d0 = lane < d ? v0 - mean : 0.f;
+    const float d1 = lane + 64 < d ? v1 - mean : 0.f;
+    const float rstd = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) / fd + 1e-5f);
     float* yr = y + (size_t)row * ldy;
-    if (lane < ldy) yr[lane] = v0;
-    if (lane + 64 < ldy) yr[lane + 64] = v1;
+    if (lane < ldy) yr[lane] = lane < d ? d0 * rstd * w[lane] + b[lane] : 0.f;
+    if (lane + 64 < ldy) yr[lane + 64] = lane + 64 < d ? d1 * rstd * w[lane + 64] + b[lane + 64] : 0.f;
   }
 }
 
@@ -33,7 +39,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __
                                                                  int ldy, int rows, int d, const float* __restrict__ w,
                                                                  const float* __restrict__ b) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float inv_d = 1.0f / (float)d;
+  const float fd = (float)d;
   for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
     const float* xr = x + (size_t)row * ldx;
     float v[LN_WIDE_MAX];
@@ -44,7 +50,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __
       v[j] = c < d ? xr[c] : 0.f;
       s += v[j];
     }
-    const float mean = wave_sum(s) * inv_d;
+    const float mean = wave_sum(s) / fd;  // (divided, as in layernorm_fwd_kernel)
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < LN_WIDE_MAX; ++j) {
@@ -52,7 +58,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __
       v[j] = c < d ? v[j] - mean : 0.f;
       q += v[j] * v[j];
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / fd + 1e-5f);
     float* yr = y + (size_t)row * ldy;
 #pragma unroll
     for (int j = 0; j < LN_WIDE_MAX; ++j) {
@@ -80,7 +86,8 @@ __global__ __launch_bounds__(256) void dot_score_fwd_kernel(const float* __restr
   }
 }
 
-// dl = dy * dlink/ds; d_o[row] = dl * p_row; d_p[p_row] += dl * o[row]
+// dl = dy * dlink/ds; d_o[row] = dl * p_row; d_p[p_row] += dl * o[row]  (slot-wise: one target per profile row.  Last-slot
+// scoring has T targets per profile row; their sum is dot_score_bwd_last_dp_kernel's.)
 __global__ __launch_bounds__(256) void dot_score_bwd_kernel(const float* __restrict__ p, int ldp,
                                                             const float* __restrict__ o, int ldo,
                                                             const float* __restrict__ y, const float* __restrict__ dy,
@@ -101,13 +108,31 @@ __global__ __launch_bounds__(256) void dot_score_bwd_kernel(const float* __restr
     for (int h = 0; h < 2; ++h) {
       const int c = lane + 64 * h;
       if (c < ld_do) dor[c] = c < d ? dl * pr[c] : 0.f;
-      if (c < d) {
-        if (slotwise)
-          dpr[c] += dl * orow[c];  // one writer per element and launch; groups are separate, stream-ordered launches
-        else
-          atomicAdd(&dpr[c], dl * orow[c]);
-      }
+      if (c < d && slotwise) dpr[c] += dl * orow[c];  // one writer per element and launch; groups are separate, stream-ordered launches
     }
+  }
+}
+
+// Last-slot scoring: d_p[b][L-1] += sum_t dl[b][t] o[b][t].  One wave per user sums its T targets in registers and adds
+// the sum once: T atomics per element would each round at the size of what d_p already holds, in arrival order.
+__global__ __launch_bounds__(256) void dot_score_bwd_last_dp_kernel(const float* __restrict__ o, int ldo,
+                                                                    const float* __restrict__ y,
+                                                                    const float* __restrict__ dy, float* __restrict__ dp,
+                                                                    int ld_dp, int B, int L, int T, int d, int link) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int t = 0; t < T; ++t) {
+      const size_t row = (size_t)b * T + t;
+      const float yy = y[row];
+      const float dl = dy[row] * (link == 0 ? yy * (1.0f - yy) : 0.5f);
+      const float* orow = o + row * ldo;
+      if (lane < d) a0 += dl * orow[lane];
+      if (lane + 64 < d) a1 += dl * orow[lane + 64];
+    }
+    float* dpr = dp + ((size_t)b * L + L - 1) * ld_dp;
+    if (lane < d) dpr[lane] += a0;
+    if (lane + 64 < d) dpr[lane + 64] += a1;
   }
 }
 
@@ -131,10 +156,10 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict
   for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
     const float* xr = x + (size_t)row * ldx;
     const float v0 = lane < d ? xr[lane] : 0.f, v1 = lane + 64 < d ? xr[lane + 64] : 0.f;
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(v0 * v0 + v1 * v1)), 1e-12f);
+    const float den = fmaxf(sqrtf(wave_sum(v0 * v0 + v1 * v1)), 1e-12f);  // (divided by: x / |x| is exactly +-1 at d = 1)
     float* yr = y + (size_t)row * ldy;
-    if (lane < ldy) yr[lane] = v0 * inv;
-    if (lane + 64 < ldy) yr[lane + 64] = v1 * inv;
+    if (lane < ldy) yr[lane] = v0 / den;
+    if (lane + 64 < ldy) yr[lane + 64] = v1 / den;
   }
 }
 // dx = (dy - y (y . dy)) / max(||x||, 1e-12), y = normalize(x)   (rows with ||x|| < 1e-12: dx = dy / 1e-12 like autograd)
@@ -149,12 +174,12 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
     const float g0 = lane < d ? gr[lane] : 0.f, g1 = lane + 64 < d ? gr[lane + 64] : 0.f;
     const float nrm = sqrtf(wave_sum(v0 * v0 + v1 * v1));
     const bool tiny = nrm < 1e-12f;
-    const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-    const float y0 = v0 * inv, y1 = v1 * inv;
+    const float den = fmaxf(nrm, 1e-12f);
+    const float y0 = v0 / den, y1 = v1 / den;  // (as the forward: at d = 1 the exact gradient 0 comes out as 0)
     const float dot = tiny ? 0.f : wave_sum(y0 * g0 + y1 * g1);
     float* outr = dx + (size_t)row * ld_dx;
-    if (lane < ld_dx) outr[lane] = lane < d ? (g0 - y0 * dot) * inv : 0.f;
-    if (lane + 64 < ld_dx) outr[lane + 64] = lane + 64 < d ? (g1 - y1 * dot) * inv : 0.f;
+    if (lane < ld_dx) outr[lane] = lane < d ? (g0 - y0 * dot) / den : 0.f;
+    if (lane + 64 < ld_dx) outr[lane + 64] = lane + 64 < d ? (g1 - y1 * dot) / den : 0.f;
   }
 }
 
@@ -427,6 +452,11 @@ extern "C" int carca_dot_score_bwd(const float* p, int ldp, const float* o, int 
   hipLaunchKernelGGL(dot_score_bwd_kernel, dim3(row_blocks(B * T)), dim3(256), 0, (hipStream_t)stream_, p, ldp, o, ldo, y,
                      dy, dp, ld_dp, d_o, ld_do, B, L, T, d, slotwise, link);
   CARCA_LAUNCH_CHECK();
+  if (!slotwise) {
+    hipLaunchKernelGGL(dot_score_bwd_last_dp_kernel, dim3(row_blocks(B)), dim3(256), 0, (hipStream_t)stream_, o, ldo, y, dy,
+                       dp, ld_dp, B, L, T, d, link);
+    CARCA_LAUNCH_CHECK();
+  }
   return CARCA_OK;
 }
 

@@ -949,15 +949,29 @@ def dot_score_bwd(p: Tensor, o: Tensor, y: Tensor, dy: Tensor, dp: Tensor, B: in
     return d_o
 
 
+def _rows_view(t: Tensor) -> Tuple[Tensor, int]:
+    """[B, T, d] fp32 -> (a tensor whose B * T rows lie one constant stride apart, that stride).  Dense tensors and column
+    slices of a wider [B, T, w] buffer (q / k / v cut from one fused projection) are read in place; any other layout is
+    copied."""
+    if t.dtype != torch.float32:
+        raise CarcaHipError(f"expected float32, got {t.dtype}")
+    if t.dim() == 3 and t.stride(2) == 1 and t.stride(1) >= t.shape[2] and (t.shape[0] == 1 or
+                                                                            t.stride(0) == t.shape[1] * t.stride(1)):
+        return t, t.stride(1)
+    t = t.contiguous()
+    return t, t.shape[-1]
+
+
 def add_positions(x: Tensor, pos: Tensor) -> Tensor:
     """Encoding.forward (carca.py:25-31, 54-60): x [B, T, d] + pos [T, d]."""
     _need_cuda(x, pos)
-    x, pos = _f32(x), _f32(pos.detach()).contiguous()
-    if x.dim() != 3 or x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1) or pos.shape != (x.shape[1], x.shape[2]):
-        raise CarcaHipError("add_positions: x must be [B, T, d] with dense rows and pos [T, d]")
+    pos = _f32(pos.detach())
+    if x.dim() != 3 or pos.shape != (x.shape[1], x.shape[2]):
+        raise CarcaHipError("add_positions: x must be [B, T, d] and pos [T, d]")
+    x, ldx = _rows_view(x)
     B, T, d = x.shape
     out = torch.empty(B, T, d, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().carca_add_positions(x.data_ptr(), x.stride(1), pos.data_ptr(), out.data_ptr(), d, B, T, d,
+    _lib.check(_lib.load().carca_add_positions(x.data_ptr(), ldx, pos.data_ptr(), out.data_ptr(), d, B, T, d,
                                                _stream()), "add_positions")
     return out
 
@@ -970,21 +984,21 @@ def mha_core(q: Tensor, k: Tensor, v: Tensor, q_ids: Tensor, k_ids: Tensor, H: i
     _need_cuda(q, k, v, q_ids, k_ids)
     B, Tq, d = q.shape
     Tk = k.shape[1]
-    q2, k2, v2 = (_f32(t).reshape(-1, d) for t in (q, k, v))
-    if k2.stride(0) != v2.stride(0):
-        raise CarcaHipError("mha_core: k and v must share their row stride")
+    (q2, ldq), (k2, ldk), (v2, ldv) = (_rows_view(t) for t in (q, k, v))
+    if ldk != ldv:
+        k2, v2, ldk = k2.contiguous(), v2.contiguous(), d
     qi, ki = _ids32(q_ids.reshape(-1)), _ids32(k_ids.reshape(-1))
     out = torch.empty(B, Tq, d, dtype=torch.float32, device=q.device)
     w = torch.empty(H * B, Tq, Tk, dtype=torch.float32, device=q.device) if want_w else None
     if drop is not None and drop[0] > 0:
         keep = torch.empty(B, H, Tq, Tk, dtype=torch.uint8, device=q.device)
         ds = _drop_struct(*drop)
-        _lib.check(_lib.load().carca_mha_core_drop(q2.data_ptr(), q2.stride(0), k2.data_ptr(), v2.data_ptr(), k2.stride(0),
+        _lib.check(_lib.load().carca_mha_core_drop(q2.data_ptr(), ldq, k2.data_ptr(), v2.data_ptr(), ldk,
                                                    qi.data_ptr(), ki.data_ptr(), B, Tq, Tk, d, H, int(causal is not None),
                                                    int(causal or 0), out.data_ptr(), d, _ptr(w), C.byref(ds),
                                                    keep.data_ptr(), _stream()), "mha_core")
         return out, w, keep
-    _lib.check(_lib.load().carca_mha_core(q2.data_ptr(), q2.stride(0), k2.data_ptr(), v2.data_ptr(), k2.stride(0),
+    _lib.check(_lib.load().carca_mha_core(q2.data_ptr(), ldq, k2.data_ptr(), v2.data_ptr(), ldk,
                                           qi.data_ptr(), ki.data_ptr(), B, Tq, Tk, d, H, int(causal is not None),
                                           int(causal or 0), out.data_ptr(), d, _ptr(w), _stream()), "mha_core")
     return out, w
