@@ -19,7 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h"]
 
@@ -299,6 +299,13 @@ class SampledBceDesc(C.Structure):
                 ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dTp", _fp), ("dC", _fp), ("dS", _fp)]
 
 
+class SimilarDesc(C.Structure):
+    """CarcaSimilarDesc (carca_similar_items)."""
+    _fields_ = [(n, C.c_int32) for n in ("Q", "n_items", "n_cols", "k", "metric", "exclude_self")] + [
+        ("table", _fp), ("ld_table", C.c_int32), ("rnorm", _fp), ("items", _fp), ("cand_table", _fp),
+        ("ld_cand_table", C.c_int32), ("cand_rnorm", _fp), ("gather_candidates", C.c_int32)] + _TOPK_OUT
+
+
 class FeatCache(C.Structure):  # CarcaFeatCache
     _fields_ = [("p_c", _fp), ("a_c", _fp), ("state", _fp), ("table", _fp), ("n_rows", C.c_int32), ("ld_p", C.c_int32),
                 ("ld_a", C.c_int32)]
@@ -391,6 +398,8 @@ SIGNATURES = {
     "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
     "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
+    "carca_row_rnorm": (_i, [_fp, _i, _i, _i, _fp, _fp]),
+    "carca_similar_items": (_i, [C.POINTER(SimilarDesc), C.POINTER(Candidates), _fp]),
     "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),

@@ -3,7 +3,8 @@ DESIGN.md sections 10-12).  A call fills the model side of a descriptor (carca_m
 a (user, item) pair), then does what the four share -- the k / items checks, the exclusion list, the outputs and the
 launch (recommend, rank_items).  A model's two descriptors name their model-side and exclusion fields alike
 (include/carca_hip.h), so one function fills both.  CandidateSet is the item set the CARCA calls can be restricted to
-(DESIGN.md section 15)."""
+(DESIGN.md section 15).  similar_items is the item-to-item top-k over a row table (CARCA.similar_items, KNN.similar_items,
+ops.similar_rows)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -270,3 +271,93 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
         D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
         return _launch(what, D, entry, "ranks", N, profile[0].device, cand)
+
+
+# ---- item-to-item top-k (include/carca_hip.h: carca_similar_items) ------------------------------
+SIMILAR_METRICS = {"dot": 0, "cosine": 1}  # CARCA_SIMILAR_DOT, CARCA_SIMILAR_COSINE
+SIMILAR_BLOCK = 64  # queries per scoring workgroup (csrc: SI_QB): the granule of a chunk
+
+
+def similar_chunk_rows(max_scratch_bytes: int, n_columns: int) -> int:
+    """Queries per chunk: as many whole 64-query blocks as keep the [Qc, C] fp32 score buffer within max_scratch_bytes,
+    and one block where the budget does not hold even that."""
+    return max(SIMILAR_BLOCK, int(max_scratch_bytes) // (4 * max(int(n_columns), 1)) // SIMILAR_BLOCK * SIMILAR_BLOCK)
+
+
+def similar_chunks(n_queries: int, chunk_rows: int) -> list:
+    """The [start, stop) query slices of the chunk loop."""
+    return [(s, min(n_queries, s + chunk_rows)) for s in range(0, n_queries, chunk_rows)]
+
+
+def similar_args(what: str, items: Optional[Tensor], k: int, metric: str) -> None:
+    """The argument checks that need no table."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    if metric not in SIMILAR_METRICS:
+        raise ValueError(f'{what}: metric must be "cosine" or "dot", got {metric!r}')
+    if items is not None and (not isinstance(items, Tensor) or items.dim() != 1 or items.is_floating_point()
+                              or items.is_complex() or items.dtype == torch.bool):
+        raise CarcaHipError(f"{what}: items must be None (every item) or a 1-D integer tensor of item ids")
+
+
+def row_rnorm(table: Tensor, n_cols: int) -> Tensor:
+    """r [n_rows] = 1 / max(||table[i, :n_cols]||, 1e-12) in fp32 (carca_row_rnorm)."""
+    ops._need_cuda(table)
+    out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    if table.shape[0]:
+        _lib.check(_lib.load().carca_row_rnorm(table.data_ptr(), table.stride(0), table.shape[0], int(n_cols),
+                                               out.data_ptr(), ops._stream()), "row_rnorm")
+    return out
+
+
+def similar_items(what: str, table: Tensor, n_cols: int, rnorm: Callable[[], Tensor], items: Optional[Tensor], k: int,
+                  metric: str, exclude_self: bool, candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+    """The k rows of `table` [n_items, ld] (fp32, n_cols live columns, ld a multiple of 4, 16-byte aligned) closest to each
+    row listed in items: (scores [Q, k] float32, ids [Q, k] int64).  rnorm() gives the reciprocal row norms (row_rnorm of
+    the table; called for "cosine" only, so a caller can cache them).  The queries go in chunks of similar_chunk_rows
+    with no sync between them, each writing its slice of the outputs."""
+    similar_args(what, items, k, metric)
+    if isinstance(candidates, CandidateSet) and candidates.n_items != table.shape[0]:
+        raise CarcaHipError(f"{what}: the candidate set was built for n_items = {candidates.n_items}, the table has "
+                            f"{table.shape[0]}")
+    ops._need_cuda(table, items)
+    if table.dim() != 2 or table.dtype != torch.float32 or table.stride(1) != 1 or table.stride(0) % 4 or \
+            table.data_ptr() % 16 or not 1 <= int(n_cols) <= table.shape[1]:
+        raise CarcaHipError(f"{what}: the table must be float32 [n_items, >= n_cols] with unit column stride, a row stride "
+                            "that is a multiple of 4 floats and a 16-byte aligned base")
+    n_items, k, dev = table.shape[0], int(k), table.device
+    with torch.no_grad():
+        ids = torch.arange(n_items, dtype=torch.int32, device=dev) if items is None else _ids32_clamped(items, n_items)
+        Q = ids.shape[0]
+        D = _lib.SimilarDesc()
+        D.n_items, D.n_cols, D.k = n_items, int(n_cols), k
+        D.metric, D.exclude_self = SIMILAR_METRICS[metric], int(bool(exclude_self))
+        keep = [table, ids]
+        cand = _candidates(what, candidates, D, keep, dev)
+        n_columns = n_items if cand is None else cand.n
+        if Q == 0 or n_columns == 0:  # nothing to score: all padding, no launch
+            return (torch.zeros(Q, k, dtype=torch.float32, device=dev), torch.zeros(Q, k, dtype=torch.int64, device=dev))
+        scores = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        out_ids = torch.empty(Q, k, dtype=torch.int64, device=dev)
+        D.table, D.ld_table = table.data_ptr(), table.stride(0)
+        if metric == "cosine":
+            rn = rnorm()
+            keep.append(rn)
+            D.rnorm = rn.data_ptr()
+        if cand is not None:  # the listed rows (and their r), compacted by the first chunk's gather launch
+            ldc = (int(n_cols) + 3) // 4 * 4
+            ct = torch.empty(n_columns, ldc, dtype=torch.float32, device=dev)
+            keep.append(ct)
+            D.cand_table, D.ld_cand_table = ct.data_ptr(), ldc
+            if metric == "cosine":
+                cr = torch.empty(n_columns, dtype=torch.float32, device=dev)
+                keep.append(cr)
+                D.cand_rnorm = cr.data_ptr()
+        D.ld_scores = D.ld_ids_out = k
+        lib, stream = _lib.load(), ops._stream()
+        for n, (lo, hi) in enumerate(similar_chunks(Q, similar_chunk_rows(max_scratch_bytes, n_columns))):
+            D.Q, D.gather_candidates = hi - lo, int(n == 0)
+            D.items = ids.data_ptr() + 4 * lo
+            D.scores, D.ids_out = scores.data_ptr() + 4 * k * lo, out_ids.data_ptr() + 8 * k * lo
+            _lib.check(lib.carca_similar_items(C.byref(D), None if cand is None else C.byref(cand), stream), what)
+        return scores, out_ids

@@ -187,7 +187,7 @@ def _rows(x: Tensor) -> int:
 # carca.py:91).  T = the class's own embed_segments over one target segment ids = arange(n_items) with zero context, M
 # composed from its weights with carca_gemm_rows.  Cached per weight version like every other derived copy (the key of
 # _PackedModule._packed plus the identity of the registered attribute table); kept out of pickles.
-_TABLE_KEYS = ("_item_table_cache", "_ctx_matrix_cache", "_reco_cache")
+_TABLE_KEYS = ("_item_table_cache", "_ctx_matrix_cache", "_reco_cache", "_item_rnorm_cache")
 
 
 def _cached_table(module: nn.Module, slot: str, params, extra: tuple, build, keep=None):
@@ -200,6 +200,19 @@ def _cached_table(module: nn.Module, slot: str, params, extra: tuple, build, kee
     value = build()
     module.__dict__[slot] = (key, value, keep)
     return value
+
+
+def _item_rnorm(module: nn.Module, T: Tensor) -> Tensor:
+    """r [n_items] = 1 / max(||T[i]||, 1e-12) for T = module.item_table(): a derived copy under the item table's own key
+    (the entry references T, so a new table is a new entry)."""
+    tc = module.__dict__.get("_item_table_cache")
+    key = tc[0] if tc is not None and tc[1] is T else None
+    cache = module.__dict__.get("_item_rnorm_cache")
+    if cache is not None and key is not None and cache[0] == key and cache[2] is T:
+        return cache[1]
+    r = catalogue.row_rnorm(T, module.d)
+    module.__dict__["_item_rnorm_cache"] = (key, r, T)
+    return r
 
 
 def _need_attr_table(module: nn.Module, what: str) -> Tensor:
@@ -1367,6 +1380,31 @@ class CARCA(_PackedModule, Model):
                                     partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude,
                                     candidates)
 
+    # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items) ---------------------------------
+    def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,
+                      candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+        """The k items closest to each listed item in the space of the item table T[i] = e(i, 0) -- the row every
+        catalogue call scores an item by: (scores [Q, k] float32, ids [Q, k] int64), best first, on the device.
+
+        items: an int [Q] tensor of item ids (duplicates allowed), or None for every item (outputs [n_items, k], row i
+        for item i, row 0 padding).  metric "cosine": ((T[q] . T[i]) * r_q) * r_i with r = 1 / max(||T[.]||, 1e-12) in
+        fp32 (an all-zero row scores 0); "dot": T[q] . T[i]; anything else raises ValueError.  Eligible neighbours are
+        ids 1 .. n_items - 1, minus the query itself when exclude_self (items whose rows duplicate it stay), intersected
+        with `candidates` when given (a catalogue.CandidateSet, or a raw tensor / mask that builds one for this call and
+        costs a host sync; the query need not be in it).  Order and padding are recommend's: score descending, ties to
+        the smaller id, fewer than k eligible items pad with id 0 and score 0; a query id outside [1, n_items) gives a
+        fully padded row; scores are the raw metric.  1 <= k <= 128.  Bit-reproducible, and a pair's score bits do not
+        depend on the query's position, on the candidates or on max_scratch_bytes: the queries go in chunks whose
+        [Qc, C] score buffer stays within it (C = n_items or |S|; one 64-query block at least), with no sync between
+        them.  Runs under no_grad in train and eval mode alike; embeddings that read attributes need
+        register_attr_table.  T and r are cached per weight version."""
+        catalogue.similar_args("similar_items", items, k, metric)
+        with torch.no_grad():
+            emb = self.embeds
+            T = emb.item_table()
+            return catalogue.similar_items("similar_items", T, emb.d, partial(_item_rnorm, emb, T), items, k, metric,
+                                           exclude_self, candidates, max_scratch_bytes)
+
     # ---- inference: one host call per forward (include/carca_hip.h: carca_forward) -----------------------------
     def _fused_ok(self, trace) -> bool:
         if trace is not None or len(self.encoder) > _lib.MAX_BLOCKS or not self._fusable():
@@ -1602,11 +1640,49 @@ class KNN(Model):
     def register_attr_table(self, attrs: Optional[Tensor]) -> None:
         self._attr_table = None if attrs is None else attrs.detach().to(torch.float32).contiguous()
         self.__dict__.pop("_i8_cache", None)
+        self.__dict__.pop("_similar_cache", None)
 
     def __getstate__(self):
         state = dict(super().__getstate__())
         state.pop("_i8_cache", None)
+        state.pop("_similar_cache", None)
         return state
+
+    def _similar_tables(self) -> dict:
+        """The derived copies similar_items runs on, cached with the table and keyed on its identity and _version as
+        int8_table is: "rows", the table itself or, where F is no multiple of 4, a copy with zero-padded rows (the
+        scoring kernel reads 16 bytes at a time); "rnorm", the reciprocal row norms, filled on the first cosine call."""
+        table = self._attr_table
+        c = self.__dict__.get("_similar_cache")
+        if c is None or c[0] is not table or c[1] != table._version:
+            rows = table
+            if table.shape[1] % 4 or table.data_ptr() % 16:
+                rows = torch.zeros(table.shape[0], (table.shape[1] + 3) // 4 * 4, dtype=torch.float32, device=table.device)
+                rows[:, :table.shape[1]] = table
+            c = (table, table._version, dict(rows=rows, rnorm=None))
+            self.__dict__["_similar_cache"] = c
+        return c[2]
+
+    def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,
+                      candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+        """The k items whose attribute rows are closest to each listed item's: CARCA.similar_items over the registered
+        attribute table [n_items, F] (its rows are the whole model), with the same arguments, order, padding and bits
+        rules.  With metric "dot" and exclude_self=False the scores are recommend's for a profile ending in that item."""
+        catalogue.similar_args("KNN.similar_items", items, k, metric)
+        table = self._attr_table
+        if table is None:
+            raise CarcaHipError("KNN.similar_items: no attribute table registered -- call register_attr_table(attrs) with "
+                                "the [n_items, n_attrs] item-attribute matrix first (the catalogue is its rows)")
+        ops._need_cuda(table)
+        with torch.no_grad():
+            c = self._similar_tables()
+
+            def rnorm():
+                if c["rnorm"] is None:
+                    c["rnorm"] = catalogue.row_rnorm(c["rows"], table.shape[1])
+                return c["rnorm"]
+            return catalogue.similar_items("KNN.similar_items", c["rows"], table.shape[1], rnorm, items, k, metric,
+                                           exclude_self, candidates, max_scratch_bytes)
 
     def int8_table(self) -> Optional[Tensor]:
         """The int8 copy of the registered table that the catalogue scoring runs on (ops.knn_int8_table), or None when

@@ -1771,3 +1771,17 @@ def sampled_bce(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, n_
         raise CarcaHipError(f"sampled_bce: beta must lie in [0, 1], got {beta}")
     _need_cuda(*ops_f, pos, s_ids)
     return _SampledBceFn.apply(P, Tp, S, C, _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1)), int(n_items), float(beta))
+
+
+def similar_rows(table: Tensor, n_cols: int, items: Optional[Tensor], k: int = 10, metric: str = "cosine",
+                 exclude_self: bool = True, candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+    """Item-to-item top-k over any fp32 row table on the device (carca_similar_items): for each id
+    of `items` (int [Q]; None = every row) the k rows of table [n_items, >= n_cols] closest to row id -- (scores [Q, k]
+    float32, ids [Q, k] int64), score descending, ties to the smaller id, padded with (0, 0).  metric "cosine" or "dot"
+    over the first n_cols columns (columns past them are not used); row 0 is the padding item and never listed.  The row
+    stride must be a multiple of 4 floats.  The reciprocal row norms are computed per call (CARCA.similar_items and
+    KNN.similar_items cache theirs).  The semantics are CARCA.similar_items'."""
+    from . import catalogue
+
+    return catalogue.similar_items("similar_rows", table, n_cols, lambda: catalogue.row_rnorm(table, n_cols), items, k,
+                                   metric, exclude_self, candidates, max_scratch_bytes)

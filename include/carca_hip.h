@@ -1123,6 +1123,48 @@ typedef struct CarcaSampledBceDesc {
 int carca_sampled_bce_fwd(const CarcaSampledBceDesc* desc, void* stream);
 int carca_sampled_bce_bwd(const CarcaSampledBceDesc* desc, void* stream);
 
+/* ---- item-to-item top-k over a row table: "which items are closest to this item"  -------------
+ * carca_row_rnorm: out[i] = 1 / max(sqrt(sum_c table[i][c]^2), 1e-12) over the first n_cols columns of each of the n_rows
+ * rows of table [n_rows, ld], in fp32, one wave per row.
+ *
+ * carca_similar_items: for each of the Q query ids items[q] (int32) the k columns of the table X [n_items, ld_table] (fp32,
+ * n_cols live columns; ld_table a multiple of 4, base 16-byte aligned; no column past n_cols reaches a product) that score
+ * highest against row items[q]:
+ *   metric CARCA_SIMILAR_DOT:    score = X[q] . X[i];
+ *   metric CARCA_SIMILAR_COSINE: score = ((X[q] . X[i]) * rnorm[q]) * rnorm[i], rnorm [n_items] from carca_row_rnorm (the
+ *     caller owns it: it is not recomputed per call).  An all-zero row is eligible and scores 0.
+ * Eligible: ids 1 .. n_items - 1, minus the query's own id when exclude_self, intersected with the candidate list when
+ * one is given (candidates NULL: the whole table; n >= 1 otherwise -- the caller pads for an empty list).  Order and
+ * padding are carca_recommend's: score descending, ties to the smaller id, fewer than k eligible items pad with id 0 and
+ * score 0; scores are the raw metric (no link).  A query id outside [1, n_items) gives a fully padded row; duplicates are
+ * allowed.  With a list, its rows and their rnorm are first copied into the caller's cand_table [n, ld_cand_table] (a
+ * multiple of 4, >= n_cols, 16-byte aligned) and cand_rnorm [n] when gather_candidates is set -- a caller that splits its
+ * queries over several calls sets it on the first only -- and the same scoring kernel runs over that compact table.
+ * Exact-fp32 MFMA products; the Q x C scores (C = n_items or n) live in stream scratch (or the capture's memory), with
+ * the gathered query rows when n_cols > 128; the selection launch is carca_recommend's.  A pair's score bits do not
+ * depend on Q, on the query's position or on the list; the same call gives the same bits.  No host wait.
+ * CARCA_ERR_UNSUPPORTED: k outside 1..128, n_cols > 2^22.  CARCA_ERR_BADARG: null pointers, strides, alignment, an
+ * unknown metric, cosine without rnorm, a list without cand_table (or, for cosine, cand_rnorm), n outside 1..n_items-1. */
+enum { CARCA_SIMILAR_DOT = 0, CARCA_SIMILAR_COSINE = 1 };
+typedef struct CarcaSimilarDesc {
+  int Q, n_items, n_cols, k;
+  int metric, exclude_self;
+  const float* table; /* [n_items, ld_table] */
+  int ld_table;
+  const float* rnorm;   /* [n_items], or NULL for CARCA_SIMILAR_DOT */
+  const int32_t* items; /* [Q] query ids */
+  float* cand_table;    /* [n, ld_cand_table] with a candidate list, else unused */
+  int ld_cand_table;
+  float* cand_rnorm;    /* [n] with a candidate list and CARCA_SIMILAR_COSINE */
+  int gather_candidates; /* fill cand_table / cand_rnorm in this call (else a previous call on the stream has) */
+  float* scores; /* [Q, ld_scores] */
+  int ld_scores;
+  int64_t* ids_out; /* [Q, ld_ids_out] */
+  int ld_ids_out;
+} CarcaSimilarDesc;
+int carca_row_rnorm(const float* table, int ld, int n_rows, int n_cols, float* out, void* stream);
+int carca_similar_items(const CarcaSimilarDesc* desc, const CarcaCandidates* candidates, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
