@@ -371,6 +371,7 @@ SIGNATURES = {
     "carca_gemm_rows_log": (_i, [C.c_char_p, _i]),
     "carca_feat_dedup_rows_multiplied": (C.c_longlong, []),
     "carca_feat_dedup_rows_computed": (C.c_longlong, []),
+    "carca_feat_dedup_rows_grouped": (C.c_longlong, []),
     "carca_feat_cache_arm": (_i, [C.POINTER(FeatCache)]),
     "carca_get_tuning": (_i, [_i]),
     "carca_mha_core_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, C.POINTER(Dropout),

@@ -234,6 +234,7 @@ enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRA
        CARCA_TUNE_SKC_MIN_STEPS = 19,      // ... and the K steps below which the product stays off that kernel
        CARCA_TUNE_FEAT_DEDUP = 20,
        CARCA_TUNE_FEAT_CACHE = 21,         // 1: the evaluation dedup never uses a per-item cache of P rows (A/B, tests)
+       CARCA_TUNE_DEDUP_SOLO = 22,         // 1: every row issues its own compare with its cache entry (ranks taken, unused)
        CARCA_TUNE_COUNT = 24 };
 // Values of key 0 (CARCA_TUNE_GEMM_VARIANT): A/B switches of the row GEMMs, the weight-gradient GEMMs and the gather, one
 // at a time -- which is why 158 exists.  A value with two meanings switches both.
@@ -315,6 +316,11 @@ int carca_gemm_rows_passenger(const CarcaGemmDesc* desc, const CarcaGatherArgs* 
 // the product plans from instead of flag, cnt [1] the number of such rows (zeroed by the insert launch: the product
 // returns at once when it reads 0), and pub [R] the id a slot's owner publishes its P row (and attribute row) under in
 // the expand launch, 0 = none.  Without a cache need, pub and cnt are null and every launch is what it was.
+// With a cache that keeps attribute rows (cache.a_c; round 20) the insert launch also ranks the rows of each table slot:
+// cnt_slot [2^hbits] (third array of the table, kept clean the same way) counts them, rank [R] is each row's rank in its
+// slot and mem [2^hbits][DD_LIST] the rows of the first DD_LIST ranks; the resolve launch lets the row of every
+// DD_GROUP-th rank compare its group with ONE read of the entry and marks the rows it did that for in grp [R].  solo: tuning
+// key 22 = 1, every row for itself.  All four are null otherwise.
 struct CarcaDedupRun {
   CarcaGemmDesc d;
   int nseg, R, vec, vec2, hbits;
@@ -328,6 +334,9 @@ struct CarcaDedupRun {
   int ldp;
   CarcaFeatCache cache;
   int *need, *pub, *cnt;
+  int *rank, *grp, *cnt_slot, *mem;
+  int solo;
+  int* err;  // carca_kernel_error_word(): 4 = a slot's row list named a row outside the batch
 };
 // 1 = not this product's path (nothing launched), CARCA_OK with *run filled, or an error
 int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, CarcaDedupRun* run);
@@ -335,7 +344,8 @@ int carca_feat_dedup_plan(const CarcaDedupRun* run, hipStream_t stream, hipEvent
 int carca_feat_dedup_expand(const CarcaDedupRun* run, hipStream_t stream, hipEvent_t stop);
 int carca_gemm_rows_feat_dedup(const CarcaGemmDesc* desc, void* stream);
 // host-visible word a kernel sets when it meets something no launch status can carry (1: a stream-K taker gave up waiting,
-// 2: gemm_rows_skc_kernel's row-block lists too short, 3: gemm_wgrad_cu_kernel's partial-tile slots too few); reported and
+// 2: gemm_rows_skc_kernel's row-block lists too short, 3: gemm_wgrad_cu_kernel's partial-tile slots too few, 4: a row list of
+// dedup_resolve_kernel named a row outside its batch); reported and
 // cleared by carca_poll_errors and by the next stream-K launch (gemm.hip).  Device view, or null.
 int* carca_kernel_error_word();
 // the joint embedding over q's columns with the item term from a projected table (embed.hip; CarcaForwardDesc.z_table)

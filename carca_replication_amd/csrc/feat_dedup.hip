@@ -38,6 +38,16 @@
 //      in one launch.
 // A row's P bits are then those of the batch that first computed it (another cut of the K sums; the same for equal call
 // sequences).
+//
+// Where the cache keeps attribute rows (dense batches), launch 2's time is the bytes it requests, and the rows of one item
+// all ask for the same entry.  So launch 1 also ranks the rows of each table slot (a third table array counts them; rank
+// [R] and the rows of the first DD_LIST ranks go to the per-launch scratch), and in launch 2 the row of every DD_GROUP-th
+// rank of a FILLED entry compares its own bytes and those of the next ranks' rows with one read of the entry, and writes
+// for each of them what that row's wave would have written; the other listed rows leave at once.  Every wave decides
+// which of the three it is from what launch 1 wrote and from `state`: nobody waits for anybody, and which row took which
+// rank changes no result.  A row's `slot` is the one word launch 2 reads and writes, so only the row's own wave writes
+// it.  Rows past the list, rows of an empty entry, the table path and a launch without a cache run the code above
+// (launches without ranks in an instantiation of launch 2 that holds nothing else).
 #include <hip/hip_ext.h>
 
 #include <vector>
@@ -53,6 +63,11 @@ constexpr int EXP_MAX_K1 = 8;
 constexpr int EXP_WB4 = ((EXP_MAX_K1 + 1) * EXP_MAX_N / 4 + 255) / 256;  // 16-byte pieces of the weight block per thread
 // floats of the compact weight block [K1 + 1][N] (rows 0 .. K1-1: W_c^T, row K1: b_f), padded to whole 16-byte pieces
 __host__ __device__ inline int exp_wb_floats(int K1, int N) { return ((K1 + 1) * N + 3) / 4 * 4; }
+// the hit compare of a batch against a filled cache (round 20): the rows of a table slot are ranked by the insert launch, the
+// first DD_LIST ranks are listed, and the row of every DD_GROUP-th rank compares its group with one read of the entry
+constexpr int DD_LIST = 16;
+constexpr int DD_GROUP = 4;
+static_assert(DD_LIST % DD_GROUP == 0 && DD_GROUP <= 8, "a leader's ranks stay inside the list");
 
 __device__ __forceinline__ int dd_seg(const CarcaDedupRun& a, int g) {
   int s = 0;
@@ -91,6 +106,11 @@ __global__ __launch_bounds__(256) void dedup_insert_kernel(const CarcaDedupRun a
     }
     atomicMax(&a.val[hh], 0xFFFFFFFFu - (unsigned)g);  // (max of ~row = the lowest row)
     h = (int)hh;
+    if (a.cnt_slot) {  // the row's rank among its slot's rows: which row takes which depends on timing, no result does
+      const int k = atomicAdd(&a.cnt_slot[hh], 1);
+      a.rank[g] = k;
+      if (k < DD_LIST) a.mem[(size_t)hh * DD_LIST + k] = g;
+    }
   }
   a.slot[g] = h;
 }
@@ -130,8 +150,96 @@ __device__ __forceinline__ bool dd_rows_differ(const unsigned* p, const unsigned
   return diff;
 }
 
-// one wave per row; VEC: every attribute row (the cache's copies included) 16-byte aligned and K0 % 4 == 0
+// which of the rows p[0 .. n-1] differ from row q (bit j: row j), by one wave: q's words are loaded ONCE per round and every
+// row's round is in flight with them; a row that differed is not read further.  2 KB per row and round (VEC), so that
+// DD_GROUP rows and the entry stay inside the registers of eight waves per SIMD.
 template <bool VEC>
+__device__ __forceinline__ unsigned dd_group_differ(const unsigned* const (&p)[DD_GROUP], const int n, const unsigned* q,
+                                                    const int K, const int lane) {
+  unsigned diff = 0;
+  const unsigned all = (1u << n) - 1u;
+  if constexpr (VEC) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    constexpr int RU = 2;
+    for (int k0 = 0; k0 < K && diff != all; k0 += RU * 256) {
+      u4 y[RU], x[DD_GROUP][RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int k = k0 + (u * 64 + lane) * 4;
+        y[u] = k < K ? *reinterpret_cast<const u4*>(q + k) : u4{0, 0, 0, 0};
+      }
+#pragma unroll
+      for (int j = 0; j < DD_GROUP; ++j) {
+        const bool on = j < n && !((diff >> j) & 1u);
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+          const int k = k0 + (u * 64 + lane) * 4;
+          x[j][u] = on && k < K ? __builtin_nontemporal_load(reinterpret_cast<const u4*>(p[j] + k)) : u4{0, 0, 0, 0};
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < DD_GROUP; ++j) {
+        const bool on = j < n && !((diff >> j) & 1u);
+        bool d = false;
+#pragma unroll
+        for (int u = 0; u < RU; ++u)
+          d = d || x[j][u][0] != y[u][0] || x[j][u][1] != y[u][1] || x[j][u][2] != y[u][2] || x[j][u][3] != y[u][3];
+        if (on && __ballot(d) != 0) diff |= 1u << j;
+      }
+    }
+  } else {
+    for (int k0 = 0; k0 < K && diff != all; k0 += 256) {
+      bool d[DD_GROUP];
+#pragma unroll
+      for (int j = 0; j < DD_GROUP; ++j) d[j] = false;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * 64 + lane;
+        if (k < K) {
+          const unsigned y = q[k];
+#pragma unroll
+          for (int j = 0; j < DD_GROUP; ++j)
+            if (j < n && !((diff >> j) & 1u)) d[j] = d[j] || p[j][k] != y;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < DD_GROUP; ++j)
+        if (j < n && __ballot(d[j]) != 0) diff |= 1u << j;
+    }
+  }
+  return diff;
+}
+
+// whether row g merges into its slot's owner r0 (another row): rows of one table under one id are one row, else by bytes
+template <bool VEC>
+__device__ __forceinline__ bool dd_merges(const CarcaDedupRun& a, const int g, const int r0, const int lane) {
+  const int s = dd_seg(a, g), t = dd_seg(a, r0);
+  const CarcaGemmSeg &sg = a.d.seg[s], &tg = a.d.seg[t];
+  if (sg.a0_gather && tg.a0_gather && sg.a0 == tg.a0) return true;  // (one table, one id: one row)
+  const unsigned* p = reinterpret_cast<const unsigned*>(dd_a0_row(a, s, g - a.row0[s]));
+  const unsigned* q = reinterpret_cast<const unsigned*>(dd_a0_row(a, t, r0 - a.row0[t]));
+  return !dd_rows_differ<VEC>(p, q, a.d.K0, lane);
+}
+
+// what the resolve launch leaves of kept row g (one lane): its representative and the flags the product plans from
+__device__ __forceinline__ void dd_write_row(const CarcaDedupRun& a, const int g, const int r0, const int ci, const bool filled,
+                                             const bool hit, const bool merge) {
+  // (a hit that does not own the slot counts as merged: its owner hit too unless the owner carries other bytes)
+  a.rep[g] = hit ? -2 - ci : (merge ? r0 : g);
+  a.flag[g] = hit ? (r0 == g ? 1 : 0) : (merge ? 0 : 1);
+  if (a.cache.state) {
+    const int need = !hit && !merge;
+    a.need[g] = need;
+    a.pub[g] = r0 == g && ci > 0 && !filled ? ci : 0;  // (the owner is its own representative: P[g] is computed)
+    if (need) atomicAdd(a.cnt, 1);
+  }
+}
+
+// one wave per row; VEC: every attribute row (the cache's copies included) 16-byte aligned and K0 % 4 == 0; GROUPS: the
+// insert launch ranked the rows and key 22 is off -- every other launch (no cache, the table path, a cold call's empty
+// entries aside) runs an instantiation without the group code: on the table path this pass is a few us of launch and
+// round trips, and the group code in its way cost it 1.6 us
+template <bool VEC, bool GROUPS>
 __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun a) {
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -146,9 +254,13 @@ __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun 
         a.need[g] = 0;
         a.pub[g] = 0;
       }
+      if (a.grp) a.grp[g] = 0;
     }
     return;
   }
+  // (ranks exist only under a cache that keeps attribute rows, and only for rows with an id)
+  int rk = DD_LIST;
+  if constexpr (GROUPS) rk = a.rank[g];
   const int r0 = (int)(0xFFFFFFFFu - a.val[h]);
   const int s = dd_seg(a, g);
   const CarcaGemmSeg& sg = a.d.seg[s];
@@ -162,6 +274,47 @@ __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun 
       ci = id;
       filled = a.cache.state[id] == 1;
     }
+    // A GROUPED row: filled entry, ranked, rank inside the list.  Every row of the slot decides this from what the insert
+    // launch left (slot, key, rank) and from state, which nobody writes during this launch, and all rows of a slot carry one
+    // id: they agree.  The row of every DD_GROUP-th rank compares for the ranks up to the next one; the others leave.
+    if (GROUPS && filled && rk < DD_LIST) {
+      if (rk % DD_GROUP == 0) {
+        const int n = min(min(a.cnt_slot[h], DD_LIST) - rk, DD_GROUP);  // (>= 1: this row)
+        int m[DD_GROUP];
+        const unsigned* p[DD_GROUP];
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < DD_GROUP; ++j) {
+          m[j] = j > 0 && j < n ? __builtin_amdgcn_readfirstlane(a.mem[(size_t)h * DD_LIST + rk + j]) : g;
+          if ((unsigned)m[j] >= (unsigned)a.R) {  // no row of this batch: the list is corrupt.  Nothing is read or written
+            bad = true;                           // out of bounds (the entry counts as this row again) and the host is
+            m[j] = g;                             // told: the rows the list should have named keep no outputs
+          }
+          const int t = dd_seg(a, m[j]);
+          p[j] = reinterpret_cast<const unsigned*>(dd_a0_row(a, t, m[j] - a.row0[t]));
+        }
+        if (bad && lane == 0 && a.err) *a.err = 4;  // (reported by carca_poll_errors and the next stream-K launch)
+        const unsigned* q = reinterpret_cast<const unsigned*>(a.cache.a_c + (size_t)ci * a.cache.ld_a);
+        const unsigned diff = dd_group_differ<VEC>(p, n, q, a.d.K0, lane);
+#pragma unroll 1
+        for (int j = 0; j < n; ++j) {
+          int mj = g;
+#pragma unroll
+          for (int i = 1; i < DD_GROUP; ++i)
+            if (j == i) mj = m[i];
+          const bool hj = !((diff >> j) & 1u);
+          bool merge = false;
+          if (!hj && r0 != mj) merge = dd_merges<VEC>(a, mj, r0, lane);  // (a changed row under a cached id: rare)
+          if (lane == 0) {
+            dd_write_row(a, mj, r0, ci, true, hj, merge);
+            a.grp[mj] = 1;
+          }
+        }
+      }
+      // (its own wave alone writes a row's slot: that wave reads it at its top)
+      if (lane == 0 && r0 != g) a.slot[g] = -1;
+      return;
+    }
     if (filled) {
       if (a.cache.a_c) {
         const unsigned* p = reinterpret_cast<const unsigned*>(dd_a0_row(a, s, g - a.row0[s]));
@@ -173,26 +326,10 @@ __global__ __launch_bounds__(256) void dedup_resolve_kernel(const CarcaDedupRun 
     }
   }
   bool merge = false;
-  if (!hit && r0 != g) {
-    const int t = dd_seg(a, r0);
-    const CarcaGemmSeg& tg = a.d.seg[t];
-    merge = sg.a0_gather && tg.a0_gather && sg.a0 == tg.a0;  // (one table, one id: one row)
-    if (!merge) {
-      const unsigned* p = reinterpret_cast<const unsigned*>(dd_a0_row(a, s, g - a.row0[s]));
-      const unsigned* q = reinterpret_cast<const unsigned*>(dd_a0_row(a, t, r0 - a.row0[t]));
-      merge = !dd_rows_differ<VEC>(p, q, a.d.K0, lane);
-    }
-  }
+  if (!hit && r0 != g) merge = dd_merges<VEC>(a, g, r0, lane);
   if (lane == 0) {
-    // (a hit that does not own the slot counts as merged: its owner hit too unless the owner carries other bytes)
-    a.rep[g] = hit ? -2 - ci : (merge ? r0 : g);
-    a.flag[g] = hit ? (r0 == g ? 1 : 0) : (merge ? 0 : 1);
-    if (cache) {
-      const int need = !hit && !merge;
-      a.need[g] = need;
-      a.pub[g] = r0 == g && ci > 0 && !filled ? ci : 0;  // (the owner is its own representative: P[g] is computed)
-      if (need) atomicAdd(a.cnt, 1);
-    }
+    dd_write_row(a, g, r0, ci, filled, hit, merge);
+    if (a.grp) a.grp[g] = 0;
     if (r0 != g) a.slot[g] = -1;  // (the slot stays with its owner, the lowest row: the expand kernel clears it)
   }
 }
@@ -258,6 +395,7 @@ __global__ __launch_bounds__(256) void dedup_expand_kernel(const CarcaDedupRun a
       if (h >= 0) {  // (nobody reads the table after the resolve kernel)
         a.key[h] = 0;
         a.val[h] = 0u;
+        if (a.cnt_slot) a.cnt_slot[h] = 0;
       }
     }
     reps[row] = u;
@@ -356,8 +494,9 @@ struct DdLast {
   hipStream_t stream;
   size_t bytes, flag_off, need_off;  // (need_off = flag_off without a cache: every flagged row is multiplied)
   int R;
+  size_t grp_off;  // (0: the launch ranked no rows)
 };
-thread_local DdLast g_dd_last{nullptr, 0, 0, 0, 0};
+thread_local DdLast g_dd_last{nullptr, 0, 0, 0, 0, 0};
 
 }  // namespace
 
@@ -411,9 +550,15 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
     if (fc.a_c && (((uintptr_t)fc.a_c & 15) != 0 || fc.ld_a % 4 != 0)) a.vec = 0;
     if (((uintptr_t)fc.p_c & 7) != 0 || fc.ld_p % 2 != 0) a.vec2 = 0;
   }
-  // the table (zeroed when allocated, kept clean by the expand kernel) and the per-launch arrays + weight block + P
-  const size_t hbytes = (size_t)2 * sizeof(int) << hb;
-  const size_t ibytes = ((size_t)(cached ? 5 * R + 1 : 3 * R) * sizeof(int) + 255) / 256 * 256;
+  // the table (zeroed when allocated, kept clean by the expand kernel) and the per-launch arrays + weight block + P.
+  // The table always has room for its third array, the per-slot row counts: every launch on a stream shares one buffer
+  // whatever its hbits, so all of it has to be clean between launches -- which is why the slots' row lists, which nobody
+  // clears, lie with the per-launch arrays (behind them: flag_off / need_off stay where they were).
+  const bool ranked = cached && fc.a_c != nullptr;
+  a.solo = carca_tuning(CARCA_TUNE_DEDUP_SOLO) == 1 ? 1 : 0;
+  const size_t hbytes = (size_t)3 * sizeof(int) << hb;
+  const size_t nints = (size_t)(cached ? 5 * R + 1 : 3 * R) + (ranked ? (size_t)2 * R + ((size_t)DD_LIST << hb) : 0);
+  const size_t ibytes = (nints * sizeof(int) + 255) / 256 * 256;
   const size_t wbytes = ((size_t)exp_wb_floats(D.K1, D.N) * sizeof(float) + 255) / 256 * 256;
   const size_t bytes = ibytes + wbytes + (size_t)R * a.ldp * sizeof(float);
   char* ht = (char*)(cap ? carca_capture_alloc(stream, hbytes, false, nullptr, hbytes)
@@ -431,10 +576,18 @@ int carca_feat_dedup_prepare(const CarcaGemmDesc* desc, hipStream_t stream, Carc
     a.pub = a.need + R;
     a.cnt = a.pub + R;
   }
+  if (ranked) {
+    a.err = carca_kernel_error_word();
+    a.cnt_slot = (int*)(ht + ((size_t)2 * sizeof(int) << hb));
+    a.rank = a.cnt + 1;
+    a.grp = a.rank + R;
+    a.mem = a.grp + R;
+  }
   a.wcb = (float*)(buf + ibytes);
   a.P = (float*)(buf + ibytes + wbytes);
   g_dd_last = cap ? DdLast{nullptr, 0, 0, 0, 0}
-                  : DdLast{stream, bytes, (size_t)2 * R * sizeof(int), (size_t)(cached ? 3 : 2) * R * sizeof(int), a.R};
+                  : DdLast{stream, bytes, (size_t)2 * R * sizeof(int), (size_t)(cached ? 3 : 2) * R * sizeof(int), a.R,
+                           ranked ? (size_t)(6 * R + 1) * sizeof(int) : 0};
   return CARCA_OK;
 }
 
@@ -447,10 +600,10 @@ int carca_feat_dedup_plan(const CarcaDedupRun* run, hipStream_t stream, hipEvent
   else
     hipLaunchKernelGGL(dedup_insert_kernel, gi, dim3(256), 0, stream, a);
   CARCA_LAUNCH_CHECK();
-  if (a.vec)
-    hipLaunchKernelGGL(dedup_resolve_kernel<true>, gr, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(dedup_resolve_kernel<false>, gr, dim3(256), 0, stream, a);
+  const bool groups = a.rank != nullptr && !a.solo;
+  auto kern = a.vec ? (groups ? dedup_resolve_kernel<true, true> : dedup_resolve_kernel<true, false>)
+                    : (groups ? dedup_resolve_kernel<false, true> : dedup_resolve_kernel<false, false>);
+  hipLaunchKernelGGL(kern, gr, dim3(256), 0, stream, a);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -492,3 +645,8 @@ static long long dd_count_last(size_t DdLast::*off) {
 extern "C" long long carca_feat_dedup_rows_multiplied(void) { return dd_count_last(&DdLast::flag_off); }
 // ... and the rows the product multiplied: the flagged rows that no cache entry served.
 extern "C" long long carca_feat_dedup_rows_computed(void) { return dd_count_last(&DdLast::need_off); }
+// ... and the rows whose compare with their cache entry the row of a group's first rank issued, that row included; 0 where
+// the launch ranked no rows (no cache, the attribute-table path, a captured launch, none yet).
+extern "C" long long carca_feat_dedup_rows_grouped(void) {
+  return g_dd_last.grp_off ? dd_count_last(&DdLast::grp_off) : 0;
+}

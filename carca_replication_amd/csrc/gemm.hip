@@ -1888,6 +1888,12 @@ static int sk_check_error_word() {
                     "selects the atomic flush");
     return CARCA_ERR_UNSUPPORTED;
   }
+  if (g_sk_err_host && *(volatile int*)g_sk_err_host == 4) {
+    *(volatile int*)g_sk_err_host = 0;
+    carca_set_error("feat_dedup: an EARLIER dedup_resolve_kernel launch met a row list that names a row outside its batch "
+                    "(rows of that item keep no outputs): a bug -- carca_set_tuning(22, 1) selects the per-row compare");
+    return CARCA_ERR_UNSUPPORTED;
+  }
   if (g_sk_err_host && *(volatile int*)g_sk_err_host == 2) {
     *(volatile int*)g_sk_err_host = 0;
     carca_set_error("gemm_rows: an EARLIER gemm_rows_skc_kernel launch met a stretch of more row blocks than its lists hold "

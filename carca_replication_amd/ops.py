@@ -1309,7 +1309,15 @@ def feat_dedup_rows_computed() -> int:
     return int(_lib.load().carca_feat_dedup_rows_computed())
 
 
+def feat_dedup_rows_grouped() -> int:
+    """Rows of that launch whose byte compare with their cache entry was issued by the first row of their group of up to
+    four rows of one item, that row included; 0 where the launch grouped nothing (no cache, the attribute-table path,
+    tuning key 22 = 1, a captured launch)."""
+    return int(_lib.load().carca_feat_dedup_rows_grouped())
+
+
 TUNE_FEAT_CACHE = 21  # 1: the evaluation dedup never uses the per-item cache of P rows (A/B, tests)
+TUNE_DEDUP_SOLO = 22  # 1: under that cache every row compares with its entry itself (A/B, tests); the cache stays on
 
 
 def get_tuning(key: int) -> int:

@@ -104,7 +104,9 @@ int carca_abi_version(void);
  *   key 19 gemm_rows_skc_kernel: K steps of k-source 0 below which the product stays off it (0 = 64)
  *   key 20 feature product of an evaluation forward (carca_forward without a backward's saves): 0 = over one representative
  *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests)
- *   key 21 1 = the per-item cache of that product (carca_feat_cache_arm) is never used (A/B, tests) */
+ *   key 21 1 = the per-item cache of that product (carca_feat_cache_arm) is never used (A/B, tests)
+ *   key 22 1 = under that cache every row compares its bytes with its entry itself; 0 = one row of up to four of an item
+ *          compares for all of them with one read of the entry (the same results; A/B, tests).  Does not switch the cache off */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
@@ -507,6 +509,10 @@ int carca_gemm_rows_log(char* out /*or NULL*/, int cap);
 long long carca_feat_dedup_rows_multiplied(void);
 /* ... and the rows of that launch the product really multiplied: those of the count above that no cache entry served. */
 long long carca_feat_dedup_rows_computed(void);
+/* ... and the rows of that launch whose compare with their cache entry another row's wave (or their own, as the first of
+ * a group) issued together with its neighbours'; 0 where the launch grouped nothing: no cache, the attribute-table path,
+ * key 22 = 1, a captured launch, no launch yet. */
+long long carca_feat_dedup_rows_grouped(void);
 /* A per-item cache of the evaluation feature product's attribute part, P[i] = attrs[i] W_a^T (feat_dedup.hip; DESIGN.md
  * 4f), indexed by item id.  The "+dedup" launches fill it lazily -- a slot's owner row publishes its P row (and, for dense
  * batches, the attribute row it was computed from) into an EMPTY entry -- and later launches take a filled entry's row
