@@ -388,6 +388,9 @@ SIGNATURES = {
     "carca_early_event_recorded": (_i, []),
     "carca_adam_step": (_i, [C.POINTER(AdamTensor), _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
                         _fp]),
+    "carca_adam_step_ex": (_i, [C.POINTER(AdamTensor), _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                           _i, _fp, _fp]),
+    "carca_grad_norm": (_i, [C.POINTER(AdamTensor), _i, C.c_double, _fp, C.c_int64, _fp, _fp]),
     "carca_mark_rows": (_i, [_fp, C.c_int64, _fp, C.c_int64, _fp]),
     "carca_zero_rows": (_i, [_fp, C.c_int64, _i, C.POINTER(_fp), C.POINTER(C.c_int64), _i, _fp]),
     "carca_concat_ids": (_i, [C.POINTER(_fp), C.POINTER(C.c_int64), _i, _fp, _fp]),

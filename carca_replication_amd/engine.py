@@ -84,6 +84,10 @@ def train_step(model, optim, batch, sharded: bool = False, global_batch: Optiona
     global_batch: users of the whole step over all ranks (shards as dist.shard_range cuts them); lets a model with a
     big item table size its row exchange without a host sync (dist.allgather_row_gradients).
     Returns the (device) loss: the global batch loss's local share when sharded.
+
+    optim: any torch optimizer; optim.Adam / optim.AdamW take the step in one launch.  With their max_grad_norm the clip
+    by global gradient norm happens inside optim.step(), which every path here calls after the gradient all-reduce: the
+    norm is over the summed gradient on every rank and needs no collective of its own.
     """
     if loss not in LOSSES:
         raise ValueError(f"train_step: loss must be one of {LOSSES}, got {loss!r}")
@@ -289,7 +293,8 @@ def _forward_backward(model, optim, batch, denom: Optional[torch.Tensor]) -> tor
 
 class GraphedTrainStep:
     """train_step with its forward + backward (~40 launches, 1.3-2.0 ms of host time at C2 against 1.1-1.9 ms of GPU
-    time) captured ONCE into a hipGraph and replayed per batch; the optimizer's single launch is issued behind each replay.
+    time) captured ONCE into a hipGraph and replayed per batch; the optimizer's single launch (three with max_grad_norm:
+    the two of the gradient norm in front of it) is issued behind each replay, outside the graph.
 
         step = GraphedTrainStep(model, optim, example_batch)   # shapes and dtypes are fixed from here on
         for batch in loader: loss = step(batch)                  # device loss, overwritten by the next call

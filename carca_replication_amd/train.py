@@ -229,7 +229,9 @@ def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_l
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,
           resume: Union[str, None] = None, resume_trusted: bool = False, loss: str = "bce", sampler=None) -> Model:
-    """src/train.py:56-152.  Extensions, off by default:
+    """src/train.py:56-152.  optim: any torch optimizer; optim.Adam / optim.AdamW step in one launch and clip by global
+    gradient norm inside the step when built with max_grad_norm -- nothing to pass here.
+    Extensions, off by default:
     graphed: batches of the first batch's shape replay their forward + backward from one hipGraph
       (engine.GraphedTrainStep); any other shape (a short last batch) takes the eager step;
     resume: path of a checkpoint written by an earlier run (save_checkpoint): model, optimizer and scheduler state are

@@ -685,6 +685,25 @@ typedef struct {
 } CarcaAdamTensor;
 int carca_adam_step(const CarcaAdamTensor* tensors, int n, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int step, void* stream);
+/* The same launch with two options.  carca_adam_step forwards here with decoupled = 0, grad_scale = NULL.
+ *   grad_scale (device, one float, may be NULL): g = g * *grad_scale before anything else, the product rounded on its
+ *     own -- the bits of scaling the gradient in a separate pass (clipping by global norm: out[1] of carca_grad_norm).
+ *   decoupled != 0: torch.optim.AdamW's decay, p = p * (1 - lr*weight_decay) (the factor combined in double, rounded
+ *     once), then Adam's update on the undecayed g, instead of g += wd*p.
+ * A row mask needs weight_decay == 0 with either style: decoupled decay moves untouched rows too. */
+int carca_adam_step_ex(const CarcaAdamTensor* tensors, int n, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int step, int decoupled, const float* grad_scale, void* stream);
+/* The 2-norm of every gradient of the table taken as one vector, and the factor that clips it to max_norm (> 0):
+ *   out[0] = norm = (float)sqrt(sum g^2),  out[1] = scale = min(1, max_norm / (norm + 1e-6f))  (fp32)
+ * -- torch.nn.utils.clip_grad_norm_'s arithmetic with error_if_nonfinite=False: a non-finite gradient gives a
+ * non-finite scale.  Only g, n, row_mask and row_len of an entry are read; rows whose mask byte is 0 are not read at all
+ * (their gradient is exactly 0 by the contract above, so the result has the bits of the unmasked sum); a row mask needs
+ * row_len >= 1 dividing n.  One fp32 partial per 1024-element chunk goes to `partials` (device, n_partials >= the sum
+ * over entries of ceil(n_i / 1024) floats), one block then adds them in double in index order: no atomics, the same
+ * bits for the same gradients on every call.  The library allocates nothing; `partials` and `out` (device, 2 floats)
+ * are the caller's.  Launches only: reading `out` is the caller's synchronisation. */
+int carca_grad_norm(const CarcaAdamTensor* tensors /*host [n]*/, int n, double max_norm, float* partials, int64_t n_partials,
+                    float* out /*[2]: norm, scale*/, void* stream);
 /* mask[ids[i]] = 1 for i < n (ids outside [0, n_rows) are ignored): the rows a batch touches, for CarcaAdamTensor.row_mask */
 int carca_mark_rows(const int32_t* ids, int64_t n, uint8_t* mask, int64_t n_rows, void* stream);
 /* table[ids[i]][0 .. row_len) = 0 for every id of up to CARCA_MAX_SEGS id lists (ids outside [0, n_rows) ignored): clears
