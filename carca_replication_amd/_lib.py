@@ -26,6 +26,7 @@ HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", 
 MAX_SEGS = 4
 MAX_GROUPS = 3
 MAX_L = 64
+MAX_PROFILE_L = 1024  # CARCA_MAX_PROFILE_L: profile slots of carca_recommend / carca_rank_items
 
 _lock = threading.Lock()
 _lib = None

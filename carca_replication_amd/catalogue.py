@@ -85,25 +85,49 @@ def _candidates(what: str, candidates, D, keep: list, device):
     return _lib.Candidates(ids.data_ptr() if ids.shape[0] else None, ids.shape[0])
 
 
-def carca_model_side(model, profile, context: Optional[Tensor], what: str, D) -> Tuple[list, Tensor]:
-    """Checks the envelope of CARCA.recommend / rank_items and fills the model-side fields of D (RecommendDesc or RankDesc)
-    -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path of forward
-    (embed_segments + the fused blocks + the final LayerNorm), then K, V -> u, M c, dq and w . M c.  Returns (the tensors
-    D points into, kept alive by the caller until the launch is queued; the profile ids as int32).  Call under no_grad."""
+def carca_route(what: str, d: int, encoder_heads, L: int, decoder_heads: Optional[int], allow_composed: bool) -> str:
+    """The envelope of CARCA.recommend / rank_items and the path their profile side takes: "fused" (the per-user kernels)
+    or "composed" (long_profile's row-level encoder); raises CarcaHipError outside the envelope.  encoder_heads: H of every
+    encoder block; decoder_heads: H of a cross-attention decoder, None for the dot decoders (their sweep needs only d).
+    allow_composed=False: L <= 64 and every attention module's (d, H) among the built geometries, always fused.
+    allow_composed=True: L <= 1024 and d <= 128; a cross-attention decoder still needs its own (d, H) built (the sweep's
+    scorer is instantiated per geometry); the profile side is composed where ops.use_composed says so (L > 64, or an
+    encoder head count with no fused geometry) and fused otherwise.  No tensor is touched."""
+    heads = list(encoder_heads) + ([decoder_heads] if decoder_heads is not None else [])
+    no_kernel = "(d, H) = ({}, {}) has no fused attention kernel built (CARCA_ATT_GEOMETRIES in csrc/attn_common.h)"
+    if not allow_composed:
+        if L > _lib.MAX_L:
+            raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L} (allow_composed=True "
+                                f"takes up to {_lib.MAX_PROFILE_L} slots)")
+        bad = [H for H in heads if d > ops.FUSED_MAX_D or not ops.attn_geometry_built(d, H)]
+        if bad:
+            raise CarcaHipError(f"{what}: " + no_kernel.format(d, bad[0]))
+        return "fused"
+    if L > _lib.MAX_PROFILE_L:
+        raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_PROFILE_L = {_lib.MAX_PROFILE_L}")
+    if d > ops.FUSED_MAX_D:
+        raise CarcaHipError(f"{what}: d = {d} exceeds {ops.FUSED_MAX_D} (the sweep keeps an item's row in registers)")
+    if decoder_heads is not None and not ops.attn_geometry_built(d, decoder_heads):
+        raise CarcaHipError(f"{what}: " + no_kernel.format(d, decoder_heads))
+    return "composed" if ops.use_composed(d, encoder_heads, L) else "fused"
+
+
+def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
+                     allow_composed: bool = False) -> Tuple[list, Tensor]:
+    """Checks the envelope of CARCA.recommend / rank_items (carca_route) and fills the model-side fields of D (RecommendDesc
+    or RankDesc) -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path of
+    forward (embed_segments, then the fused blocks + the final LayerNorm, or long_profile.encode where the route is
+    composed), then K, V -> u, M c, dq and w . M c.  Returns (the tensors D points into, kept alive by the caller until
+    the launch is queued; the profile ids as int32).  Call under no_grad."""
     from .modules import CrossAttentionBlock, DotProduct, WeightedDotProduct
 
     p_x, p_a, p_c = profile
     ops._need_cuda(p_x, p_a, p_c, context)
     B, L = p_x.shape
-    if L > _lib.MAX_L:
-        raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}")
     emb, dec = model.embeds, model.decoder
     d = emb.d
-    bad = [H for H in model._attn_heads() if d > ops.FUSED_MAX_D or not ops.attn_geometry_built(d, H)]
-    if bad:
-        raise CarcaHipError(f"{what}: (d, H) = ({d}, {bad[0]}) has no fused attention kernel built "
-                            "(CARCA_ATT_GEOMETRIES in csrc/attn_common.h)")
     ca = isinstance(dec, CrossAttentionBlock)
+    route = carca_route(what, d, [b.attn.H for b in model.encoder], L, dec.attn.H if ca else None, allow_composed)
     if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
         raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
     n_ctx = context.shape[-1] if context is not None else 0
@@ -115,13 +139,19 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D) ->
     H = dec.attn.H if ca else model._heads()
     dpi, _, _ = ops.padded_dims(d, H)
     ld = ops.row_ld(d)
-    # profile side: the encoder path of forward (embed_segments + the fused blocks + the final LayerNorm)
+    # profile side: the encoder path of forward (embed_segments + the blocks + the final LayerNorm)
     es, _ = emb.embed_segments([(p_x, p_a, p_c, False)], ld_e=dpi)
     x = es[0]
-    for blk in model.encoder:
-        blk._check_mode()
-        x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
-    p_n = ops.layernorm_fwd(x.reshape(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)
+    if route == "composed":  # the row-level kernels, as forward runs them for such a profile; rows padded back to dpi
+        from . import long_profile
+        from .autograd import _pad_to
+
+        p_n = _pad_to(long_profile.encode(model, x[..., :d], p_x), dpi).view(B * L, dpi)
+    else:
+        for blk in model.encoder:
+            blk._check_mode()
+            x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
+        p_n = ops.layernorm_fwd(x.reshape(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)
     mc = None
     if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
         (mc,) = ops.gemm_rows([dict(a0=ops._f32(context))], M, d, n_ctx, ld)
@@ -238,15 +268,21 @@ def _launch(what: str, D, entry: str, second: str, n: int, device, cand=None) ->
     return outs
 
 
+def _fill(fill: Callable, what: str, D, allow_composed: bool):
+    """fill(what, D) -> (keep, p_ids); the keyword goes only to a model side that was asked for it (carca_model_side)."""
+    return fill(what, D, allow_composed=True) if allow_composed else fill(what, D)
+
+
 def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, exclude,
-              candidates=None) -> Tuple[Tensor, Tensor]:
+              candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
     """The top-k call: desc the descriptor class, entry its C entry point, fill(what, D) -> (keep, p_ids) the model side;
-    candidates: None, or the set the call is restricted to (entry + "_among")."""
+    candidates: None, or the set the call is restricted to (entry + "_among"); allow_composed: CARCA's wider envelope
+    (carca_route), handed to fill."""
     if not 1 <= int(k) <= KMAX:
         raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
     with torch.no_grad():
         D = desc()
-        keep, p_ids = fill(what, D)
+        keep, p_ids = _fill(fill, what, D, allow_composed)
         D.k = int(k)
         _exclusion(what, exclude, p_ids, D, keep, clamp=False)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
@@ -254,7 +290,7 @@ def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, excl
 
 
 def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tensor, exclude,
-               candidates=None) -> Tuple[Tensor, Tensor]:
+               candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
     """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""
     ops._need_cuda(items)
     if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
@@ -264,7 +300,7 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
         raise CarcaHipError(f"{what}: N = {N} items per user outside 1..{KMAX}")
     with torch.no_grad():
         D = desc()
-        keep, p_ids = fill(what, D)
+        keep, p_ids = _fill(fill, what, D, allow_composed)
         _exclusion(what, exclude, p_ids, D, keep, clamp=True)
         lst = _ids32_clamped(items, D.n_items)
         keep.append(lst)

@@ -1,7 +1,8 @@
 // What carca_recommend (recommend.hip) and carca_rank_items (rank.hip) share around the per-pair arithmetic of
 // recommend_common.h, and the counting step they share with carca_knn_rank_items (knn_catalogue.hip):
 //   sweep_kernel   a 256-item tile in registers walks a chunk of users, stages each user in LDS and scores the pair.  The
-//                  scorer (rc::CaScorer / rc::DotScorer) says how, the sink what becomes of the logit: recommend stores
+//                  scorer (rc::CaScorer / rc::DotScorer; rc::CaLongScorer under sweep_long_kernel, which stages a long
+//                  profile in chunks) says how, the sink what becomes of the logit: recommend stores
 //                  it, rank_items compares its key with the user's target keys; the item map (recommend_common.h:
 //                  rc::AllItems / rc::ListedItems) says which item a lane owns: the catalogue's, or a candidate list's;
 //   count_larger   per target, the keys of the workgroup that are larger, one integer atomic per target;
@@ -31,6 +32,38 @@ __global__ __launch_bounds__(TILE) void sweep_kernel(typename Sink::Desc D, Sink
     sink.begin_user(D, u, C);
     scorer.stage_user(D, u, S);
     sink.put(D, u, pos, item, live, scorer.logit(D, u, I, S), C);
+  }
+}
+
+// sweep_kernel for a chunked scorer (rc::CaLongScorer: a profile of more than CARCA_MAX_L slots), same sinks and maps.
+// Barriers per user: the loop's own (the previous user's LDS is read out); begin_user's two (the compacted slot list and
+// the sink's LDS are published); per chunk, one in front of every chunk but the first (the previous chunk is read out)
+// and stage_chunk's two (K / u, then beta).  Every trip count in front of a barrier is workgroup-uniform: u0, u1 come from
+// launch parameters, n_chunks() from LDS words every thread reads after begin_user's barrier.
+template <class Scorer, class Sink, class Map = AllItems>
+__global__ __launch_bounds__(TILE) void sweep_long_kernel(typename Sink::Desc D, Sink sink, int users_per_block, Map map) {
+  __shared__ typename Scorer::User S;
+  __shared__ typename Sink::Lds C;
+  Scorer scorer(D);
+  const int pos = blockIdx.x * TILE + threadIdx.x;
+  const int item = map.item(pos);
+  const bool live = item >= 1 && item < D.n_items;
+  typename Scorer::Item I;
+  scorer.load_item(D, item, live, I);
+  const int u0 = blockIdx.y * users_per_block, u1 = min(D.B, u0 + users_per_block);
+  for (int u = u0; u < u1; ++u) {
+    __syncthreads();  // the previous user's LDS is read out
+    sink.begin_user(D, u, C);
+    scorer.begin_user(D, u, S);
+    typename Scorer::Acc A;
+    scorer.reset(A);
+    const int nc = scorer.n_chunks();
+    for (int c = 0; c < nc; ++c) {
+      if (c) __syncthreads();  // the previous chunk is read out
+      scorer.stage_chunk(D, u, c, S);
+      scorer.accumulate(I, S, c, A);
+    }
+    sink.put(D, u, pos, item, live, scorer.finish(D, u, I, A), C);
   }
 }
 
@@ -86,7 +119,8 @@ template <class Desc>
 int check_model(const Desc& D, const char* what) {
   CARCA_CHECK_ARG(D.B >= 1 && D.L >= 1 && D.n_items >= 1 && D.d >= 1 && D.H >= 1,
                   "%s: B, L, n_items, d and H must be positive", what);
-  CARCA_CHECK_SUPPORTED(D.L <= CARCA_MAX_L, "%s: profile length L = %d exceeds CARCA_MAX_L = %d", what, D.L, CARCA_MAX_L);
+  CARCA_CHECK_SUPPORTED(D.L <= CARCA_MAX_PROFILE_L, "%s: profile length L = %d exceeds CARCA_MAX_PROFILE_L = %d", what, D.L,
+                        CARCA_MAX_PROFILE_L);
   CARCA_CHECK_ARG(D.decoder >= 0 && D.decoder <= 2, "%s: decoder must be 0 (cross-attention), 1 (dot) or 2 (normalised dot)",
                   what);
   CARCA_CHECK_ARG(D.p_ids && D.item_q, "%s: null pointer", what);
@@ -131,7 +165,8 @@ inline int check_candidates(const CarcaCandidates* cand, const char* what) {
   return CARCA_OK;
 }
 
-// launch(ScorerOf<Scorer>{}) for the descriptor's scorer: one of CARCA_ATT_GEOMETRIES, or one of the three dot widths
+// launch(ScorerOf<Scorer>{}) for the descriptor's scorer: one of CARCA_ATT_GEOMETRIES (CaScorer up to CARCA_MAX_L slots,
+// CaLongScorer beyond), or one of the three dot widths (DotScorer reads no L)
 template <class Scorer>
 struct ScorerOf {
   using type = Scorer;
@@ -140,13 +175,21 @@ template <int DPI, int DHP, int H, class Launch>
 int launch_ca(Launch& launch) {
   return launch(ScorerOf<CaScorer<DHP, H>>{});
 }
+template <int DPI, int DHP, int H, class Launch>
+int launch_ca_long(Launch& launch) {
+  return launch(ScorerOf<CaLongScorer<DHP, H>>{});
+}
 template <class Desc, class Launch>
 int dispatch_scorer(const Desc& D, const char* what, Launch launch) {
   int dpi = 0, dhp = 0, dpo = 0;
   carca_padded_dims(D.d, D.H, &dpi, &dhp, &dpo);
   const int H = D.H;
   if (D.decoder == 0) {
-    CARCA_ATT_DISPATCH(launch_ca, launch);
+    if (D.L <= CARCA_MAX_L) {  // the whole user in LDS
+      CARCA_ATT_DISPATCH(launch_ca, launch);
+    } else {  // the profile staged CARCA_MAX_L valid slots at a time
+      CARCA_ATT_DISPATCH(launch_ca_long, launch);
+    }
     carca_set_error("%s: no cross-attention kernel for (dpi %d, dhp %d, H %d)", what, dpi, dhp, H);
     return CARCA_ERR_UNSUPPORTED;
   }

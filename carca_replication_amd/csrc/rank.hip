@@ -6,8 +6,9 @@
 // the same helpers as carca_recommend's, so the two calls agree bit for bit.  Three launches, no host wait, nothing
 // retained:
 //   1. list scoring, one workgroup per user: the n_list targets and the n_exclude excluded entries are scored with the
-//      user staged in LDS by the sweep's scorer; their keys go to stream scratch, the targets' linked scores to `scores`,
-//      and the user's [n_list] counter is zeroed;
+//      user staged in LDS by the sweep's scorer (a cross-attention profile of more than CARCA_MAX_L slots: in chunks,
+//      rk_list_long_kernel); their keys go to stream scratch, the targets' linked scores to `scores`, and the user's
+//      [n_list] counter is zeroed;
 //   2. counting sweep, recommend's sweep kernel (catalogue_sweep.h: a 256-item tile in registers walking a chunk of
 //      users) with the sink below: each lane compares its item's key with the user's target keys (LDS), a wave counts
 //      with ballot + popcount, the four waves sum in LDS and one integer atomic per (workgroup, user, target) with a
@@ -62,6 +63,38 @@ __global__ __launch_bounds__(RK_TILE) void rk_list_kernel(CarcaRankDesc D, RkScr
     typename Scorer::Item I;
     scorer.load_item(D, id, valid, I);
     rk_store_list(D, W, u, idx, id, valid, scorer.logit(D, u, I, S));
+  }
+}
+
+// rk_list_kernel for a chunked scorer (rc::CaLongScorer).  The list is walked in rounds of RK_TILE entries with a
+// trip count that is the same for the whole workgroup (n_list + n_exclude is a launch parameter), and a thread past
+// the end of the list carries a dead item through the round, so every thread reaches every barrier.  The chunks are
+// staged again in each round: a lane's (m, den, num) must see the user's slots in order.  Barriers: begin_user's two
+// (the slot list is published); in front of every stage_chunk but the very first, one (the chunk staged before it is
+// read out); stage_chunk's two (K / u, then beta).  n_chunks() is workgroup-uniform (LDS words read after a barrier).
+template <class Scorer>
+__global__ __launch_bounds__(RK_TILE) void rk_list_long_kernel(CarcaRankDesc D, RkScratch W) {
+  __shared__ typename Scorer::User S;
+  const int u = blockIdx.x, tid = threadIdx.x;
+  Scorer scorer(D);
+  for (int t = tid; t < D.n_list; t += RK_TILE) W.counts[(size_t)u * D.n_list + t] = 0;
+  scorer.begin_user(D, u, S);
+  const int n = D.n_list + D.n_exclude, nc = scorer.n_chunks();
+  for (int base = 0; base < n; base += RK_TILE) {
+    const int idx = base + tid;
+    const bool listed = idx < n;
+    const int id = listed ? rk_list_id(D, u, idx) : 0;
+    const bool valid = listed && rk_valid(id, D.n_items);
+    typename Scorer::Item I;
+    scorer.load_item(D, id, valid, I);
+    typename Scorer::Acc A;
+    scorer.reset(A);
+    for (int c = 0; c < nc; ++c) {
+      if (base || c) __syncthreads();  // the chunk staged before this one is read out
+      scorer.stage_chunk(D, u, c, S);
+      scorer.accumulate(I, S, c, A);
+    }
+    if (listed) rk_store_list(D, W, u, idx, id, valid, scorer.finish(D, u, I, A));
   }
 }
 
@@ -130,11 +163,20 @@ int rk_run(const CarcaRankDesc& D, Map map, int n_slots, hipStream_t stream) {
   const rc::SweepGrid G = rc::sweep_grid(std::max(n_slots, 1), D.B);
   const int rc = rc::dispatch_scorer(D, "rank_items", [&](auto scorer) -> int {
     using Scorer = typename decltype(scorer)::type;
-    hipLaunchKernelGGL(rk_list_kernel<Scorer>, dim3(D.B), dim3(RK_TILE), 0, stream, D, W);
+    if constexpr (Scorer::chunked) {  // cross-attention over a profile of more than CARCA_MAX_L slots
+      hipLaunchKernelGGL(rk_list_long_kernel<Scorer>, dim3(D.B), dim3(RK_TILE), 0, stream, D, W);
+    } else {
+      hipLaunchKernelGGL(rk_list_kernel<Scorer>, dim3(D.B), dim3(RK_TILE), 0, stream, D, W);
+    }
     CARCA_LAUNCH_CHECK();
     if (n_slots == 0) return CARCA_OK;  // (an empty candidate list: no tile to sweep, every count stays 0)
-    hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RkCountSink, Map>), G.grid, dim3(RK_TILE), 0, stream, D, RkCountSink{W},
-                       G.users_per_block, map);
+    if constexpr (Scorer::chunked) {
+      hipLaunchKernelGGL((rc::sweep_long_kernel<Scorer, RkCountSink, Map>), G.grid, dim3(RK_TILE), 0, stream, D,
+                         RkCountSink{W}, G.users_per_block, map);
+    } else {
+      hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RkCountSink, Map>), G.grid, dim3(RK_TILE), 0, stream, D, RkCountSink{W},
+                         G.users_per_block, map);
+    }
     CARCA_LAUNCH_CHECK();
     return CARCA_OK;
   });

@@ -9,7 +9,9 @@
 // Three launches, no host wait, nothing retained:
 //   1. scoring, the sweep of catalogue_sweep.h with the sink below: workgroups own 256-item tiles (one item per lane, its
 //      row in registers) and walk a chunk of users, each user's keys / folded values / score biases staged in LDS
-//      (recommend_common.h); raw logits go to a [B, n_items] stream-scratch buffer;
+//      (recommend_common.h) -- whole for a profile of up to CARCA_MAX_L slots, in chunks of CARCA_MAX_L valid slots
+//      beyond (rc::CaLongScorer under rc::sweep_long_kernel; the dot decoders read no L); raw logits go to a
+//      [B, n_items] stream-scratch buffer;
 //   2. exclusion: id 0 and the caller's [B, E] list are overwritten with a sentinel that selection never picks;
 //   3. selection: one workgroup per user, an MSB-first radix select over 64-bit keys (order-preserving logit bits,
 //      then the complemented item id, so ties go to the smaller id), a bitonic sort of the k survivors, and the link
@@ -62,8 +64,13 @@ int rc_run(const CarcaRecommendDesc& D, Map map, int n_slots, hipStream_t stream
     const rc::SweepGrid G = rc::sweep_grid(n_slots, D.B);
     const int rc = rc::dispatch_scorer(D, "recommend", [&](auto scorer) -> int {
       using Scorer = typename decltype(scorer)::type;
-      hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
-                         RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
+      if constexpr (Scorer::chunked) {  // cross-attention over a profile of more than CARCA_MAX_L slots
+        hipLaunchKernelGGL((rc::sweep_long_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
+                           RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
+      } else {
+        hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
+                           RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
+      }
       CARCA_LAUNCH_CHECK();
       return CARCA_OK;
     });

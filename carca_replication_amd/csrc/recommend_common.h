@@ -1,9 +1,10 @@
 // Per-(user, item) logit arithmetic and the item order shared by the full-catalogue kernels: the top-k sweep of
 // recommend.hip and the list scoring / counting sweep of rank.hip (both through catalogue_sweep.h).  Both calls order items
 // by the same 64-bit key (order-preserving logit bits, then the complemented id), so they must produce the same logit bits
-// for the same (user, item): every kernel stages a user and scores an item through one of the two scorers below
-// (CaScorer, DotScorer: the same five members), never through a copy of their arithmetic.  Desc is CarcaRecommendDesc or
-// CarcaRankDesc (the model-side fields carry the same names and meanings, include/carca_hip.h).
+// for the same (user, item): every kernel stages a user and scores an item through one of the scorers below
+// (CaScorer, DotScorer: the same five members; CaLongScorer, CaScorer's arithmetic over a profile staged in chunks),
+// never through a copy of their arithmetic.  Desc is CarcaRecommendDesc or CarcaRankDesc (the model-side fields carry
+// the same names and meanings, include/carca_hip.h).
 #pragma once
 #include "attn_common.h"
 
@@ -66,14 +67,80 @@ struct ListedItems {
   }
 };
 
-// ---- the two scorers -----------------------------------------------------------------------------------------------
+// ---- the scorers ---------------------------------------------------------------------------------------------------
 // A scorer is built per thread from the descriptor and has: User (one user's share, in LDS), Item (one item's share, in
 // registers), load_item (zeros where !live), stage_user (whole workgroup of TILE threads; the caller has synchronised
-// since the previous user's LDS was last read; ends with a barrier) and logit.
+// since the previous user's LDS was last read; ends with a barrier) and logit.  `chunked` says which protocol a kernel
+// runs: false = stage_user + logit, true = CaLongScorer's chunk loop.
 
-// cross-attention decoder
+// ---- what the two cross-attention scorers share ------------------------------------------------------------------
+// Stages n <= CARCA_MAX_L profile slots of user u, slot[0 .. n), into S (any User with Ks4 / Us / Bs): their K rows
+// head-padded, their folded values and the pre-scaled score biases.  Whole workgroup of TILE threads; n is
+// workgroup-uniform; the caller has synchronised since S was last read and has published slot[].  Two barriers: the
+// first publishes Ks / Us (beta reads Ks), the second Bs.
+template <int DHP, int H, class Desc, class User>
+__device__ __forceinline__ void ca_stage_slots(const Desc& D, int u, const int* slot, int n, float sc, User& S) {
+  constexpr int DPO = DHP * H;
+  const int tid = threadIdx.x, nthr = TILE;
+  const int dh = D.d / H;
+  float* Ks = reinterpret_cast<float*>(S.Ks4);
+  for (int idx = tid; idx < n * DPO; idx += nthr) {
+    const int j = idx / DPO, col = idx % DPO, h = col / DHP, c = col % DHP;
+    Ks[idx] = c < dh ? D.user_k[((size_t)u * D.L + slot[j]) * D.ld_user_k + h * dh + c] : 0.f;
+  }
+  for (int idx = tid; idx < n * H; idx += nthr) {
+    const int j = idx / H, h = idx % H;
+    S.Us[j][h] = D.user_u[((size_t)u * D.L + slot[j]) * D.ld_user_u + h];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < n * H; idx += nthr) {  // beta_hl = (M c_u W_Q^T)_h . K_hl, pre-scaled
+    const int j = idx / H, h = idx % H;
+    float b = 0.f;
+    if (D.user_q) {
+      const float* dq = D.user_q + (size_t)u * D.ld_user_q + h * dh;
+      for (int c = 0; c < dh; ++c) b = fmaf(dq[c], Ks[j * DPO + h * DHP + c], b);
+    }
+    S.Bs[h][j] = b * sc;
+  }
+  __syncthreads();
+}
+
+// One step of a head's online exp2 softmax: staged slot j of head h joins the running (m, den, num).  The only copy of
+// this arithmetic: CaScorer walks all of a user's slots with it, CaLongScorer the same slots 64 at a time.
+template <int DHP, int H, class User>
+__device__ __forceinline__ void ca_slot_step(const float (&q)[DHP], const User& S, int h, int j, float sc, float& m,
+                                             float& den, float& num) {
+  const float4* kr = S.Ks4 + (j * DHP * H + h * DHP) / 4;
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int c4 = 0; c4 < DHP / 4; ++c4) {
+    const float4 k4 = kr[c4];
+    s0 = fmaf(q[4 * c4], k4.x, s0);
+    s1 = fmaf(q[4 * c4 + 1], k4.y, s1);
+    s0 = fmaf(q[4 * c4 + 2], k4.z, s0);
+    s1 = fmaf(q[4 * c4 + 3], k4.w, s1);
+  }
+  const float s = fmaf(s0 + s1, sc, S.Bs[h][j]);
+  const float mn = fmaxf(m, s);
+  const float a = exp2f(m - mn), e = exp2f(s - mn);
+  den = fmaf(den, a, e);
+  num = fmaf(num, a, e * S.Us[j][h]);
+  m = mn;
+}
+
+// the terms of a cross-attention logit that no profile slot enters
+template <class Desc>
+__device__ __forceinline__ float ca_logit_offsets(const Desc& D, int u, float item_off) {
+  float logit = item_off;
+  if (D.user_off) logit += D.user_off[(size_t)u * D.ld_user_off];
+  if (D.ffn_b) logit += D.ffn_b[0];
+  return logit;
+}
+
+// cross-attention decoder, profiles of up to CARCA_MAX_L slots: the whole user in LDS
 template <int DHP, int H>
 struct CaScorer {
+  static constexpr bool chunked = false;
   static constexpr int DPO = DHP * H;
   struct User {
     float4 Ks4[CARCA_MAX_L * DHP * H / 4];  // compacted valid profile slots, head-padded
@@ -106,9 +173,7 @@ struct CaScorer {
 
   template <class Desc>
   __device__ __forceinline__ void stage_user(const Desc& D, int u, User& S) {
-    const int tid = threadIdx.x, nthr = TILE;
-    const int dh = D.d / H;
-    float* Ks = reinterpret_cast<float*>(S.Ks4);
+    const int tid = threadIdx.x;
     if (tid < 64) {  // compact the valid slots (leading pad slots and any interior id 0 are skipped)
       const bool v = tid < D.L && D.p_ids[(size_t)u * D.ld_p_ids + tid] != 0;
       const unsigned long long m = __ballot(v);
@@ -117,56 +182,122 @@ struct CaScorer {
     }
     __syncthreads();
     nv = S.nvalid;
-    for (int idx = tid; idx < nv * DPO; idx += nthr) {
-      const int j = idx / DPO, col = idx % DPO, h = col / DHP, c = col % DHP;
-      Ks[idx] = c < dh ? D.user_k[((size_t)u * D.L + S.slot[j]) * D.ld_user_k + h * dh + c] : 0.f;
-    }
-    for (int idx = tid; idx < nv * H; idx += nthr) {
-      const int j = idx / H, h = idx % H;
-      S.Us[j][h] = D.user_u[((size_t)u * D.L + S.slot[j]) * D.ld_user_u + h];
-    }
-    __syncthreads();
-    for (int idx = tid; idx < nv * H; idx += nthr) {  // beta_hl = (M c_u W_Q^T)_h . K_hl, pre-scaled
-      const int j = idx / H, h = idx % H;
-      float b = 0.f;
-      if (D.user_q) {
-        const float* dq = D.user_q + (size_t)u * D.ld_user_q + h * dh;
-        for (int c = 0; c < dh; ++c) b = fmaf(dq[c], Ks[j * DPO + h * DHP + c], b);
-      }
-      S.Bs[h][j] = b * sc;
-    }
-    __syncthreads();
+    ca_stage_slots<DHP, H>(D, u, S.slot, nv, sc, S);
   }
 
   template <class Desc>
   __device__ __forceinline__ float logit(const Desc& D, int u, const Item& I, const User& S) const {
-    float logit = I.off;
-    if (D.user_off) logit += D.user_off[(size_t)u * D.ld_user_off];
-    if (D.ffn_b) logit += D.ffn_b[0];
+    float logit = ca_logit_offsets(D, u, I.off);
     if (nv > 0) {  // (a fully masked profile: attention term 0, carca.py:256)
 #pragma unroll
       for (int h = 0; h < H; ++h) {
         float m = -INFINITY, den = 0.f, num = 0.f;
-        for (int j = 0; j < nv; ++j) {
-          const float4* kr = S.Ks4 + (j * DPO + h * DHP) / 4;
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int c4 = 0; c4 < DHP / 4; ++c4) {
-            const float4 k4 = kr[c4];
-            s0 = fmaf(I.q[h][4 * c4], k4.x, s0);
-            s1 = fmaf(I.q[h][4 * c4 + 1], k4.y, s1);
-            s0 = fmaf(I.q[h][4 * c4 + 2], k4.z, s0);
-            s1 = fmaf(I.q[h][4 * c4 + 3], k4.w, s1);
-          }
-          const float s = fmaf(s0 + s1, sc, S.Bs[h][j]);
-          const float mn = fmaxf(m, s);
-          const float a = exp2f(m - mn), e = exp2f(s - mn);
-          den = fmaf(den, a, e);
-          num = fmaf(num, a, e * S.Us[j][h]);
-          m = mn;
-        }
+        for (int j = 0; j < nv; ++j) ca_slot_step<DHP, H>(I.q[h], S, h, j, sc, m, den, num);
         logit += num / den;
       }
+    }
+    return logit;
+  }
+};
+
+// Cross-attention decoder, profiles of up to CARCA_MAX_PROFILE_L slots: the valid slots' positions in LDS, their rows
+// staged CARCA_MAX_L at a time.  A lane keeps (m, den, num) per head across the chunks and walks the slots in ascending
+// compacted order through ca_slot_step, so each head sees the sequence of steps CaScorer::logit would run over the
+// same valid slots, and finish adds the same terms in the same order: the same logit bits.  In place of stage_user /
+// logit a kernel runs
+//   begin_user; for (c = 0; c < n_chunks(); ++c) { if (c) __syncthreads(); stage_chunk(c); accumulate(c); }  finish
+// (sweep_long_kernel in catalogue_sweep.h, rk_list_long_kernel in rank.hip).  n_chunks() is workgroup-uniform: every
+// thread computes it from the same LDS words after begin_user's barrier.
+template <int DHP, int H>
+struct CaLongScorer {
+  static constexpr bool chunked = true;
+  using Short = CaScorer<DHP, H>;
+  using Item = typename Short::Item;
+  static constexpr int ROUNDS = CARCA_MAX_PROFILE_L / TILE, WAVES = TILE / 64;
+  static_assert(ROUNDS * TILE == CARCA_MAX_PROFILE_L, "the compaction covers the profile in whole rounds");
+  struct User {
+    float4 Ks4[CARCA_MAX_L * DHP * H / 4];  // the staged chunk: K rows of CARCA_MAX_L compacted slots, head-padded
+    float Us[CARCA_MAX_L][H];
+    float Bs[H][CARCA_MAX_L];
+    int slot[CARCA_MAX_PROFILE_L];  // positions of the valid slots, ascending
+    int wcnt[ROUNDS * WAVES];       // valid slots per (round, wave) of the compaction
+  };
+  struct Acc {
+    float m[H], den[H], num[H];
+  };
+  Short base;
+  int nv;  // valid profile slots of the user begun
+
+  template <class Desc>
+  __device__ __forceinline__ explicit CaLongScorer(const Desc& D) : base(D), nv(0) {}
+
+  template <class Desc>
+  __device__ __forceinline__ void load_item(const Desc& D, int item, bool live, Item& I) const {
+    base.load_item(D, item, live, I);
+  }
+
+  // Compacts the valid slots of all D.L positions into S.slot, ROUNDS rounds of TILE positions (a constant trip count):
+  // a ballot per wave, the wave bases summed through LDS.  Whole workgroup; the caller has synchronised since the
+  // previous user's LDS was last read.  The first barrier publishes wcnt, the second slot[].
+  template <class Desc>
+  __device__ __forceinline__ void begin_user(const Desc& D, int u, User& S) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned long long mask[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const int pos = r * TILE + tid;
+      const bool v = pos < D.L && D.p_ids[(size_t)u * D.ld_p_ids + pos] != 0;
+      mask[r] = __ballot(v);
+      if (lane == 0) S.wcnt[r * WAVES + w] = __popcll(mask[r]);
+    }
+    __syncthreads();
+    // before: the valid slots ahead of this wave's share of round r; total: all of them, summed by every thread from the
+    // same LDS words, so nv is workgroup-uniform
+    int before = 0, total = 0;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+#pragma unroll
+      for (int v = 0; v < WAVES; ++v) {
+        if (v == w) before = total;
+        total += S.wcnt[r * WAVES + v];
+      }
+      if ((mask[r] >> lane) & 1ull) S.slot[before + __popcll(mask[r] & ((1ull << lane) - 1ull))] = r * TILE + tid;
+    }
+    nv = total;
+    __syncthreads();
+  }
+
+  __device__ __forceinline__ int n_chunks() const { return (nv + CARCA_MAX_L - 1) / CARCA_MAX_L; }
+  __device__ __forceinline__ int chunk_size(int c) const { return min(CARCA_MAX_L, nv - c * CARCA_MAX_L); }
+
+  // Chunk c's rows into S.  Whole workgroup; the caller has synchronised since the previous chunk was last read; ends
+  // with the barrier that publishes Bs (ca_stage_slots).
+  template <class Desc>
+  __device__ __forceinline__ void stage_chunk(const Desc& D, int u, int c, User& S) const {
+    ca_stage_slots<DHP, H>(D, u, S.slot + c * CARCA_MAX_L, chunk_size(c), base.sc, S);
+  }
+
+  __device__ __forceinline__ void reset(Acc& A) const {
+#pragma unroll
+    for (int h = 0; h < H; ++h) A.m[h] = -INFINITY, A.den[h] = 0.f, A.num[h] = 0.f;
+  }
+
+  __device__ __forceinline__ void accumulate(const Item& I, const User& S, int c, Acc& A) const {
+    const int n = chunk_size(c);
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      float m = A.m[h], den = A.den[h], num = A.num[h];
+      for (int j = 0; j < n; ++j) ca_slot_step<DHP, H>(I.q[h], S, h, j, base.sc, m, den, num);
+      A.m[h] = m, A.den[h] = den, A.num[h] = num;
+    }
+  }
+
+  template <class Desc>
+  __device__ __forceinline__ float finish(const Desc& D, int u, const Item& I, const Acc& A) const {
+    float logit = ca_logit_offsets(D, u, I.off);
+    if (nv > 0) {  // (a fully masked profile: attention term 0, carca.py:256)
+#pragma unroll
+      for (int h = 0; h < H; ++h) logit += A.num[h] / A.den[h];
     }
     return logit;
   }
@@ -175,6 +306,7 @@ struct CaScorer {
 // dot decoders
 template <int DPI>
 struct DotScorer {
+  static constexpr bool chunked = false;
   struct User {
     float4 As4[DPI / 4], Ms4[DPI / 4];
     float am_mm[2];

@@ -199,6 +199,23 @@ def cross_block(dec, o: Tensor, o_ids: Tensor, p_n: Tensor, p_ids: Tensor, seed:
     return torch.sigmoid(logit)
 
 
+def encode(model, x: Tensor, p_x: Tensor, seed: int = 0, sink=None, trace: Optional[dict] = None) -> Tensor:
+    """The encoder of CARCA.forward (carca.py:416-421) on the embedded profile x [B, L, d]: the embedding dropout (training),
+    every SelfAttentionBlock, the final LayerNorm -> p_n [B, L, d].  forward below and the profile side of the catalogue
+    calls (catalogue.carca_model_side, under no_grad in eval mode) both run it."""
+    if model.training and model.dropout.p > 0:  # carca.py:416
+        x = _DropoutFn.apply(x, float(model.dropout.p), seed, 1000, sink, ("embed",))
+    for i, blk in enumerate(model.encoder):
+        blk._check_mode()
+        x = sa_block(blk, x, p_x, seed, 4 * i, sink, i)
+        if trace is not None:
+            trace[f"block{i}"] = x
+    p_n = _norm(x, model.norm)  # carca.py:421
+    if trace is not None:
+        trace["p_final"] = p_n
+    return p_n
+
+
 def forward(model, profile, targets, trace: Optional[dict] = None) -> List[Tensor]:
     """CARCA.forward (carca.py:411-431) for any profile length: the groups' scores [B, N_g] (not yet squeezed / joined)."""
     from .modules import CrossAttentionBlock, cached_parameters, note_training_forward
@@ -233,16 +250,7 @@ def forward(model, profile, targets, trace: Optional[dict] = None) -> List[Tenso
         trace["p_embed"] = x
         for gi in range(len(targets)):
             trace[f"o_embed{gi}"] = es[gi + 1]
-    if training and model.dropout.p > 0:  # carca.py:416
-        x = _DropoutFn.apply(x, float(model.dropout.p), seed, 1000, sink, ("embed",))
-    for i, blk in enumerate(model.encoder):
-        blk._check_mode()
-        x = sa_block(blk, x, p_x, seed, 4 * i, sink, i)
-        if trace is not None:
-            trace[f"block{i}"] = x
-    p_n = _norm(x, model.norm)  # carca.py:421
-    if trace is not None:
-        trace["p_final"] = p_n
+    p_n = encode(model, x, p_x, seed, sink, trace)
     if isinstance(dec, CrossAttentionBlock):
         ys = [cross_block(dec, es[gi + 1], targets[gi][0], p_n, p_x, seed, 2000 + gi, sink, gi) for gi in range(len(targets))]
     else:

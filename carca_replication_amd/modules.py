@@ -1333,7 +1333,7 @@ class CARCA(_PackedModule, Model):
 
     # ---- full-catalogue top-k and ranks (include/carca_hip.h: carca_recommend / carca_rank_items) -
     def recommend(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
-                  exclude="profile", candidates=None) -> Tuple[Tensor, Tensor]:
+                  exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
         """The k best items of the whole catalogue per user: (scores [B, k] float32, ids [B, k] int64), best first.
 
         Scores equal what forward(profile, [(ids, attrs, context broadcast)]) returns for those items (eval mode: the
@@ -1348,17 +1348,23 @@ class CARCA(_PackedModule, Model):
         built for this model's n_items, or a raw 1-D integer tensor / bool mask [n_items], which builds one for this call
         and so costs a host sync per call.  The result is then the k best items of S minus the excluded ones, in the same
         order and with the same padding; a returned item's score is bit-identical to the unrestricted call's for that
-        (user, item), and time and scratch ([B, |S|]) follow |S|, not n_items.  An empty S returns all zeros."""
+        (user, item), and time and scratch ([B, |S|]) follow |S|, not n_items.  An empty S returns all zeros.
+
+        allow_composed=True widens the envelope to what forward takes at d <= 128: L up to 1024 and any encoder head
+        count, the profile side then running long_profile's composed encoder (several times slower per user than the
+        fused blocks); the dot decoders at every (d, H), a cross-attention decoder at its built (d, H) geometries (past
+        64 slots the sweep stages a user's valid slots 64 at a time: DESIGN.md section 19).  Inside the fused envelope
+        the keyword changes nothing."""
         if self.training:
             raise CarcaHipError("recommend: the model is in training mode; recommendation scores with eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
         return catalogue.recommend("recommend", _lib.RecommendDesc, "carca_recommend",
                                    partial(catalogue.carca_model_side, self, profile, context), profile, k, exclude,
-                                   candidates)
+                                   candidates, allow_composed)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
-                   exclude="profile", candidates=None) -> Tuple[Tensor, Tensor]:
+                   exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
         """Exact full-catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64).
 
         items: an int32 / int64 [B, N] tensor, 1 <= N <= 128.  ranks[u, j] is the 0-based number of ELIGIBLE catalogue
@@ -1371,14 +1377,16 @@ class CARCA(_PackedModule, Model):
         candidates: as recommend's.  With a set S, ranks[u, j] counts the eligible items OF S (in S, not excluded) that
         come before items[u, j] -- the position recommend(candidates=S) would give it; a target outside S, like an
         excluded or repeated one, still gets the position it would take, and with an empty S every valid target has
-        rank 0.  scores keep their meaning and their bits."""
+        rank 0.  scores keep their meaning and their bits.
+
+        allow_composed: as recommend's."""
         if self.training:
             raise CarcaHipError("rank_items: the model is in training mode; ranks use eval semantics "
                                 "(call model.eval() first)")
         self._check_built()
         return catalogue.rank_items("rank_items", _lib.RankDesc, "carca_rank_items",
                                     partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude,
-                                    candidates)
+                                    candidates, allow_composed)
 
     # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md 17) ---------------------------------
     def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,

@@ -123,6 +123,15 @@ def _candidate_set(model, method: str, candidates, device):
     return candidates.to(device)
 
 
+def _wide_envelope(model, method: str) -> dict:
+    """The keyword that lets CARCA.recommend / rank_items take profiles of more than 64 slots and encoder geometries
+    with no fused kernel (allow_composed=True; inside the fused envelope it routes to the same kernels), for a model
+    whose `method` has it (KNN has no such limit and no such keyword)."""
+    import inspect
+
+    return {"allow_composed": True} if "allow_composed" in inspect.signature(getattr(model, method)).parameters else {}
+
+
 def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candidates=None) -> Tuple[float, float]:
     """(HR@k, NDCG@k) with the positive o_x[:, 0] ranked against EVERY item of the catalogue instead of the loader's
     sampled negatives (full-ranking protocol; Krichene & Rendle, KDD 2020).  Per batch: model.recommend (CARCA.recommend or
@@ -134,6 +143,7 @@ def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candida
     sums and of the user count (membership is tested on the device, no extra sync)."""
     model = model.eval().to(device)
     cand = _candidate_set(model, "recommend", candidates, device)
+    wide = _wide_envelope(model, "recommend")
     sums = torch.zeros(3, dtype=torch.float32, device=device)
     with torch.no_grad():
         for batch in loader:
@@ -141,10 +151,10 @@ def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candida
             pos = o_x[:, :1].to(torch.int64)
             excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
             if cand is None:
-                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl)
+                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl, **wide)
                 users = ids.shape[0]
             else:  # (a positive outside S is never in the list: it only has to leave the user count)
-                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl, candidates=cand)
+                _, ids = model.recommend((p_x, p_a, p_c), o_c[:, 0], k=k, exclude=excl, candidates=cand, **wide)
                 users = cand.contains(pos).sum()
             hit = ids == pos
             rank = torch.arange(k, device=ids.device, dtype=torch.float32).expand_as(ids)
@@ -207,6 +217,7 @@ def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5,
     ks = _check_ks(ks)
     model = model.eval().to(device)
     cand = _candidate_set(model, "rank_items", candidates, device)
+    wide = _wide_envelope(model, "rank_items")
     sums = torch.zeros(2 * len(ks) + 3, dtype=torch.float64, device=device)
     with torch.no_grad():
         for batch in loader:
@@ -214,9 +225,9 @@ def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5,
             pos = o_x[:, :1].to(torch.int64)
             excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
             if cand is None:
-                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl)
+                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl, **wide)
             else:
-                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl, candidates=cand)
+                _, ranks = model.rank_items((p_x, p_a, p_c), o_c[:, 0], pos, exclude=excl, candidates=cand, **wide)
                 ranks = torch.where(cand.contains(pos), ranks, torch.full_like(ranks, -1))  # (_rank_sums skips them)
             sums += _rank_sums(ranks, ks)
     out = _metrics_from_sums(sums, ks)

@@ -36,6 +36,7 @@ extern "C" {
 #define CARCA_MAX_SEGS 4   /* profile + up to 3 target groups per embed call */
 #define CARCA_MAX_GROUPS 3 /* target groups per scoring call (train: pos, neg) */
 #define CARCA_MAX_L 64     /* profile slots one workgroup keeps in LDS */
+#define CARCA_MAX_PROFILE_L 1024 /* profile slots of carca_recommend / carca_rank_items (staged CARCA_MAX_L at a time) */
 #define CARCA_EMBED_GATHER 1
 #define CARCA_EMBED_FEAT 2
 #define CARCA_EMBED_JOINT 4
@@ -845,8 +846,11 @@ int carca_rank_metrics(const float* y /*[B,N]*/, int B, int N, int k, const int3
  * decoder 2) -- what the model's forward returns for that item.  Ties go to the smaller id; id 0 and the nonzero entries of
  * exclude [B, n_exclude] (int32, 0 = no entry, duplicates allowed) are never selected; fewer than k eligible items pad
  * with id 0 and score 0.  Bit-identical run to run (no float atomics).  Logits of the B x n_items pairs live in stream
- * scratch.  CARCA_ERR_UNSUPPORTED: L > CARCA_MAX_L, k > 128, d > 128 or d % H != 0, a cross-attention (d, H) with no
- * kernel built.  CARCA_ERR_BADARG: null pointers, strides shorter than a row, ld_item_q / ld_user_k / ld_user_q /
+ * scratch.  L may be up to CARCA_MAX_PROFILE_L: the dot decoders read only the scored row; decoder 0 keeps a user's valid
+ * slots in LDS whole up to CARCA_MAX_L, and beyond walks them CARCA_MAX_L at a time with the same per-slot arithmetic in the
+ * same order, so a (user, item) logit depends on the user's valid slots and not on L or on where the pad slots lie
+ * (DESIGN.md section 19).  exclude may then be as wide as the profile.  CARCA_ERR_UNSUPPORTED: L > CARCA_MAX_PROFILE_L,
+ * k > 128, d > 128 or d % H != 0, a cross-attention (d, H) with no kernel built.  CARCA_ERR_BADARG: null pointers, strides shorter than a row, ld_item_q / ld_user_k / ld_user_q /
  * ld_user_m not multiples of 4. */
 typedef struct CarcaRecommendDesc {
   int B, L, n_items, d, H, k;
@@ -889,7 +893,8 @@ int carca_recommend(const CarcaRecommendDesc* desc, void* stream);
  * Three launches, no host wait, nothing retained: the listed and excluded items are scored; a sweep over the catalogue
  * counts per (user, target) the items ordering before the target with integer atomics into a zeroed counter (no
  * [B, n_items] buffer); a correction subtracts the distinct excluded ids that order before it.  Bit-identical run to
- * run.  Scratch: stream scratch, or the capture's memory.  CARCA_ERR_UNSUPPORTED as carca_recommend, and n_list outside
+ * run.  Scratch: stream scratch, or the capture's memory.  L up to CARCA_MAX_PROFILE_L as carca_recommend (the list is then
+ * scored in rounds of 256 entries, the profile staged again in each).  CARCA_ERR_UNSUPPORTED as carca_recommend, and n_list outside
  * 1..128.  CARCA_ERR_BADARG as carca_recommend, and null items / scores / ranks or strides shorter than n_list. */
 typedef struct CarcaRankDesc {
   int B, L, n_items, d, H;
@@ -940,8 +945,8 @@ int carca_rank_items(const CarcaRankDesc* desc, void* stream);
  * outside [0, n_items): rank -1 and score 0.  scores as carca_rank_items.  The counting sweep runs over S; the correction
  * subtracts only the distinct excluded ids that S holds.
  *
- * Cost falls with n: the sweep's grid, the scratch and the selection cover n positions, not n_items.  Errors as the
- * unrestricted calls, and CARCA_ERR_BADARG for a null list, n < 0, or null ids with n > 0. */
+ * Cost falls with n: the sweep's grid, the scratch and the selection cover n positions, not n_items.  Limits (L up to
+ * CARCA_MAX_PROFILE_L) and errors as the unrestricted calls, and CARCA_ERR_BADARG for a null list, n < 0, or null ids with n > 0. */
 typedef struct CarcaCandidates {
   const int32_t* ids; /* [n] ascending, distinct, in [1, n_items) */
   int n;
