@@ -311,7 +311,7 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
 
 # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items) ------------------------------
 SIMILAR_METRICS = {"dot": 0, "cosine": 1}  # CARCA_SIMILAR_DOT, CARCA_SIMILAR_COSINE
-SIMILAR_BLOCK = 64  # queries per scoring workgroup (csrc: SI_QB): the granule of a chunk
+SIMILAR_BLOCK = 64  # queries per scoring workgroup (csrc: rs::QB): the granule of a chunk
 
 
 def similar_chunk_rows(max_scratch_bytes: int, n_columns: int) -> int:

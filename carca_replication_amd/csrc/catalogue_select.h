@@ -1,6 +1,6 @@
 // The exclusion and selection launches of a full-catalogue top-k over a [B, n_items] buffer of raw logits, shared by
-// carca_recommend (recommend.hip) and carca_knn_recommend (knn_catalogue.hip).  Desc is the caller's descriptor, or a view
-// with these fields: n_items, k, decoder, exclude / n_exclude / ld_exclude, scores / ld_scores, ids_out / ld_ids_out.
+// carca_recommend (recommend.hip), carca_knn_recommend (knn_catalogue.hip) and carca_similar_items (similar_items.hip).
+// Desc is the caller's descriptor, or a view (SelectView) with these fields: n_items, k, decoder, exclude / n_exclude / ld_exclude, scores / ld_scores, ids_out / ld_ids_out.
 // `decoder` picks the link applied to the k selected logits: an int (recommend_common.h: rc::link) or rc::IdentityLink
 // (the raw logit, for models without a link).  Keys are built and taken apart by recommend_common.h's helpers
 // (rc::order_key, rc::key_id); an item whose order bits are 0 holds the exclusion sentinel and is skipped.
@@ -17,6 +17,19 @@ constexpr unsigned RC_SENTINEL = 0xFFFFFFFFu;  // a negative NaN pattern no arit
 
 struct IdentityLink {};
 __device__ __forceinline__ float link(float y, IdentityLink) { return y; }
+
+// the view of a caller without a model descriptor (knn_catalogue.hip, similar_items.hip): no link; the exclusion fields
+// stay zero where the caller has no exclusion launch
+struct SelectView {
+  int n_items, k;
+  IdentityLink decoder;
+  const int32_t* exclude;
+  int n_exclude, ld_exclude;
+  float* scores;
+  int ld_scores;
+  int64_t* ids_out;
+  int ld_ids_out;
+};
 
 // ---- exclusion ----------------------------------------------------------------------------------------------
 template <class Desc, class Map = AllItems>

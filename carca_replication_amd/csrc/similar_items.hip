@@ -6,7 +6,7 @@
 //   score = X[q] . X[i]                       ("dot")
 //   score = ((X[q] . X[i]) * r_q) * r_i       ("cosine"), r = 1 / max(||row||, 1e-12) from carca_row_rnorm
 // Columns are item ids (rc::AllItems, C = n_items) or positions in an ascending candidate list (rc::ListedItems, C = n):
-// the listed rows and their r are first copied into a compact [C, ld_cand] table (si_gather_kernel) and the same scoring
+// the listed rows and their r are first copied into a compact [C, ld_cand] table (rs::gather_kernel) and the same scoring
 // kernels run over it, so a pair's score bits do not depend on the list, on the query's position or on the chunk.
 // Launches per chunk: (gather, first chunk of a call with a list), scoring, selection.  The scoring epilogue writes the
 // selection's sentinel into the id-0 column (no list), into the query's own column (exclude_self) and into every column of
@@ -15,42 +15,24 @@
 //   n_cols <= 128: query-stationary.  Each wave loads the A operands of the 64 query rows once (KP / 4 registers per
 //     16-query block, KP = 64 / 96 / 128 the padded width) and streams 16-item tiles through them: only item rows and
 //     the r vectors are read in the loop.  The tiles go round-robin over the waves of the workgroups of a query block.
-//   n_cols > 128: knn_catalogue.hip's streaming loop (operands re-read from a gathered, zero-padded query buffer at
-//     every 64-byte step, MFMA chains folded every 256 k) with this file's epilogue.
+//   n_cols > 128: rs::score_kernel (row_stream.h), the streaming loop KNN's catalogue calls run too (operands re-read
+//     from a gathered, zero-padded query buffer at every 64-byte step, MFMA chains folded every 256 k), with this
+//     file's prologue and epilogue.
 // Item rows come through buffer loads whose wave-uniform base carries the 64-bit row offset: lane offsets stay below 16
 // rows, loads past the last row return 0, and no column past n_cols reaches a product (masked after the load).
 #include "catalogue_select.h"
+#include "row_stream.h"
 
 namespace {
 
-constexpr int SI_THREADS = 256;
-constexpr int SI_WAVES = SI_THREADS / 64;
-constexpr int SI_MQ = 4;              // 16-query blocks per workgroup
-constexpr int SI_QB = 16 * SI_MQ;     // queries per workgroup
 constexpr int SI_STAT_MAX = 128;      // widest row of the query-stationary kernel
-constexpr int SI_UNROLL = 4;          // streaming: 64-byte row chunks in flight per operand
-constexpr int SI_FOLD = 16;           // streaming: chunks per MFMA chain
 constexpr int SI_SELF_NONE = -1;      // no column to blank for this query
 constexpr int SI_SELF_INVALID = -2;   // the query id is outside [1, n_items): every column blanked
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t si_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-// the fields the selection launch reads (catalogue_select.h), with no link
-struct SiSelect {
-  int n_items, k;
-  rc::IdentityLink decoder;
-  float* scores;
-  int ld_scores;
-  int64_t* ids_out;
-  int ld_ids_out;
-};
-
 // ---- reciprocal row norms: one wave per row -----------------------------------------------------------------------
-__global__ __launch_bounds__(SI_THREADS) void si_rnorm_kernel(const float* __restrict__ table, int64_t ld, int n_rows,
+__global__ __launch_bounds__(rs::THREADS) void si_rnorm_kernel(const float* __restrict__ table, int64_t ld, int n_rows,
                                                               int n_cols, float* __restrict__ out) {
-  const int row = blockIdx.x * SI_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int row = blockIdx.x * rs::WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n_rows) return;
   const float* x = table + (size_t)row * ld;
   float s = 0.f;
@@ -59,31 +41,24 @@ __global__ __launch_bounds__(SI_THREADS) void si_rnorm_kernel(const float* __res
   if (lane == 0) out[row] = 1.f / fmaxf(sqrtf(s), 1e-12f);
 }
 
-// ---- row gather: dst[u] = src[ids[u]] over the live columns, zero past them and for an id outside [1, n_src) ------
-struct SiGather {
+// ---- the row source of rs::gather_kernel: src[ids[u]], a zero row for an id outside [1, n_src) and past the n ids;
+// thread 0 also copies the row's r where the caller asks for it
+struct SiRow {
   const float* src;
   int64_t ld_src;
-  int n_src, n_cols;
+  int n_src;
   const float* rn_src;  // or NULL
   const int32_t* ids;
-  int n;  // ids; rows n .. gridDim.x - 1 of dst are zero rows
-  float* dst;
-  int64_t ld_dst;
+  int n;
   float* rn_dst;  // [n] or NULL
-};
-
-__global__ __launch_bounds__(SI_THREADS) void si_gather_kernel(SiGather G) {
-  const int u = blockIdx.x;
-  const float* src = nullptr;
-  int id = 0;
-  if (u < G.n) {
-    id = G.ids[u];
-    if (id >= 1 && id < G.n_src) src = G.src + (size_t)id * G.ld_src;
+  __device__ const float* operator()(int u) const {
+    if (u >= n) return nullptr;
+    const int id = ids[u];
+    const float* row = id >= 1 && id < n_src ? src + (size_t)id * ld_src : nullptr;
+    if (rn_dst && threadIdx.x == 0) rn_dst[u] = (row && rn_src) ? rn_src[id] : 0.f;
+    return row;
   }
-  float* dst = G.dst + (size_t)u * G.ld_dst;
-  for (int k = threadIdx.x; k < G.ld_dst; k += SI_THREADS) dst[k] = (src && k < G.n_cols) ? src[k] : 0.f;
-  if (G.rn_dst && u < G.n && threadIdx.x == 0) G.rn_dst[u] = (src && G.rn_src) ? G.rn_src[id] : 0.f;
-}
+};
 
 // ---- scoring -------------------------------------------------------------------------------------------------------
 struct SiScore {
@@ -104,15 +79,15 @@ struct SiScore {
 };
 
 struct SiQueries {  // per query of the workgroup's block
-  alignas(16) float rq[SI_QB];
-  int self[SI_QB];
+  alignas(16) float rq[rs::QB];
+  int self[rs::QB];
 };
 
 // Workgroup prologue: r_q and the column to blank of each of the block's 64 queries.  Ends with a barrier.
 template <class Map>
 __device__ __forceinline__ void si_stage_queries(const SiScore& P, int q0, const Map& map, SiQueries& S) {
   const int t = threadIdx.x;
-  if (t < SI_QB) {
+  if (t < rs::QB) {
     const int q = q0 + t;
     const int id = q < P.Q ? P.items[q] : 0;
     const bool valid = id >= 1 && id < P.n_items;
@@ -124,14 +99,14 @@ __device__ __forceinline__ void si_stage_queries(const SiScore& P, int q0, const
 
 // One 16-item x 64-query tile out of the accumulators: D holds column (item) r, rows (queries) 4g .. 4g + 3 of each block.
 template <class Map>
-__device__ __forceinline__ void si_epilogue(const SiScore& P, const f32x4 (&acc)[SI_MQ], int q0, int col, int g,
+__device__ __forceinline__ void si_epilogue(const SiScore& P, const f32x4 (&acc)[rs::MQ], int q0, int col, int g,
                                             const SiQueries& S) {
   if (col >= P.C) return;
   const float ri = P.cosine ? P.crn[col] : 0.f;
   const float sent = __uint_as_float(rc::RC_SENTINEL);
   const bool pad_col = !Map::listed && col == 0;  // id 0 is the padding item; no list holds it
 #pragma unroll
-  for (int m = 0; m < SI_MQ; ++m) {
+  for (int m = 0; m < rs::MQ; ++m) {
     const f32x4 rq = *reinterpret_cast<const f32x4*>(&S.rq[16 * m + 4 * g]);
     const int* self = &S.self[16 * m + 4 * g];
 #pragma unroll
@@ -146,28 +121,32 @@ __device__ __forceinline__ void si_epilogue(const SiScore& P, const f32x4 (&acc)
   }
 }
 
-// the lane's four k of chunk c, zero where k >= n_cols (lim = n_cols - 4g)
-__device__ __forceinline__ f32x4 si_mask(u32x4 v, int c, int lim) {
-  f32x4 f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[j] = (16 * c + j < lim) ? __uint_as_float(v[j]) : 0.f;
-  return f;
-}
+// rs::score_kernel's epilogue for the streaming case (n_cols > 128)
+template <class Map>
+struct SiStream {
+  SiScore P;
+  Map map;
+  typedef SiQueries Shared;
+  __device__ void stage(int q0, Shared& S) const { si_stage_queries(P, q0, map, S); }
+  __device__ void store(const f32x4 (&tile)[rs::MQ], int q0, int col, int g, const Shared& S) const {
+    si_epilogue<Map>(P, tile, q0, col, g, S);
+  }
+};
 
 template <int KP, class Map>
-__global__ __launch_bounds__(SI_THREADS) void si_score_stationary_kernel(SiScore P, Map map) {
+__global__ __launch_bounds__(rs::THREADS) void si_score_stationary_kernel(SiScore P, Map map) {
   constexpr int NCH = KP / 16;
   __shared__ SiQueries S;
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int qb = blockIdx.x % P.nqb, split = blockIdx.x / P.nqb;
-  const int q0 = qb * SI_QB;
+  const int q0 = qb * rs::QB;
   si_stage_queries(P, q0, map, S);
   const int lim = P.n_cols - 4 * g;
   // A operands: chunk c of query row 16m + r, bytes 64c + 16g .. +15, zero for an invalid query
-  f32x4 a[NCH][SI_MQ];
+  f32x4 a[NCH][rs::MQ];
 #pragma unroll
-  for (int m = 0; m < SI_MQ; ++m) {
+  for (int m = 0; m < rs::MQ; ++m) {
     const int q = q0 + 16 * m + r;
     const int id = q < P.Q ? P.items[q] : 0;
     const bool valid = id >= 1 && id < P.n_items;
@@ -177,31 +156,31 @@ __global__ __launch_bounds__(SI_THREADS) void si_score_stationary_kernel(SiScore
       a[c][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (valid && 16 * c < lim) {  // (ld is a multiple of 4: the 16 bytes stay inside the row's stride)
         const u32x4 v = *reinterpret_cast<const u32x4*>(row + 16 * c + 4 * g);
-        a[c][m] = si_mask(v, c, lim);
+        a[c][m] = rs::mask4(v, c, lim);
       }
     }
   }
-  const int t_end = P.tiles, t_step = P.nsplit * SI_WAVES;
+  const int t_end = P.tiles, t_step = P.nsplit * rs::WAVES;
   const int t_off = (r * P.cld + 4 * g) * 4;
   auto load_tile = [&](int t, f32x4 (&b)[NCH]) {
     const int i0 = t * 16, rows = min(16, P.C - i0);
-    const auto tr = si_rsrc(P.ctable + (size_t)i0 * P.cld, (unsigned)rows * P.cld * 4);
+    const auto tr = rs::rsrc(P.ctable + (size_t)i0 * P.cld, (unsigned)rows * P.cld * 4);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) b[c] = si_mask(__builtin_amdgcn_raw_buffer_load_b128(tr, t_off, c * 64, 0), c, lim);
+    for (int c = 0; c < NCH; ++c) b[c] = rs::mask4(__builtin_amdgcn_raw_buffer_load_b128(tr, t_off, c * 64, 0), c, lim);
   };
   auto score_tile = [&](int t, const f32x4 (&b)[NCH]) {
-    f32x4 acc[SI_MQ];
+    f32x4 acc[rs::MQ];
 #pragma unroll
-    for (int m = 0; m < SI_MQ; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < rs::MQ; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
-      for (int m = 0; m < SI_MQ; ++m) acc[m] = mfma16_group(a[c][m], b[c], acc[m]);
+      for (int m = 0; m < rs::MQ; ++m) acc[m] = mfma16_group(a[c][m], b[c], acc[m]);
     si_epilogue<Map>(P, acc, q0, t * 16 + r, g, S);
   };
   // Tiles go round-robin over the waves of the nsplit workgroups of a query block: at any time they write one window of
   // nsplit x 64 neighbouring columns per query row.  The next tile's rows are in flight under this tile's products.
-  int t = split * SI_WAVES + wave;
+  int t = split * rs::WAVES + wave;
   f32x4 b0[NCH], b1[NCH];
   if (t < t_end) load_tile(t, b0);
   while (t < t_end) {
@@ -215,83 +194,26 @@ __global__ __launch_bounds__(SI_THREADS) void si_score_stationary_kernel(SiScore
   }
 }
 
-// Operand chunk c of a row is its bytes 64c .. 64c + 63: lane (r, g) holds bytes 64c + 16g .. +15 of query row r (A
-// operand) and item row r (B operand).  Each wave owns 16 items x 64 queries.
-template <class Map>
-__global__ __launch_bounds__(SI_THREADS) void si_score_streaming_kernel(SiScore P, Map map) {
-  __shared__ SiQueries S;
-  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int qb = blockIdx.x % P.nqb, it = blockIdx.x / P.nqb;
-  const int q0 = qb * SI_QB, i0 = it * (16 * SI_WAVES) + wave * 16;
-  si_stage_queries(P, q0, map, S);
-  const int lim = P.n_cols - 4 * g;
-  const int rows = max(0, min(16, P.C - i0));
-  const auto tr = si_rsrc(P.ctable + (size_t)i0 * P.cld, (unsigned)rows * P.cld * 4);
-  const auto qr = si_rsrc(P.qbuf + (size_t)q0 * P.ldq, (unsigned)SI_QB * P.ldq * 4);
-  const int t_off = (r * P.cld + 4 * g) * 4;
-  int q_off[SI_MQ];
-#pragma unroll
-  for (int m = 0; m < SI_MQ; ++m) q_off[m] = ((16 * m + r) * P.ldq + 4 * g) * 4;
-  auto load_t = [&](int c) -> f32x4 { return si_mask(__builtin_amdgcn_raw_buffer_load_b128(tr, t_off, c * 64, 0), c, lim); };
-  auto load_q = [&](int m, int c) -> f32x4 {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(qr, q_off[m], c * 64, 0);
-    return (f32x4){__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-  };
-  // the MFMA chain restarts every SI_FOLD chunks (256 k) and is added into `tot`: two short sums, not one long chain
-  f32x4 acc[SI_MQ], tot[SI_MQ];
-#pragma unroll
-  for (int m = 0; m < SI_MQ; ++m) acc[m] = tot[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto fold = [&]() {
-#pragma unroll
-    for (int m = 0; m < SI_MQ; ++m) tot[m] += acc[m], acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  };
-  int c = 0;
-  for (; c + SI_UNROLL <= P.nchunks; c += SI_UNROLL) {
-    f32x4 t[SI_UNROLL], q[SI_UNROLL][SI_MQ];
-#pragma unroll
-    for (int j = 0; j < SI_UNROLL; ++j) {
-      t[j] = load_t(c + j);
-#pragma unroll
-      for (int m = 0; m < SI_MQ; ++m) q[j][m] = load_q(m, c + j);
-    }
-#pragma unroll
-    for (int j = 0; j < SI_UNROLL; ++j)
-#pragma unroll
-      for (int m = 0; m < SI_MQ; ++m) acc[m] = mfma16_group(q[j][m], t[j], acc[m]);
-    if ((c + SI_UNROLL) % SI_FOLD == 0) fold();
-  }
-  for (; c < P.nchunks; ++c) {
-    const f32x4 t = load_t(c);
-#pragma unroll
-    for (int m = 0; m < SI_MQ; ++m) acc[m] = mfma16_group(load_q(m, c), t, acc[m]);
-  }
-  fold();
-  si_epilogue<Map>(P, tot, q0, i0 + r, g, S);
-}
-
 template <class Map>
 int si_launch_score(const SiScore& P0, const Map& map, hipStream_t stream) {
   SiScore P = P0;
-  if (P.n_cols <= SI_STAT_MAX) {
-    // enough workgroups to fill the device, each wave keeping at least 2 tiles under its A operands where the range allows
-    const int want = (1024 + P.nqb - 1) / P.nqb;
-    const int most = (P.tiles + 2 * SI_WAVES - 1) / (2 * SI_WAVES);
-    P.nsplit = max(1, min(want, most));
-    const long long blocks = (long long)P.nqb * P.nsplit;
-    CARCA_CHECK_SUPPORTED(blocks < (1ll << 31), "similar_items: %lld scoring workgroups", blocks);
-    const dim3 grid((unsigned)blocks), block(SI_THREADS);
-    if (P.n_cols <= 64)
-      hipLaunchKernelGGL((si_score_stationary_kernel<64, Map>), grid, block, 0, stream, P, map);
-    else if (P.n_cols <= 96)
-      hipLaunchKernelGGL((si_score_stationary_kernel<96, Map>), grid, block, 0, stream, P, map);
-    else
-      hipLaunchKernelGGL((si_score_stationary_kernel<128, Map>), grid, block, 0, stream, P, map);
-  } else {
-    const long long blocks = (long long)P.nqb * ((P.C + 16 * SI_WAVES - 1) / (16 * SI_WAVES));
-    CARCA_CHECK_SUPPORTED(blocks < (1ll << 31), "similar_items: %lld scoring workgroups", blocks);
-    hipLaunchKernelGGL((si_score_streaming_kernel<Map>), dim3((unsigned)blocks), dim3(SI_THREADS), 0, stream, P, map);
+  if (P.n_cols > SI_STAT_MAX) {
+    const rs::Operands R = {P.ctable, P.cld, P.qbuf, P.ldq, P.C, P.n_cols, P.nchunks, P.nqb};
+    return rs::launch_score<rs::F32Aligned>(R, SiStream<Map>{P, map}, "similar_items", stream);
   }
+  // enough workgroups to fill the device, each wave keeping at least 2 tiles under its A operands where the range allows
+  const int want = (1024 + P.nqb - 1) / P.nqb;
+  const int most = (P.tiles + 2 * rs::WAVES - 1) / (2 * rs::WAVES);
+  P.nsplit = max(1, min(want, most));
+  const long long blocks = (long long)P.nqb * P.nsplit;
+  CARCA_CHECK_SUPPORTED(blocks < (1ll << 31), "similar_items: %lld scoring workgroups", blocks);
+  const dim3 grid((unsigned)blocks), block(rs::THREADS);
+  if (P.n_cols <= 64)
+    hipLaunchKernelGGL((si_score_stationary_kernel<64, Map>), grid, block, 0, stream, P, map);
+  else if (P.n_cols <= 96)
+    hipLaunchKernelGGL((si_score_stationary_kernel<96, Map>), grid, block, 0, stream, P, map);
+  else
+    hipLaunchKernelGGL((si_score_stationary_kernel<128, Map>), grid, block, 0, stream, P, map);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
@@ -303,7 +225,7 @@ size_t si_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
 extern "C" int carca_row_rnorm(const float* table, int ld, int n_rows, int n_cols, float* out, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   CARCA_CHECK_ARG(table && out && n_rows >= 1 && n_cols >= 1 && ld >= n_cols, "row_rnorm: null pointer, empty table or ld < n_cols");
-  hipLaunchKernelGGL(si_rnorm_kernel, dim3((n_rows + SI_WAVES - 1) / SI_WAVES), dim3(SI_THREADS), 0, stream, table,
+  hipLaunchKernelGGL(si_rnorm_kernel, dim3((n_rows + rs::WAVES - 1) / rs::WAVES), dim3(rs::THREADS), 0, stream, table,
                      (int64_t)ld, n_rows, n_cols, out);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
@@ -336,19 +258,18 @@ extern "C" int carca_similar_items(const CarcaSimilarDesc* desc, const CarcaCand
                     "and, for cosine, cand_rnorm");
   }
   const bool streaming = D.n_cols > SI_STAT_MAX;
-  const int nqb = (D.Q + SI_QB - 1) / SI_QB;
+  const int nqb = (D.Q + rs::QB - 1) / rs::QB;
   const int ldq = round_up(D.n_cols, 16);  // a whole number of 64-byte chunks
   const size_t out_bytes = si_align((size_t)D.Q * (size_t)C * sizeof(float));
-  const size_t q_bytes = streaming ? si_align((size_t)nqb * SI_QB * ldq * sizeof(float)) : 0;
+  const size_t q_bytes = streaming ? si_align((size_t)nqb * rs::QB * ldq * sizeof(float)) : 0;
   const size_t bytes = out_bytes + q_bytes;
   char* base = (char*)(carca_stream_capturing(stream) ? carca_capture_alloc(stream, bytes, false, nullptr)
                                                       : carca_stream_scratch(stream, CARCA_SCRATCH_SIMILAR, bytes));
   CARCA_CHECK_ARG(base, "similar_items: scratch allocation of %zu bytes failed", bytes);
   if (cand && D.gather_candidates) {
-    SiGather G;
-    G.src = D.table, G.ld_src = D.ld_table, G.n_src = D.n_items, G.n_cols = D.n_cols, G.rn_src = D.rnorm;
-    G.ids = cand->ids, G.n = C, G.dst = D.cand_table, G.ld_dst = D.ld_cand_table, G.rn_dst = D.cand_rnorm;
-    hipLaunchKernelGGL(si_gather_kernel, dim3(C), dim3(SI_THREADS), 0, stream, G);
+    const SiRow src = {D.table, D.ld_table, D.n_items, D.rnorm, cand->ids, C, D.cand_rnorm};
+    hipLaunchKernelGGL((rs::gather_kernel<float, SiRow>), dim3(C), dim3(rs::THREADS), 0, stream, src, D.n_cols, D.cand_table,
+                       D.ld_cand_table);
     CARCA_LAUNCH_CHECK();
   }
   SiScore P = {};
@@ -359,27 +280,27 @@ extern "C" int carca_similar_items(const CarcaSimilarDesc* desc, const CarcaCand
   P.cosine = D.metric == CARCA_SIMILAR_COSINE, P.exclude_self = D.exclude_self != 0;
   P.nqb = nqb, P.tiles = (C + 15) / 16, P.out = (float*)base;
   if (streaming) {
-    SiGather G;
-    G.src = D.table, G.ld_src = D.ld_table, G.n_src = D.n_items, G.n_cols = D.n_cols, G.rn_src = nullptr;
-    G.ids = D.items, G.n = D.Q, G.dst = (float*)(base + out_bytes), G.ld_dst = ldq, G.rn_dst = nullptr;
-    hipLaunchKernelGGL(si_gather_kernel, dim3(nqb * SI_QB), dim3(SI_THREADS), 0, stream, G);
+    float* qbuf = (float*)(base + out_bytes);
+    const SiRow src = {D.table, D.ld_table, D.n_items, nullptr, D.items, D.Q, nullptr};
+    hipLaunchKernelGGL((rs::gather_kernel<float, SiRow>), dim3(nqb * rs::QB), dim3(rs::THREADS), 0, stream, src, D.n_cols,
+                       qbuf, ldq);
     CARCA_LAUNCH_CHECK();
-    P.qbuf = G.dst, P.ldq = ldq, P.nchunks = ldq / 16;
+    P.qbuf = qbuf, P.ldq = ldq, P.nchunks = ldq / 16;
   }
-  SiSelect S;
+  rc::SelectView S = {};
   S.n_items = D.n_items, S.k = D.k, S.scores = D.scores, S.ld_scores = D.ld_scores, S.ids_out = D.ids_out;
   S.ld_ids_out = D.ld_ids_out;
   if (cand) {
     const rc::ListedItems map = {cand->ids, C};
     const int rc_ = si_launch_score(P, map, stream);
     if (rc_ != CARCA_OK) return rc_;
-    hipLaunchKernelGGL((rc::rc_select_kernel<SiSelect, rc::ListedItems>), dim3(D.Q), dim3(rc::RC_SEL_THREADS), 0, stream, S,
+    hipLaunchKernelGGL((rc::rc_select_kernel<rc::SelectView, rc::ListedItems>), dim3(D.Q), dim3(rc::RC_SEL_THREADS), 0, stream, S,
                        (const float*)P.out, C, map);
   } else {
     const rc::AllItems map = {};
     const int rc_ = si_launch_score(P, map, stream);
     if (rc_ != CARCA_OK) return rc_;
-    hipLaunchKernelGGL((rc::rc_select_kernel<SiSelect, rc::AllItems>), dim3(D.Q), dim3(rc::RC_SEL_THREADS), 0, stream, S,
+    hipLaunchKernelGGL((rc::rc_select_kernel<rc::SelectView, rc::AllItems>), dim3(D.Q), dim3(rc::RC_SEL_THREADS), 0, stream, S,
                        (const float*)P.out, C, map);
   }
   CARCA_LAUNCH_CHECK();

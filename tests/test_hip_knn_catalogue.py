@@ -108,7 +108,8 @@ def _targets(B, N, n_items, p_x, seed):
 
 
 # ---- integer tables: the i8 path, exact ----------------------------------------------------------------------------
-@pytest.mark.parametrize("F,n_items,B,density", [(37, 1000, 5, 0.3), (64, 3000, 70, 0.1), (4096, 12102, 128, 0.01)])
+@pytest.mark.parametrize("F,n_items,B,density", [(37, 1000, 5, 0.3), (64, 3000, 70, 0.1), (4096, 12102, 128, 0.01),
+                                                   (260, 300, 70, 0.1)])  # int8 rows of 320 bytes: five chunks
 def test_multihot_exact(F, n_items, B, density):
     A = _multihot(n_items, F, density, F)
     model = _model(A)
@@ -128,7 +129,7 @@ def test_multihot_exact(F, n_items, B, density):
 
 
 # ---- real-valued tables: the fp32 path ------------------------------------------------------------------------------
-@pytest.mark.parametrize("F,n_items,B", [(37, 2000, 9), (64, 3000, 66), (516, 5000, 17)])
+@pytest.mark.parametrize("F,n_items,B", [(37, 2000, 9), (64, 3000, 66), (516, 5000, 17), (256, 300, 70), (260, 300, 70)])
 def test_real_valued_within_bound(F, n_items, B):
     A = _real(n_items, F, F)
     model = _model(A)

@@ -68,6 +68,12 @@ OP_CASES = [
     (1000, 37, 0, 5, 1, "dot"),          # 0.000
     (300, 96, 4, 65, 128, "dot"),        # 0.028
     (300, 132, 4, 65, 128, "dot"),       # 0.026
+    # the streaming loop's edges (csrc/row_stream.h: 4 chunks of 16 columns in flight, chains folded every 16 chunks)
+    (300, 192, 0, 65, 10, "dot"),        # 0.003  12 chunks: three unrolled groups, folded only at the end
+    (300, 256, 0, 65, 10, "dot"),        # 0.006  exactly one fold, no tail
+    (300, 260, 0, 65, 10, "cosine"),     # 0.009  17 chunks: one fold plus a one-chunk tail
+    (300, 1028, 0, 65, 10, "dot"),       # 0.018  four folds plus tail
+    (77, 132, 0, 70, 10, "dot"),         # 0.000  last workgroup: a 13-row wave and waves without rows; 2nd query block partial
 ]
 
 
@@ -373,6 +379,24 @@ def test_knn_similar_items_agrees_with_recommend(F, kind):
                 float(S64.abs().max()), ties=True)
     assert knn.__dict__["_similar_cache"][2]["rnorm"] is not None
     pickle.dumps(knn)
+
+
+@pytest.mark.parametrize("F,kind", [(37, "random"), (256, "random"), (260, "random"), (4102, "random"), (64, "multihot")])
+def test_knn_similar_items_has_recommend_bits(F, kind):
+    """With the query's own row kept and no exclusion the two calls return the same bits.  F = 256 / 260 / 4102: both run
+    one kernel (csrc/row_stream.h) with aligned loads, at one fold, one fold plus a tail and many folds.  F = 37:
+    recommend's unaligned loads against similar_items' query-stationary kernel over a zero-padded copy of the table (one
+    chain in the same order).  The multi-hot table: recommend's int8 products against fp32 ones (exact integer sums)."""
+    n, k = 300, 20
+    g = torch.Generator().manual_seed(F)
+    A = (torch.rand(n, F, generator=g) < 0.1).float() if kind == "multihot" else torch.randn(n, F, generator=g)
+    A[0] = 0
+    knn = KNN()
+    knn.register_attr_table(A.cuda())
+    ids = _queries(n, 40).cuda()
+    ss, si = knn.similar_items(ids, k, "dot", exclude_self=False)
+    rs, ri = knn.recommend((ids[:, None], None, None), None, k, exclude=None)
+    assert torch.equal(ss, rs) and torch.equal(si, ri)
 
 
 # ---- 7. reproducibility -----------------------------------------------------------------------------------------------

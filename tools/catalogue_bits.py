@@ -13,7 +13,11 @@ KNN in table mode on a multi-hot table (i8) and on real-valued tables (fp32, F %
 shapes of tools/bench_recommend.py and tools/bench_knn_catalogue.py.  Every CARCA case ends with the calls restricted to
 candidate sets (lines named .../among-...): a tenth of the catalogue, a set of 257 ids (one past a
 tile; the whole catalogue where it is smaller) and the empty set, drawn after everything else so that the unrestricted
-lines keep their inputs; --no-candidates leaves them out, for a tree from before the candidate sets.
+lines keep their inputs; --no-candidates leaves them out, for a tree from before the candidate sets.  Last come the
+similar_items lines (csrc/similar_items.hip, csrc/row_stream.h; section 17): ops.similar_rows at a width for the
+query-stationary kernel and five for the streaming one, cosine and dot, with and without the query's own row and a
+candidate list, for 5 and 70 queries (invalid and repeated ids among them) and every item, one call per width and metric
+forced into six chunks; and KNN.similar_items on a table it uses as it is and on one it pads.
 usage: python tools/catalogue_bits.py [--package-root DIR] [--no-candidates] [--out listing.txt]"""
 import argparse
 import hashlib
@@ -58,6 +62,12 @@ KNN_CASES = [
     ("C2-i8", "multihot", 12102, 4096, 128, 50, False),
     ("C2-fp32", "real", 12102, 4096, 128, 50, False),
 ]
+# row widths of the similar_items cases: 90 the query-stationary kernel, the others the streaming one (csrc/row_stream.h) at
+# 9, 16, 17, 65 and 257 chunks of 16 columns
+SIMILAR_WIDTHS = [90, 132, 256, 260, 1028, 4102]
+SIMILAR_METRICS = ("cosine", "dot")
+# (name, table kind, n_items, F): KNN.similar_items on the table itself and on its zero-padded copy (F % 4 != 0)
+KNN_SIMILAR_CASES = [("multihot-f200", "multihot", 3001, 200), ("real-f130", "real", 3001, 130)]
 
 
 def _sha(t):
@@ -158,6 +168,47 @@ def knn_case(seed, name, kind, n_items, F, B, L, dense):
     return _calls("knn/" + name, model, (p_x.cuda(), p_a, None), None, g, B, n_items, p_x)
 
 
+def similar_case(seed, K):
+    """ops.similar_rows over a randn [333, K] table (five 64-row workgroups and a 13-row wave), its columns past K poisoned."""
+    n = 333
+    g = torch.Generator().manual_seed(seed)
+    ld = (K + 3) // 4 * 4
+    X = torch.full((n, ld), float("nan"))
+    X[:, :K] = torch.randn(n, K, generator=g)
+    X[0, :K] = 0
+    X = X.cuda()
+    q70 = torch.randint(1, n, (70,), generator=g)
+    q70[3], q70[4], q70[5], q70[6], q70[69] = 0, n, -2, q70[7], q70[8]  # invalid ids and duplicates
+    queries = {"Q5": q70[:5].cuda(), "Q70": q70.cuda(), "all": None}
+    cands = (torch.randperm(n - 1, generator=g)[:150] + 1).cuda()
+    out = []
+    for metric in SIMILAR_METRICS:
+        for self_ in (True, False):
+            for S, stag in ((None, "none"), (cands, "among-150")):
+                for qtag in ("Q70",) if (S is not None or not self_) else queries:
+                    s, i = ops.similar_rows(X, K, queries[qtag], 20, metric, exclude_self=self_, candidates=S)
+                    tag = f"similar/K{K}/{metric}-{'noself' if self_ else 'self'}-{stag}-{qtag}"
+                    out += [(tag + "/scores", _sha(s)), (tag + "/ids", _sha(i))]
+        # every item as a query, in chunks of 64 (six launches of the scoring kernel)
+        s, i = ops.similar_rows(X, K, None, 128, metric, max_scratch_bytes=4 * 64 * n + 100)
+        out += [(f"similar/K{K}/{metric}-chunked/scores", _sha(s)), (f"similar/K{K}/{metric}-chunked/ids", _sha(i))]
+    return out
+
+
+def knn_similar_case(seed, name, kind, n_items, F):
+    g = torch.Generator().manual_seed(seed)
+    A = (torch.rand(n_items, F, generator=g) < 0.2).float() if kind == "multihot" else torch.rand(n_items, F, generator=g) * 2 - 1
+    A[0] = 0
+    model = M.KNN().cuda()
+    model.register_attr_table(A.cuda())
+    ids = torch.randint(1, n_items, (70,), generator=g).cuda()
+    out = []
+    for metric in SIMILAR_METRICS:
+        s, i = model.similar_items(ids, 20, metric, exclude_self=metric == "cosine")
+        out += [(f"knn-similar/{name}/{metric}/scores", _sha(s)), (f"knn-similar/{name}/{metric}/ids", _sha(i))]
+    return out
+
+
 def main():
     assert torch.cuda.is_available(), "catalogue_bits.py needs a GPU"
     lines = [f"# cus={ops.num_cus()}"]
@@ -165,6 +216,10 @@ def main():
         lines += [f"{k} {h}" for k, h in carca_case(300 + i, *case)]
     for i, case in enumerate(KNN_CASES):
         lines += [f"{k} {h}" for k, h in knn_case(400 + i, *case)]
+    for i, K in enumerate(SIMILAR_WIDTHS):
+        lines += [f"{k} {h}" for k, h in similar_case(500 + i, K)]
+    for i, case in enumerate(KNN_SIMILAR_CASES):
+        lines += [f"{k} {h}" for k, h in knn_similar_case(600 + i, *case)]
     torch.cuda.synchronize()
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
