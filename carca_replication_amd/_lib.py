@@ -19,7 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h"]
 
@@ -307,6 +307,13 @@ class SimilarDesc(C.Structure):
         ("ld_cand_table", C.c_int32), ("cand_rnorm", _fp), ("gather_candidates", C.c_int32)] + _TOPK_OUT
 
 
+class MmrDesc(C.Structure):
+    """CarcaMmrDesc (carca_mmr_rerank)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "P", "k", "n_items", "n_cols", "metric", "normalize")] + [
+        ("lam", C.c_float), ("pool_scores", _fp), ("ld_pool_scores", C.c_int32), ("pool_ids", _fp),
+        ("ld_pool_ids", C.c_int32), ("table", _fp), ("ld_table", C.c_int32), ("rnorm", _fp)] + _TOPK_OUT + [("ild", _fp)]
+
+
 class FeatCache(C.Structure):  # CarcaFeatCache
     _fields_ = [("p_c", _fp), ("a_c", _fp), ("state", _fp), ("table", _fp), ("n_rows", C.c_int32), ("ld_p", C.c_int32),
                 ("ld_a", C.c_int32)]
@@ -405,6 +412,7 @@ SIGNATURES = {
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
     "carca_row_rnorm": (_i, [_fp, _i, _i, _i, _fp, _fp]),
     "carca_similar_items": (_i, [C.POINTER(SimilarDesc), C.POINTER(Candidates), _fp]),
+    "carca_mmr_rerank": (_i, [C.POINTER(MmrDesc), _fp]),
     "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),

@@ -4,7 +4,8 @@ a (user, item) pair), then does what the four share -- the k / items checks, the
 launch (recommend, rank_items).  A model's two descriptors name their model-side and exclusion fields alike
 (include/carca_hip.h), so one function fills both.  CandidateSet is the item set the CARCA calls can be restricted to
 (DESIGN.md section 15).  similar_items is the item-to-item top-k over a row table (CARCA.similar_items, KNN.similar_items,
-ops.similar_rows)."""
+ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
+(recommend_diverse, ops.mmr_rerank)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -397,3 +398,71 @@ def similar_items(what: str, table: Tensor, n_cols: int, rnorm: Callable[[], Ten
             D.scores, D.ids_out = scores.data_ptr() + 4 * k * lo, out_ids.data_ptr() + 8 * k * lo
             _lib.check(lib.carca_similar_items(C.byref(D), None if cand is None else C.byref(cand), stream), what)
         return scores, out_ids
+
+
+# ---- diversity re-ranking of a pool (include/carca_hip.h: carca_mmr_rerank) ---------------------
+MMR_MAX_USERS = 65535  # users per launch (one workgroup each)
+
+
+def mmr_args(what: str, k: int, pool: int, lam: float, metric: str) -> None:
+    """The argument checks that need no tensor."""
+    if metric not in SIMILAR_METRICS:
+        raise ValueError(f'{what}: metric must be "cosine" or "dot", got {metric!r}')
+    if not 0.0 <= float(lam) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"{what}: lam = {lam} outside [0, 1]")
+    if not 1 <= int(pool) <= KMAX:
+        raise CarcaHipError(f"{what}: pool size {pool} outside 1..{KMAX} (the largest k recommend keeps is {KMAX})")
+    if not 1 <= int(k) <= int(pool):
+        raise CarcaHipError(f"{what}: k = {k} outside 1..pool = {pool}")
+
+
+def mmr_rerank(what: str, scores: Tensor, ids: Tensor, table: Tensor, n_cols: int, k: int, lam: float, metric: str,
+               normalize: bool, rnorm: Optional[Callable[[], Tensor]]) -> Tuple[Tensor, Tensor, Tensor]:
+    """Greedy maximal-marginal-relevance re-rank of a pool (scores [B, P] float32, ids [B, P] integer, in pool order) over
+    the rows of `table` [n_items, >= n_cols] (similar_items' layout rules): (scores [B, k] float32, ids [B, k] int64 in
+    selection order, ild [B] float32).  rnorm() gives the table's reciprocal row norms (called for "cosine" only)."""
+    if not isinstance(scores, Tensor) or not isinstance(ids, Tensor) or scores.dim() != 2 or ids.dim() != 2 or \
+            tuple(scores.shape) != tuple(ids.shape):
+        raise CarcaHipError(f"{what}: the pool must be scores [B, P] and ids [B, P] of one shape")
+    if scores.dtype != torch.float32 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+        raise CarcaHipError(f"{what}: pool scores must be float32 and pool ids an integer tensor, got {scores.dtype} and "
+                            f"{ids.dtype}")
+    B, P = scores.shape
+    mmr_args(what, k, P, lam, metric)
+    if not isinstance(table, Tensor) or table.dim() != 2 or table.dtype != torch.float32 or \
+            not 1 <= int(n_cols) <= table.shape[1]:
+        raise CarcaHipError(f"{what}: the table must be float32 [n_items, >= n_cols]")
+    ops._need_cuda(scores, ids, table)
+    if table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        raise CarcaHipError(f"{what}: the table needs unit column stride, a row stride that is a multiple of 4 floats and a "
+                            "16-byte aligned base")
+    k, dev = int(k), table.device
+    with torch.no_grad():
+        out_s = torch.empty(B, k, dtype=torch.float32, device=dev)
+        out_i = torch.empty(B, k, dtype=torch.int64, device=dev)
+        ild = torch.empty(B, dtype=torch.float32, device=dev)
+        if B == 0:
+            return out_s, out_i, ild
+        s = scores.detach() if scores.stride(1) == 1 else scores.detach().contiguous()
+        i = ids.to(torch.int64)
+        i = i if i.stride(1) == 1 else i.contiguous()
+        D = _lib.MmrDesc()
+        D.P, D.k, D.n_items, D.n_cols = P, k, table.shape[0], int(n_cols)
+        D.metric, D.normalize, D.lam = SIMILAR_METRICS[metric], int(bool(normalize)), float(lam)
+        D.table, D.ld_table = table.data_ptr(), table.stride(0)
+        keep = [s, i, table]
+        if metric == "cosine":
+            rn = rnorm() if rnorm is not None else row_rnorm(table, n_cols)
+            ops._need_cuda(rn)
+            if rn.dtype != torch.float32 or rn.dim() != 1 or rn.shape[0] != table.shape[0] or not rn.is_contiguous():
+                raise CarcaHipError(f"{what}: rnorm must be a contiguous float32 [n_items] tensor (catalogue.row_rnorm)")
+            keep.append(rn)
+            D.rnorm = rn.data_ptr()
+        D.ld_pool_scores, D.ld_pool_ids, D.ld_scores, D.ld_ids_out = s.stride(0), i.stride(0), k, k
+        lib, stream = _lib.load(), ops._stream()
+        for lo in range(0, B, MMR_MAX_USERS):
+            D.B = min(B - lo, MMR_MAX_USERS)
+            D.pool_scores, D.pool_ids = s.data_ptr() + 4 * s.stride(0) * lo, i.data_ptr() + 8 * i.stride(0) * lo
+            D.scores, D.ids_out, D.ild = out_s.data_ptr() + 4 * k * lo, out_i.data_ptr() + 8 * k * lo, ild.data_ptr() + 4 * lo
+            _lib.check(lib.carca_mmr_rerank(C.byref(D), stream), what)
+        return out_s, out_i, ild

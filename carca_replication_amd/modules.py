@@ -1413,6 +1413,29 @@ class CARCA(_PackedModule, Model):
             return catalogue.similar_items("similar_items", T, emb.d, partial(_item_rnorm, emb, T), items, k, metric,
                                            exclude_self, candidates, max_scratch_bytes)
 
+    # ---- diversity re-ranking (include/carca_hip.h: carca_mmr_rerank) ----------------------------------
+    def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
+                          pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile", candidates=None,
+                          allow_composed: bool = False, normalize: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+        """recommend's `pool` best items per user, re-ranked for diversity by maximal marginal relevance in the space of
+        the item table T[i] = e(i, 0): (scores [B, k] float32, ids [B, k] int64 in selection order, ild [B] float32).
+
+        The pool is self.recommend(profile, context, k=pool, exclude, candidates, allow_composed), unchanged; then, k
+        times, the untaken pool item with the largest lam * rel - (1 - lam) * max_{s taken} sim(i, s) is taken (ties to
+        the better pool position: better score, then smaller id).  rel is the pool score normalised to [0, 1] per user
+        (normalize=True) or the score itself; sim is similar_items' "cosine" or "dot" over T, with the cached reciprocal
+        norms.  scores are recommend's for the taken items; ild is the list's intra-list diversity, the mean of 1 - sim
+        over its pairs (0 with fewer than two items); fewer than k eligible items pad with id 0 and score 0.  lam = 1 is
+        recommend(k) bit for bit; lam = 0 is pure diversity after the best item.  Errors and envelope are recommend's,
+        plus 1 <= k <= pool <= 128 (CarcaHipError) and lam in [0, 1], metric "cosine" / "dot" (ValueError)."""
+        catalogue.mmr_args("recommend_diverse", k, pool, lam, metric)
+        s, i = self.recommend(profile, context, k=pool, exclude=exclude, candidates=candidates, allow_composed=allow_composed)
+        with torch.no_grad():
+            emb = self.embeds
+            T = emb.item_table()
+            return catalogue.mmr_rerank("recommend_diverse", s, i, T, emb.d, k, lam, metric, normalize,
+                                        partial(_item_rnorm, emb, T))
+
     # ---- inference: one host call per forward (include/carca_hip.h: carca_forward) -----------------------------
     def _fused_ok(self, trace) -> bool:
         if trace is not None or len(self.encoder) > _lib.MAX_BLOCKS or not self._fusable():
@@ -1713,6 +1736,25 @@ class KNN(Model):
         eligible items pad with id 0 and score 0.  1 <= k <= 128; any L; train and eval mode alike."""
         return catalogue.recommend("KNN.recommend", _lib.KnnRecommendDesc, "carca_knn_recommend",
                                    partial(catalogue.knn_model_side, self, profile), profile, k, exclude)
+
+    def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
+                          k: int = 10, pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile",
+                          normalize: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+        """CARCA.recommend_diverse for the baseline: recommend's `pool` best items re-ranked by maximal marginal relevance
+        over the rows of the registered attribute table (the space similar_items measures in), with its cached reciprocal
+        norms: (scores [B, k], ids [B, k] in selection order, ild [B]).  lam = 1 is recommend(k) bit for bit."""
+        catalogue.mmr_args("KNN.recommend_diverse", k, pool, lam, metric)
+        s, i = self.recommend(profile, context, k=pool, exclude=exclude)
+        table = self._attr_table
+        with torch.no_grad():
+            c = self._similar_tables()
+
+            def rnorm():
+                if c["rnorm"] is None:
+                    c["rnorm"] = catalogue.row_rnorm(c["rows"], table.shape[1])
+                return c["rnorm"]
+            return catalogue.mmr_rerank("KNN.recommend_diverse", s, i, c["rows"], table.shape[1], k, lam, metric, normalize,
+                                        rnorm)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile") -> Tuple[Tensor, Tensor]:

@@ -1793,3 +1793,23 @@ def similar_rows(table: Tensor, n_cols: int, items: Optional[Tensor], k: int = 1
 
     return catalogue.similar_items("similar_rows", table, n_cols, lambda: catalogue.row_rnorm(table, n_cols), items, k,
                                    metric, exclude_self, candidates, max_scratch_bytes)
+
+
+def mmr_rerank(scores: Tensor, ids: Tensor, table: Tensor, n_cols: int, k: int, lam: float = 0.7, metric: str = "cosine",
+               normalize: bool = True, rnorm: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Diversity re-rank of a top-k pool by maximal marginal relevance (carca_mmr_rerank).
+
+    scores [B, P] float32 and ids [B, P] integer are each user's pool in pool order (recommend's outputs, or any list),
+    1 <= k <= P <= 128; table [n_items, >= n_cols] is the fp32 row table the ids index (similar_rows' layout rules).
+    Entries with an id outside [1, n_items) are skipped.  Greedily, k times: the untaken entry with the largest
+    lam * rel - (1 - lam) * max_{s selected} sim(id, id_s) is taken (the max is 0 before the first pick), ties to the
+    smaller pool position; rel is the score normalised to [0, 1] over the user's valid entries (normalize=True) or the
+    score itself; sim is "cosine" or "dot" over the first n_cols columns.  Returns (scores [B, k] -- the taken entries'
+    pool scores, ids [B, k] int64 in selection order, ild [B] -- the mean of 1 - sim over the pairs of the taken entries,
+    0 with fewer than two); fewer than k valid entries pad with id 0 and score 0.  lam = 1 returns the first k valid
+    entries.  rnorm: the table's reciprocal row norms (catalogue.row_rnorm) for "cosine"; None computes them here.
+    Bit-reproducible; a user's result does not depend on the rest of the batch."""
+    from . import catalogue
+
+    return catalogue.mmr_rerank("mmr_rerank", scores, ids, table, n_cols, k, lam, metric, normalize,
+                                None if rnorm is None else (lambda: rnorm))

@@ -167,6 +167,50 @@ def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candida
     return hr / max(users, 1.0), ndcg / max(users, 1.0)
 
 
+def evaluate_full_diverse(model: Model, loader: DataLoader, device: str, k: int, pool: int = 128, lam: float = 0.7,
+                          metric: str = "cosine", candidates=None) -> dict:
+    """evaluate_full's protocol over the diversity re-ranked list (model.recommend_diverse: recommend's `pool` best items
+    re-ranked by maximal marginal relevance): the positive o_x[:, 0] with its context against the
+    catalogue, the profile's other items excluded.  Returns {"HR@k", "NDCG@k", "ILD@k" (the lists' intra-list diversity,
+    mean over users), "coverage@k" (distinct recommended ids / (n_items - 1)), "users"}.  With lam = 1 HR and NDCG are
+    evaluate_full's.  Sums and the coverage bitmap stay on the device, one host sync at the end.
+    candidates: as evaluate_full's (CARCA only); a user whose positive is not in S is left out of every sum."""
+    model = model.eval().to(device)
+    cand = _candidate_set(model, "recommend_diverse", candidates, device)
+    wide = _wide_envelope(model, "recommend_diverse")
+    if cand is not None:
+        wide["candidates"] = cand
+    sums = torch.zeros(4, dtype=torch.float32, device=device)
+    seen = None
+    with torch.no_grad():
+        for batch in loader:
+            p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
+            pos = o_x[:, :1].to(torch.int64)
+            excl = torch.where(p_x.to(torch.int64) == pos, torch.zeros_like(pos), p_x.to(torch.int64))
+            _, ids, ild = model.recommend_diverse((p_x, p_a, p_c), o_c[:, 0], k=k, pool=pool, lam=lam, metric=metric,
+                                                  exclude=excl, **wide)
+            if seen is None:
+                n_items = (model.embeds.item_table() if hasattr(model, "embeds") else model._attr_table).shape[0]
+                seen = torch.zeros(n_items, dtype=torch.bool, device=ids.device)
+            counted = torch.ones_like(pos, dtype=torch.bool) if cand is None else cand.contains(pos)
+            hit = (ids == pos) & counted
+            rank = torch.arange(k, device=ids.device, dtype=torch.float32).expand_as(ids)
+            sums[0] += hit.sum()
+            sums[1] += (hit.to(torch.float32) / torch.log2(rank + 2.0)).sum()
+            sums[2] += (ild * counted.reshape(-1)).sum()
+            sums[3] += counted.sum()
+            seen[torch.where(counted, ids, torch.zeros_like(ids)).reshape(-1)] = True
+    if seen is None:
+        return {f"HR@{k}": 0.0, f"NDCG@{k}": 0.0, f"ILD@{k}": 0.0, f"coverage@{k}": 0.0, "users": 0}
+    seen[0] = False  # (id 0 is padding)
+    hr, ndcg, ild_sum, users, distinct = (float(v) for v in torch.cat([sums, seen.sum().reshape(1).to(sums.dtype)]).cpu())
+    if torch.device(device).type == "cuda":
+        ops.poll_errors()
+    den = max(users, 1.0)
+    return {f"HR@{k}": hr / den, f"NDCG@{k}": ndcg / den, f"ILD@{k}": ild_sum / den,
+            f"coverage@{k}": distinct / max(seen.shape[0] - 1, 1), "users": int(users)}
+
+
 def _rank_sums(ranks: torch.Tensor, ks) -> torch.Tensor:
     """[hits@k for k in ks, dcg@k for k in ks, sum 1/(rank+1), sum rank, users] (float64, on ranks' device) over the
     entries of ranks >= 0 (rank -1 marks an id outside the catalogue and counts nowhere)."""

@@ -1195,6 +1195,46 @@ typedef struct CarcaSimilarDesc {
 int carca_row_rnorm(const float* table, int ld, int n_rows, int n_cols, float* out, void* stream);
 int carca_similar_items(const CarcaSimilarDesc* desc, const CarcaCandidates* candidates, void* stream);
 
+/* ---- diversity re-ranking of a top-k pool: maximal marginal relevance + intra-list diversity ---
+ * carca_mmr_rerank: per user u of B a pool of P entries (pool_scores[u][j], pool_ids[u][j]), j = 0 .. P - 1 in pool order
+ * (carca_recommend's outputs, or any caller's), re-ranked greedily over the rows of table X [n_items, ld_table] (fp32,
+ * n_cols live columns; ld_table a multiple of 4, base 16-byte aligned; no column past n_cols reaches a product):
+ *   valid entries: 1 <= id < n_items; every other entry is skipped (no host check, no read); a repeated id is an entry
+ *     of its own;
+ *   sim(a, b) = X[a] . X[b] (CARCA_SIMILAR_DOT) or ((X[a] . X[b]) * rnorm[a]) * rnorm[b] (CARCA_SIMILAR_COSINE; rnorm
+ *     [n_items] from carca_row_rnorm, the caller's; an all-zero row has similarity 0 to everything);
+ *   rel_j = (s_j - s_min) / (s_max - s_min) over the user's valid entries, 0 where s_max == s_min (normalize != 0), or
+ *     s_j (normalize == 0);
+ *   step t = 0 .. k - 1, while an untaken valid entry remains: obj_j = lam * rel_j - (1 - lam) * M_j with M_j = 0 at
+ *     t = 0 and max over the selected s of sim(id_j, id_s) after; the largest obj wins, ties to the smaller pool position.
+ * Outputs: scores [B, k] the selected entries' pool scores (their bits), ids_out [B, k] in selection order, both padded
+ * with 0 where fewer than k entries are valid; ild [B] the mean over pairs a < b of the selected entries of 1 - sim (the
+ * values the selection used, summed in selection order), 0 with fewer than two.  lam = 1 gives the first k valid entries.
+ * One workgroup per user; only the rows of the pool's Gram matrix that the selection asks for are computed (n_cols <= 128:
+ * the pool's rows staged in LDS; wider: streamed from the table at each step).  Plain fp32 fmaf sums whose order depends
+ * on n_cols alone: bitwise-equal rows give bitwise-equal similarities; no atomics, no scratch, no host wait; a user's
+ * result does not depend on B or on its position.
+ * CARCA_ERR_UNSUPPORTED: P outside 1..128, k outside 1..P, B > 65535, n_cols > 2^22.  CARCA_ERR_BADARG: null pointers,
+ * strides, alignment, an unknown metric, cosine without rnorm, lam outside [0, 1]. */
+typedef struct CarcaMmrDesc {
+  int B, P, k, n_items, n_cols;
+  int metric, normalize; /* CARCA_SIMILAR_DOT / CARCA_SIMILAR_COSINE; rel normalised per user */
+  float lam;
+  const float* pool_scores; /* [B, ld_pool_scores] */
+  int ld_pool_scores;
+  const int64_t* pool_ids; /* [B, ld_pool_ids] */
+  int ld_pool_ids;
+  const float* table; /* [n_items, ld_table] */
+  int ld_table;
+  const float* rnorm; /* [n_items], or NULL for CARCA_SIMILAR_DOT */
+  float* scores;      /* [B, ld_scores] */
+  int ld_scores;
+  int64_t* ids_out; /* [B, ld_ids_out] */
+  int ld_ids_out;
+  float* ild; /* [B] */
+} CarcaMmrDesc;
+int carca_mmr_rerank(const CarcaMmrDesc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
