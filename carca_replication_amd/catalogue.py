@@ -5,7 +5,8 @@ launch (recommend, rank_items).  A model's two descriptors name their model-side
 (include/carca_hip.h), so one function fills both.  CandidateSet is the item set the CARCA calls can be restricted to
 (DESIGN.md section 15).  similar_items is the item-to-item top-k over a row table (CARCA.similar_items, KNN.similar_items,
 ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
-(recommend_diverse, ops.mmr_rerank)."""
+(recommend_diverse, ops.mmr_rerank).  score_items / recommend_from serve a candidate list of its
+own per user (CARCA.score_items / recommend_from)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -308,6 +309,61 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
         D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
         return _launch(what, D, entry, "ranks", N, profile[0].device, cand)
+
+
+# ---- a candidate list per user (include/carca_hip.h: carca_score_lists / carca_recommend_lists) --
+LIST_FUSED_MAX = 1024  # longest list of the one-launch top-k (csrc: LS_FUSED_MAX); read at call time
+
+
+def _lists(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool):
+    """The checks and the descriptor score_items and recommend_from share: -> (D, keep, p_ids, the lists as int32)."""
+    if not isinstance(items, Tensor) or items.dim() != 2 or items.is_floating_point() or items.is_complex() or \
+            items.dtype == torch.bool or items.shape[0] != profile[0].shape[0] or items.shape[1] < 1:
+        raise CarcaHipError(f"{what}: items must be an int [B, N] tensor with N >= 1, one row per user")
+    if items.shape[0] * items.shape[1] >= 2 ** 31:
+        raise CarcaHipError(f"{what}: B * N = {items.shape[0] * items.shape[1]} does not fit an int")
+    ops._need_cuda(items)
+    D = _lib.ListsDesc()
+    keep, p_ids = _fill(fill, what, D, allow_composed)
+    lst = _ids32_clamped(items, D.n_items)
+    return D, keep, p_ids, lst
+
+
+def _lists_launch(what: str, D, keep: list, lst: Tensor, entry: str) -> None:
+    keep.append(lst)
+    D.items, D.n_list, D.ld_items = lst.data_ptr(), lst.shape[1], lst.stride(0)
+    _lib.check(getattr(_lib.load(), entry)(C.byref(D), ops._stream()), what)
+
+
+def score_items(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool = False) -> Tensor:
+    """The list-scoring call: scores [B, N] float32 of each user's own list, in caller order (carca_score_lists)."""
+    with torch.no_grad():
+        D, keep, _, lst = _lists(what, fill, profile, items, allow_composed)
+        scores = torch.empty(D.B, lst.shape[1], dtype=torch.float32, device=profile[0].device)
+        D.scores, D.ld_scores = scores.data_ptr(), lst.shape[1]
+        _lists_launch(what, D, keep, lst, "carca_score_lists")
+        return scores
+
+
+def recommend_from(what: str, fill: Callable, profile, items: Tensor, k: int, exclude,
+                   allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+    """The top-k call over each user's own list (carca_recommend_lists): a list of up to LIST_FUSED_MAX entries goes to
+    the one-launch kernel as it is; a longer one is sorted per row on the device first (no host sync), which is the form
+    the split path asks for."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    with torch.no_grad():
+        D, keep, p_ids, lst = _lists(what, fill, profile, items, allow_composed)
+        D.k = int(k)
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        if lst.shape[1] > LIST_FUSED_MAX:
+            lst = torch.sort(lst, dim=1).values
+            D.sorted_rows = 1
+        outs = (torch.empty(D.B, int(k), dtype=torch.float32, device=profile[0].device),
+                torch.empty(D.B, int(k), dtype=torch.int64, device=profile[0].device))
+        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = outs[0].data_ptr(), int(k), outs[1].data_ptr(), int(k)
+        _lists_launch(what, D, keep, lst, "carca_recommend_lists")
+        return outs
 
 
 # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md section 17) ------------------------------

@@ -5,7 +5,8 @@
 // (the raw logit, for models without a link).  Keys are built and taken apart by recommend_common.h's helpers
 // (rc::order_key, rc::key_id); an item whose order bits are 0 holds the exclusion sentinel and is skipped.
 // Map (recommend_common.h) says what a column of the buffer is: rc::AllItems, column = item id, or rc::ListedItems,
-// column = position in an ascending candidate list ([B, C] buffer; keys carry the position, ids_out the id behind it).
+// column = position in an ascending candidate list ([B, C] buffer; keys carry the position, ids_out the id behind it), or
+// rc::UserLists, a list of its own per user: each workgroup takes its user's row of the map (for_user).
 #pragma once
 #include "recommend_common.h"
 
@@ -35,13 +36,14 @@ struct SelectView {
 template <class Desc, class Map = AllItems>
 __global__ __launch_bounds__(64) void rc_exclude_kernel(Desc D, float* __restrict__ logits, int ld_s, Map map) {
   const int u = blockIdx.x;
+  const auto m = map.for_user(u);
   float* row = logits + (size_t)u * ld_s;
   const float sent = __uint_as_float(RC_SENTINEL);
   if (!Map::listed && threadIdx.x == 0) row[0] = sent;  // id 0 is the padding item (carca.py:73); no list holds it
   for (int e = threadIdx.x; e < D.n_exclude; e += 64) {
     const int id = D.exclude[(size_t)u * D.ld_exclude + e];
     if (id > 0 && id < D.n_items) {  // (0 = no entry; duplicates write the same word)
-      const int at = map.find(id);
+      const int at = m.find(id);
       if (at >= 0) row[at] = sent;
     }
   }
@@ -57,7 +59,8 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(Desc D, const
   __shared__ int s_pbits, s_need, s_done, s_keff, s_cnt;
   const int tid = threadIdx.x, u = blockIdx.x;
   const unsigned* row = reinterpret_cast<const unsigned*>(logits + (size_t)u * ld_s);
-  const int n = map.size(D.n_items);
+  const auto m = map.for_user(u);
+  const int n = m.size(D.n_items);
   if (tid == 0) s_prefix = 0ull, s_pbits = 0, s_done = 0, s_cnt = 0;
   for (int shift = 56; shift >= 0; shift -= 8) {
     hist[tid] = 0;  // (RC_SEL_THREADS == 256 bins)
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(RC_SEL_THREADS) void rc_select_kernel(Desc D, const
     long long id = 0;
     if (tid < keff) {
       const unsigned long long key = skey[tid];
-      id = (long long)map.item((int)rc::key_id(key));
+      id = (long long)m.item((int)rc::key_id(key));
       const float y = rc::unorder_bits((unsigned)(key >> 32));
       score = rc::link(y, D.decoder);
     }

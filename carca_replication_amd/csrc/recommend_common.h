@@ -1,5 +1,6 @@
 // Per-(user, item) logit arithmetic and the item order shared by the full-catalogue kernels: the top-k sweep of
-// recommend.hip and the list scoring / counting sweep of rank.hip (both through catalogue_sweep.h).  Both calls order items
+// recommend.hip and the list scoring / counting sweep of rank.hip (both through catalogue_sweep.h), and the per-user list
+// kernels of recommend_lists.hip.  The calls order items
 // by the same 64-bit key (order-preserving logit bits, then the complemented id), so they must produce the same logit bits
 // for the same (user, item): every kernel stages a user and scores an item through one of the scorers below
 // (CaScorer, DotScorer: the same five members; CaLongScorer, CaScorer's arithmetic over a profile staged in chunks),
@@ -46,11 +47,13 @@ struct AllItems {
   __device__ __forceinline__ int size(int n_items) const { return n_items; }
   __device__ __forceinline__ int item(int pos) const { return pos; }
   __device__ __forceinline__ int find(int id) const { return id; }  // (the caller has checked 1 <= id < n_items)
+  __device__ __forceinline__ AllItems for_user(int) const { return *this; }
 };
 struct ListedItems {
   static constexpr bool listed = true;
   const int32_t* ids;
   int n;
+  __device__ __forceinline__ ListedItems for_user(int) const { return *this; }
   __device__ __forceinline__ int size(int) const { return n; }
   __device__ __forceinline__ int item(int pos) const { return pos < n ? ids[pos] : 0; }  // (0 is never live)
   __device__ __forceinline__ int find(int id) const {  // the position of id, -1 when the list does not hold it
@@ -65,6 +68,38 @@ struct ListedItems {
     }
     return (lo < n && ids[lo] == id) ? lo : -1;
   }
+};
+// A list of its own per user (recommend_lists.hip): row u of ids [B, ld], n entries in NONDECREASING order.  A position is
+// live where its id is an item and differs from its predecessor's, so a row's live positions are ascending and distinct
+// -- ListedItems' argument, per row -- and an id's first occurrence, which find returns, is its live one.  Ids outside
+// [1, n_items) sort to the two ends and are never live (item gives 0 for a repeat; the caller tests the range).  A
+// launch with one workgroup per user takes its row through for_user(u); the two maps above are their own rows.
+struct ListedRow {
+  static constexpr bool listed = true;
+  const int32_t* ids;
+  int n;
+  __device__ __forceinline__ int size(int) const { return n; }
+  __device__ __forceinline__ int item(int pos) const {
+    return (pos < n && (pos == 0 || ids[pos - 1] != ids[pos])) ? ids[pos] : 0;
+  }
+  __device__ __forceinline__ int find(int id) const {  // the live position of id, -1 when the row does not hold it
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ids[mid] < id) {
+        lo = mid + 1;
+      } else {
+        hi = mid;
+      }
+    }
+    return (lo < n && ids[lo] == id) ? lo : -1;
+  }
+};
+struct UserLists {
+  static constexpr bool listed = true;
+  const int32_t* ids;
+  int n, ld;
+  __device__ __forceinline__ ListedRow for_user(int u) const { return ListedRow{ids + (size_t)u * ld, n}; }
 };
 
 // ---- the scorers ---------------------------------------------------------------------------------------------------

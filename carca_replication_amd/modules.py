@@ -1388,6 +1388,44 @@ class CARCA(_PackedModule, Model):
                                     partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude,
                                     candidates, allow_composed)
 
+    # ---- a candidate list per user (include/carca_hip.h: carca_score_lists / carca_recommend_lists) ----
+    def score_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
+                    allow_composed: bool = False) -> Tensor:
+        """The scores of each user's own list of items, from the per-item tables: [B, N] float32.
+
+        items: an int32 / int64 [B, N] tensor, N >= 1 and as long as the caller likes (B * N must fit an int): row u is
+        user u's list, e.g. a retriever's candidates.  scores[u, j] is what forward / recommend / rank_items returns
+        for (u, items[u, j]), bit for bit rank_items' and recommend's score of that pair.  An id of 0 or outside
+        [1, n_items) scores 0 (no host check, no out-of-bounds read); duplicates are each scored, caller order is
+        kept, nothing is excluded.  One launch with the user staged once per workgroup, no scratch, no host sync.
+        profile, context and the envelope are recommend's; allow_composed: as recommend's."""
+        if self.training:
+            raise CarcaHipError("score_items: the model is in training mode; list scores use eval semantics "
+                                "(call model.eval() first)")
+        self._check_built()
+        return catalogue.score_items("score_items", partial(catalogue.carca_model_side, self, profile, context), profile,
+                                     items, allow_composed)
+
+    def recommend_from(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
+                       k: int = 10, exclude="profile", allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+        """The k best items of each user's OWN list: (scores [B, k] float32, ids [B, k] int64), best first.
+
+        items: as score_items' -- an int [B, N] tensor of any length N, a different list per user.  Per user the
+        eligible items are the distinct ids of its row that are items (in [1, n_items)) minus the excluded ones;
+        order and padding are recommend's: score descending, ties to the smaller id, fewer than k eligible items pad
+        with id 0 and score 0.  Row u is bit for bit row 0 of recommend((p_x[u:u+1], p_a[u:u+1], p_c[u:u+1]),
+        context[u:u+1], k, exclude_u, candidates=the distinct valid ids of items[u]), in both outputs, without a
+        CandidateSet and without a host sync.  Up to catalogue.LIST_FUSED_MAX = 1024 entries the call is one launch
+        with one workgroup per user; a longer list is sorted per row on the device, scored into stream scratch [B, N]
+        and selected per row -- the same result either way.  exclude: recommend's three forms; 1 <= k <= 128.
+        profile, context and the envelope are recommend's; allow_composed: as recommend's."""
+        if self.training:
+            raise CarcaHipError("recommend_from: the model is in training mode; recommendation scores with eval "
+                                "semantics (call model.eval() first)")
+        self._check_built()
+        return catalogue.recommend_from("recommend_from", partial(catalogue.carca_model_side, self, profile, context),
+                                        profile, items, k, exclude, allow_composed)
+
     # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md 17) ---------------------------------
     def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,
                       candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:

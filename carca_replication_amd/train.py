@@ -167,6 +167,31 @@ def evaluate_full(model: Model, loader: DataLoader, device: str, k: int, candida
     return hr / max(users, 1.0), ndcg / max(users, 1.0)
 
 
+def evaluate_listed(model: Model, loader: DataLoader, device: str, k: int) -> Tuple[float, float]:
+    """(HR@k, NDCG@k) under the loader's own protocol -- the positive o_x[:, 0] against the sampled negatives o_x[:, 1:]
+    (data.py:180-185) -- served from the per-item tables: per batch model.recommend_from((p_x, p_a, p_c), o_c[:, 0], o_x,
+    k, exclude=None), the positive's rank being its position in the returned list (ties: the smaller id first; a
+    negative that repeats the positive is the same item).  What evaluate() measures through forward, without the
+    feature GEMM over the candidates.  Same loaders as evaluate(); sums stay on the device, one host sync at the end."""
+    model = model.eval().to(device)
+    wide = _wide_envelope(model, "recommend_from")
+    sums = torch.zeros(3, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for batch in loader:
+            p_x, p_a, p_c, o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
+            pos = o_x[:, :1].to(torch.int64)
+            _, ids = model.recommend_from((p_x, p_a, p_c), o_c[:, 0], o_x, k=k, exclude=None, **wide)
+            hit = (ids == pos) & (pos != 0)
+            rank = torch.arange(k, device=ids.device, dtype=torch.float32).expand_as(ids)
+            sums[0] += hit.sum()
+            sums[1] += (hit.to(torch.float32) / torch.log2(rank + 2.0)).sum()
+            sums[2] += ids.shape[0]
+    hr, ndcg, users = (float(v) for v in sums.cpu())
+    if torch.device(device).type == "cuda":
+        ops.poll_errors()
+    return hr / max(users, 1.0), ndcg / max(users, 1.0)
+
+
 def evaluate_full_diverse(model: Model, loader: DataLoader, device: str, k: int, pool: int = 128, lam: float = 0.7,
                           metric: str = "cosine", candidates=None) -> dict:
     """evaluate_full's protocol over the diversity re-ranked list (model.recommend_diverse: recommend's `pool` best items

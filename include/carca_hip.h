@@ -954,6 +954,61 @@ typedef struct CarcaCandidates {
 int carca_recommend_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
 int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* candidates, void* stream);
 
+/* ---- a candidate list of its own per user (the second stage behind a retriever; the evaluation protocol's 1 + 100
+ * candidates, data.py:180-185) ---------------------------------------------------------------
+ * The model-side fields (B .. ffn_b), k and the exclusion list mean exactly what they mean in CarcaRecommendDesc, and the
+ * logit of a (user, item) pair is bit-identical to carca_recommend's.  items [B, ld_items] int32, the first n_list
+ * columns read, n_list >= 1: user u's own list, in any order, duplicates allowed; an id of 0 or outside [1, n_items) is
+ * no item and is never read out of bounds.  The user is staged once per workgroup and the list streams past it.
+ *
+ * carca_score_lists: scores[u][j] = sigmoid(logit) ((logit + 1) / 2 for decoder 2) of (u, items[u][j]), 0 where the id
+ * is no item; caller order, duplicates each scored, no exclusion (k, exclude, ids_out and sorted_rows are not read).
+ * One launch, no scratch, any n_list.
+ *
+ * carca_recommend_lists: per user the k best among the DISTINCT items of its row minus the excluded ids, in
+ * carca_recommend's order (logit descending, ties to the smaller id), padded with id 0 and score 0 -- row u is what
+ * carca_recommend_among gives user u alone with the distinct items of items[u] as the candidate list, bit for bit.
+ *   sorted_rows == 0: n_list <= 1024, rows in any order; one launch, one workgroup per user, no scratch (the keys of a
+ *                     row are sorted in LDS, and a repeated id's equal keys are dropped there);
+ *   sorted_rows != 0: the caller's contract is that every row is NONDECREASING (repeats side by side; ids that are no
+ *                     items at the two ends); any n_list.  Raw logits [B, n_list] go to stream scratch (or the capture's
+ *                     memory) by position, then carca_recommend's exclusion and selection launches run per row.
+ * Bit-identical run to run, and between the two forms.  Limits (L up to CARCA_MAX_PROFILE_L, k <= 128) and errors as
+ * carca_recommend, and CARCA_ERR_UNSUPPORTED for n_list > 1024 without sorted_rows, CARCA_ERR_BADARG for a null list,
+ * n_list < 1 or strides shorter than a row. */
+typedef struct CarcaListsDesc {
+  int B, L, n_items, d, H, k;
+  int decoder;          /* 0 cross-attention, 1 dot, 2 normalised dot */
+  const int32_t* p_ids; /* [B, ld_p_ids] profile ids */
+  int ld_p_ids;
+  const float* item_q; /* [n_items, ld_item_q] */
+  int ld_item_q;
+  const float* item_w; /* [n_items] with stride ld_item_w, or NULL */
+  int ld_item_w;
+  const float* user_k; /* [B*L, ld_user_k] */
+  int ld_user_k;
+  const float* user_u; /* [B*L, ld_user_u] */
+  int ld_user_u;
+  const float* user_q; /* [B, ld_user_q] (decoder 0: may be NULL) */
+  int ld_user_q;
+  const float* user_m; /* [B, ld_user_m] or NULL */
+  int ld_user_m;
+  const float* user_off; /* [B] with stride ld_user_off, or NULL */
+  int ld_user_off;
+  const float* ffn_b; /* float[1] or NULL */
+  const int32_t* exclude; /* [B, ld_exclude], first n_exclude columns read */
+  int n_exclude, ld_exclude;
+  const int32_t* items; /* [B, ld_items], first n_list columns: each user's own list */
+  int n_list, ld_items;
+  int sorted_rows; /* carca_recommend_lists: every row is nondecreasing */
+  float* scores; /* [B, ld_scores]: n_list columns (carca_score_lists) or k (carca_recommend_lists) */
+  int ld_scores;
+  int64_t* ids_out; /* [B, ld_ids_out] (carca_recommend_lists) */
+  int ld_ids_out;
+} CarcaListsDesc;
+int carca_score_lists(const CarcaListsDesc* desc, void* stream);
+int carca_recommend_lists(const CarcaListsDesc* desc, void* stream);
+
 /* ---- KNN baseline: full-catalogue top-k and exact ranks (replace KNN.forward over the catalogue as target groups:
  * knn.py:13-19 over the candidate lists of data.py:180-185, ranked as train.py:15-32 does) ------
  * The catalogue is the rows of the attribute table [n_items, ld_table] (fp32, F features).  For user u and item i >= 1:
