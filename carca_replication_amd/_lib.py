@@ -19,7 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h"]
 
@@ -259,6 +259,15 @@ class ListsDesc(C.Structure):
         ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("sorted_rows", C.c_int32)] + _TOPK_OUT
 
 
+class ExplainDesc(C.Structure):
+    """CarcaExplainDesc (carca_explain_lists)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "n_items", "d", "H", "k")] + _CARCA_MODEL + [
+        ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32), ("scores", _fp), ("ld_scores", C.c_int32),
+        ("base", _fp), ("ld_base", C.c_int32), ("contrib", _fp), ("ld_contrib", C.c_int32), ("weights", _fp),
+        ("ld_weights", C.c_int32), ("slots", _fp), ("ld_slots", C.c_int32), ("slot_items", _fp),
+        ("ld_slot_items", C.c_int32), ("top_m", C.c_int32)]
+
+
 class Candidates(C.Structure):
     """CarcaCandidates (carca_recommend_among / carca_rank_items_among)."""
     _fields_ = [("ids", _fp), ("n", C.c_int32)]
@@ -416,6 +425,7 @@ SIGNATURES = {
     "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
     "carca_score_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_recommend_lists": (_i, [C.POINTER(ListsDesc), _fp]),
+    "carca_explain_lists": (_i, [C.POINTER(ExplainDesc), _fp]),
     "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),
     "carca_row_rnorm": (_i, [_fp, _i, _i, _i, _fp, _fp]),

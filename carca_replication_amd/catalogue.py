@@ -6,7 +6,8 @@ launch (recommend, rank_items).  A model's two descriptors name their model-side
 (DESIGN.md section 15).  similar_items is the item-to-item top-k over a row table (CARCA.similar_items, KNN.similar_items,
 ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
 (recommend_diverse, ops.mmr_rerank).  score_items / recommend_from serve a candidate list of its
-own per user (CARCA.score_items / recommend_from)."""
+own per user (CARCA.score_items / recommend_from).  explain_items / explain_top_slots /
+recommend_explained say which profile slots drive a cross-attention score."""
 from __future__ import annotations
 
 import ctypes as C
@@ -315,15 +316,16 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
 LIST_FUSED_MAX = 1024  # longest list of the one-launch top-k (csrc: LS_FUSED_MAX); read at call time
 
 
-def _lists(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool):
-    """The checks and the descriptor score_items and recommend_from share: -> (D, keep, p_ids, the lists as int32)."""
+def _lists(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool, desc=_lib.ListsDesc):
+    """The checks and the descriptor score_items and recommend_from share (desc: explain's, which carries the same list
+    fields): -> (D, keep, p_ids, the lists as int32)."""
     if not isinstance(items, Tensor) or items.dim() != 2 or items.is_floating_point() or items.is_complex() or \
             items.dtype == torch.bool or items.shape[0] != profile[0].shape[0] or items.shape[1] < 1:
         raise CarcaHipError(f"{what}: items must be an int [B, N] tensor with N >= 1, one row per user")
     if items.shape[0] * items.shape[1] >= 2 ** 31:
         raise CarcaHipError(f"{what}: B * N = {items.shape[0] * items.shape[1]} does not fit an int")
     ops._need_cuda(items)
-    D = _lib.ListsDesc()
+    D = desc()
     keep, p_ids = _fill(fill, what, D, allow_composed)
     lst = _ids32_clamped(items, D.n_items)
     return D, keep, p_ids, lst
@@ -364,6 +366,83 @@ def recommend_from(what: str, fill: Callable, profile, items: Tensor, k: int, ex
         D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = outs[0].data_ptr(), int(k), outs[1].data_ptr(), int(k)
         _lists_launch(what, D, keep, lst, "carca_recommend_lists")
         return outs
+
+
+# ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists) --------------
+EXPLAIN_TOP_MAX = 8  # largest m of explain_top_slots (csrc: EX_TOP_MAX, the insertion list a lane keeps in registers)
+
+
+def _explain_m(what: str, m: int) -> int:
+    if not 1 <= int(m) <= EXPLAIN_TOP_MAX:
+        raise CarcaHipError(f"{what}: m = {m} outside 1..{EXPLAIN_TOP_MAX} (the most slots an explanation keeps is "
+                            f"{EXPLAIN_TOP_MAX})")
+    return int(m)
+
+
+def _explain_launch(what: str, E, keep: list, lst: Tensor, m: Optional[int], device) -> tuple:
+    """Points E at the list and at fresh outputs and queues carca_explain_lists: m None -> the dense form,
+    (scores, base, contrib [B, N, L], weights [B, H, N, L]); else the top-m form, (scores, base, slots, slot_items,
+    contrib), each [B, N, m]."""
+    B, N = E.B, lst.shape[1]
+    keep.append(lst)
+    E.items, E.n_list, E.ld_items = lst.data_ptr(), N, lst.stride(0)
+    scores = torch.empty(B, N, dtype=torch.float32, device=device)
+    base = torch.empty(B, N, dtype=torch.float32, device=device)
+    E.scores, E.ld_scores, E.base, E.ld_base = scores.data_ptr(), N, base.data_ptr(), N
+    if m is None:
+        contrib = torch.empty(B, N, E.L, dtype=torch.float32, device=device)
+        weights = torch.empty(B, E.H, N, E.L, dtype=torch.float32, device=device)
+        E.contrib, E.ld_contrib, E.weights, E.ld_weights = contrib.data_ptr(), E.L, weights.data_ptr(), E.L
+        outs = (scores, base, contrib, weights)
+    else:
+        slots = torch.empty(B, N, m, dtype=torch.int64, device=device)
+        slot_items = torch.empty(B, N, m, dtype=torch.int64, device=device)
+        contrib = torch.empty(B, N, m, dtype=torch.float32, device=device)
+        E.slots, E.ld_slots, E.slot_items, E.ld_slot_items = slots.data_ptr(), m, slot_items.data_ptr(), m
+        E.contrib, E.ld_contrib, E.top_m = contrib.data_ptr(), m, m
+        outs = (scores, base, slots, slot_items, contrib)
+    _lib.check(_lib.load().carca_explain_lists(C.byref(E), ops._stream()), what)
+    return outs
+
+
+def explain_items(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool = False) -> tuple:
+    """The dense explanation of each user's own list: (scores [B, N], base [B, N], contrib [B, N, L],
+    weights [B, H, N, L]), all float32."""
+    with torch.no_grad():
+        E, keep, _, lst = _lists(what, fill, profile, items, allow_composed, desc=_lib.ExplainDesc)
+        return _explain_launch(what, E, keep, lst, None, profile[0].device)
+
+
+def explain_top_slots(what: str, fill: Callable, profile, items: Tensor, m: int, allow_composed: bool = False) -> tuple:
+    """The m profile slots with the largest contribution per (user, list entry): (scores [B, N], base [B, N],
+    slots [B, N, m] int64, slot_items [B, N, m] int64, contrib [B, N, m] float32); no [B, N, L] buffer."""
+    m = _explain_m(what, m)
+    with torch.no_grad():
+        E, keep, _, lst = _lists(what, fill, profile, items, allow_composed, desc=_lib.ExplainDesc)
+        return _explain_launch(what, E, keep, lst, m, profile[0].device)
+
+
+def recommend_explained(what: str, fill: Callable, profile, k: int, m: int, exclude, candidates=None,
+                        allow_composed: bool = False) -> tuple:
+    """recommend, then explain_top_slots over its ids, with ONE run of the model side: the explain descriptor's
+    model-side fields are the recommend descriptor's, name for name, and are copied.  -> (scores [B, k], ids [B, k],
+    slot_items [B, k, m], contrib [B, k, m])."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    m = _explain_m(what, m)
+    with torch.no_grad():
+        D = _lib.RecommendDesc()
+        keep, p_ids = _fill(fill, what, D, allow_composed)
+        D.k = int(k)
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        device = profile[0].device
+        cand = _candidates(what, candidates, D, keep, device)
+        scores, ids = _launch(what, D, "carca_recommend", "ids_out", int(k), device, cand)
+        E = _lib.ExplainDesc()
+        for name in ("B", "L", "n_items", "d", "H", "k") + tuple(f[0] for f in _lib._CARCA_MODEL):
+            setattr(E, name, getattr(D, name))
+        _, _, _, slot_items, contrib = _explain_launch(what, E, keep, ops._ids32(ids), m, device)  # (id 0: no item)
+        return scores, ids, slot_items, contrib
 
 
 # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md section 17) ------------------------------

@@ -158,6 +158,22 @@ inline SweepGrid sweep_grid(int n_slots, int B) {
   return {dim3(tiles, (B + upb - 1) / upb), upb};
 }
 
+// The user-stationary list kernels (recommend_lists.hip, explain_lists.hip): users on the grid's x, list chunks on y.
+// Workgroups per user: one for a list of up to two rounds of TILE entries; beyond, as many as bring the grid to about two
+// workgroups per CU, each keeping at least two rounds so that a user's staging is shared.  Never more than 2 * CUs in y,
+// whatever n_list.
+struct ListGrid {
+  dim3 grid;
+  int rounds_per_wg;
+};
+inline ListGrid list_grid(int n_list, int B) {
+  const int rounds = (n_list - 1) / TILE + 1;
+  const int want = std::max(1, (2 * carca_num_cus() + B - 1) / B);
+  const int chunks = std::max(1, std::min(want, rounds / 2));
+  const int rpw = (rounds + chunks - 1) / chunks;
+  return {dim3(B, (rounds + rpw - 1) / rpw), rpw};
+}
+
 // the candidate list of carca_recommend_among / carca_rank_items_among
 inline int check_candidates(const CarcaCandidates* cand, const char* what) {
   CARCA_CHECK_ARG(cand, "%s: null candidate list", what);

@@ -1,6 +1,6 @@
 // Per-(user, item) logit arithmetic and the item order shared by the full-catalogue kernels: the top-k sweep of
 // recommend.hip and the list scoring / counting sweep of rank.hip (both through catalogue_sweep.h), and the per-user list
-// kernels of recommend_lists.hip.  The calls order items
+// kernels of recommend_lists.hip and explain_lists.hip.  The calls order items
 // by the same 64-bit key (order-preserving logit bits, then the complemented id), so they must produce the same logit bits
 // for the same (user, item): every kernel stages a user and scores an item through one of the scorers below
 // (CaScorer, DotScorer: the same five members; CaLongScorer, CaScorer's arithmetic over a profile staged in chunks),
@@ -140,11 +140,11 @@ __device__ __forceinline__ void ca_stage_slots(const Desc& D, int u, const int* 
   __syncthreads();
 }
 
-// One step of a head's online exp2 softmax: staged slot j of head h joins the running (m, den, num).  The only copy of
-// this arithmetic: CaScorer walks all of a user's slots with it, CaLongScorer the same slots 64 at a time.
+// Staged slot j's pre-softmax score of head h, in the exp2 domain (scaled by log2(e) / sqrt(dh), the bias added).  The
+// only copy of this arithmetic: the scorers reach it through ca_slot_step, and explain_lists.hip evaluates it a second
+// time per slot to turn a head's final (m, den) into that slot's softmax weight.
 template <int DHP, int H, class User>
-__device__ __forceinline__ void ca_slot_step(const float (&q)[DHP], const User& S, int h, int j, float sc, float& m,
-                                             float& den, float& num) {
+__device__ __forceinline__ float ca_slot_score(const float (&q)[DHP], const User& S, int h, int j, float sc) {
   const float4* kr = S.Ks4 + (j * DHP * H + h * DHP) / 4;
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -155,12 +155,25 @@ __device__ __forceinline__ void ca_slot_step(const float (&q)[DHP], const User& 
     s0 = fmaf(q[4 * c4 + 2], k4.z, s0);
     s1 = fmaf(q[4 * c4 + 3], k4.w, s1);
   }
-  const float s = fmaf(s0 + s1, sc, S.Bs[h][j]);
+  return fmaf(s0 + s1, sc, S.Bs[h][j]);
+}
+
+// staged slot j of head h, of score s, joins the head's running (m, den, num)
+template <class User>
+__device__ __forceinline__ void ca_online_update(float s, const User& S, int h, int j, float& m, float& den, float& num) {
   const float mn = fmaxf(m, s);
   const float a = exp2f(m - mn), e = exp2f(s - mn);
   den = fmaf(den, a, e);
   num = fmaf(num, a, e * S.Us[j][h]);
   m = mn;
+}
+
+// One step of a head's online exp2 softmax: staged slot j of head h joins the running (m, den, num).  CaScorer walks all
+// of a user's slots with it, CaLongScorer the same slots 64 at a time.
+template <int DHP, int H, class User>
+__device__ __forceinline__ void ca_slot_step(const float (&q)[DHP], const User& S, int h, int j, float sc, float& m,
+                                             float& den, float& num) {
+  ca_online_update(ca_slot_score<DHP, H>(q, S, h, j, sc), S, h, j, m, den, num);
 }
 
 // the terms of a cross-attention logit that no profile slot enters
@@ -176,7 +189,10 @@ __device__ __forceinline__ float ca_logit_offsets(const Desc& D, int u, float it
 template <int DHP, int H>
 struct CaScorer {
   static constexpr bool chunked = false;
-  static constexpr int DPO = DHP * H;
+  static constexpr int DPO = DHP * H, HEADS = H, HEAD_PAD = DHP;
+  struct Stats {
+    float m[H], den[H];  // a head's final running maximum and denominator
+  };
   struct User {
     float4 Ks4[CARCA_MAX_L * DHP * H / 4];  // compacted valid profile slots, head-padded
     float Us[CARCA_MAX_L][H];
@@ -233,6 +249,23 @@ struct CaScorer {
     }
     return logit;
   }
+
+  // logit, leaving each head's final softmax statistics in T (untouched for a fully masked profile): slot j's weight
+  // in head h is exp2(ca_slot_score(j) - T.m[h]) / T.den[h]
+  template <class Desc>
+  __device__ __forceinline__ float logit_stats(const Desc& D, int u, const Item& I, const User& S, Stats& T) const {
+    float logit = ca_logit_offsets(D, u, I.off);
+    if (nv > 0) {  // (a fully masked profile: attention term 0, carca.py:256)
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        float m = -INFINITY, den = 0.f, num = 0.f;
+        for (int j = 0; j < nv; ++j) ca_slot_step<DHP, H>(I.q[h], S, h, j, sc, m, den, num);
+        logit += num / den;
+        T.m[h] = m, T.den[h] = den;
+      }
+    }
+    return logit;
+  }
 };
 
 // Cross-attention decoder, profiles of up to CARCA_MAX_PROFILE_L slots: the valid slots' positions in LDS, their rows
@@ -248,7 +281,7 @@ struct CaLongScorer {
   static constexpr bool chunked = true;
   using Short = CaScorer<DHP, H>;
   using Item = typename Short::Item;
-  static constexpr int ROUNDS = CARCA_MAX_PROFILE_L / TILE, WAVES = TILE / 64;
+  static constexpr int ROUNDS = CARCA_MAX_PROFILE_L / TILE, WAVES = TILE / 64, HEADS = H, HEAD_PAD = DHP;
   static_assert(ROUNDS * TILE == CARCA_MAX_PROFILE_L, "the compaction covers the profile in whole rounds");
   struct User {
     float4 Ks4[CARCA_MAX_L * DHP * H / 4];  // the staged chunk: K rows of CARCA_MAX_L compacted slots, head-padded
@@ -258,7 +291,7 @@ struct CaLongScorer {
     int wcnt[ROUNDS * WAVES];       // valid slots per (round, wave) of the compaction
   };
   struct Acc {
-    float m[H], den[H], num[H];
+    float m[H], den[H], num[H];  // after the last chunk, (m, den) are what CaScorer::logit_stats leaves in its Stats
   };
   Short base;
   int nv;  // valid profile slots of the user begun

@@ -243,23 +243,9 @@ int ls_check(const CarcaListsDesc& D, const char* what) {
   return CARCA_OK;
 }
 
-// Workgroups per user: one for a list of up to two rounds; beyond, as many as bring the grid to about two workgroups per
-// CU, each keeping at least two rounds so that a user's staging is shared.  Never more than 2 * CUs in y, whatever n_list.
-struct LsGrid {
-  dim3 grid;
-  int rounds_per_wg;
-};
-LsGrid ls_grid(int n_list, int B) {
-  const int rounds = (n_list - 1) / LS_TILE + 1;
-  const int want = std::max(1, (2 * carca_num_cus() + B - 1) / B);
-  const int chunks = std::max(1, std::min(want, rounds / 2));
-  const int rpw = (rounds + chunks - 1) / chunks;
-  return {dim3(B, (rounds + rpw - 1) / rpw), rpw};
-}
-
 template <bool RAW>
 int ls_score(const CarcaListsDesc& D, const char* what, float* out, int ld_out, hipStream_t stream) {
-  const LsGrid G = ls_grid(D.n_list, D.B);
+  const rc::ListGrid G = rc::list_grid(D.n_list, D.B);  // (the rounds per workgroup: catalogue_sweep.h)
   return rc::dispatch_scorer(D, what, [&](auto scorer) -> int {
     using Scorer = typename decltype(scorer)::type;
     hipLaunchKernelGGL((ls_score_kernel<Scorer, RAW>), G.grid, dim3(LS_TILE), 0, stream, D, out, ld_out, G.rounds_per_wg);

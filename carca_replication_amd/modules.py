@@ -1426,6 +1426,65 @@ class CARCA(_PackedModule, Model):
         return catalogue.recommend_from("recommend_from", partial(catalogue.carca_model_side, self, profile, context),
                                         profile, items, k, exclude, allow_composed)
 
+    # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists) ------------------
+    def _check_explainable(self, what: str) -> None:
+        if self.training:
+            raise CarcaHipError(f"{what}: the model is in training mode; explanations use eval semantics "
+                                "(call model.eval() first)")
+        if not isinstance(self.decoder, CrossAttentionBlock):
+            raise CarcaHipError(f"{what}: decoder {type(self.decoder).__name__} has no attention over the profile to "
+                                "decompose: its eval score reads the last profile slot only (a cross-attention decoder "
+                                "is needed)")
+        self._check_built()
+
+    def explain_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
+                      allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """Why each item of each user's own list scores what it scores: (scores [B, N], base [B, N],
+        contrib [B, N, L], weights [B, H, N, L]), all float32.
+
+        In eval mode the cross-attention decoder's logit is additive over the profile slots:
+        logit(u, i) = base(u, i) + sum_t contrib[u, i, t], with contrib[u, j, t] = sum_h weights[u, h, j, t] * U[u, t, h],
+        U the decoder FFN folded into the value rows (w_ffn,h . V[u, t, h]) and base the FFN bias plus, with the
+        residual, w_ffn . e(i, context).  scores is score_items' output for the same arguments, bit for bit, and
+        sigmoid(base + contrib.sum(-1)) reproduces it up to fp32 rounding: a true decomposition, not a heuristic.
+        weights[u, h, j, t] is the reference's attention weight (MultiHeadAttention.forward(..., return_w=True)) of head
+        h, query items[u, j], key slot t.  Weights and contributions are exactly 0 at a padding slot (p_x[u, t] == 0,
+        interior zeros included), for an id that is no item (0, or outside [1, n_items): score and base 0 too) and for
+        an empty profile.  items, profile, context, the envelope and allow_composed are score_items'; one launch, no
+        host sync.  A dot decoder raises CarcaHipError."""
+        self._check_explainable("explain_items")
+        return catalogue.explain_items("explain_items", partial(catalogue.carca_model_side, self, profile, context),
+                                       profile, items, allow_composed)
+
+    def explain_top_slots(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor],
+                          items: Tensor, m: int = 3, allow_composed: bool = False
+                          ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        """The m profile slots that contribute most to each (user, item) score: (scores [B, N], base [B, N],
+        slots [B, N, m] int64, slot_items [B, N, m] int64, contrib [B, N, m] float32).
+
+        Per (u, j) the m valid slots with the largest explain_items contribution, in descending order, ties to the later
+        slot (the more recent interaction); slots are positions in [0, L), slot_items the profile ids p_x there, contrib
+        bit for bit the matching entries of explain_items' contrib.  Fewer than m valid slots, and an id that is no
+        item, pad with slot -1, item 0 and contribution 0.  1 <= m <= catalogue.EXPLAIN_TOP_MAX = 8.  No [B, N, L]
+        buffer exists on this path.  Everything else is explain_items'."""
+        self._check_explainable("explain_top_slots")
+        return catalogue.explain_top_slots("explain_top_slots", partial(catalogue.carca_model_side, self, profile, context),
+                                           profile, items, m, allow_composed)
+
+    def recommend_explained(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor],
+                            k: int = 10, m: int = 3, exclude="profile", candidates=None, allow_composed: bool = False
+                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """recommend with its reasons ("because you bought X and Y"): (scores [B, k], ids [B, k],
+        slot_items [B, k, m] int64, contrib [B, k, m] float32).
+
+        scores and ids are recommend's for the same arguments, bit for bit; the last two are explain_top_slots over
+        those ids (the padding id 0 explains as an id that is no item: items 0, contributions 0).  The profile side
+        runs once for both launches.  k, exclude, candidates and allow_composed are recommend's, m explain_top_slots'."""
+        self._check_explainable("recommend_explained")
+        return catalogue.recommend_explained("recommend_explained",
+                                             partial(catalogue.carca_model_side, self, profile, context), profile, k, m,
+                                             exclude, candidates, allow_composed)
+
     # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md 17) ---------------------------------
     def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,
                       candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:

@@ -1009,6 +1009,70 @@ typedef struct CarcaListsDesc {
 int carca_score_lists(const CarcaListsDesc* desc, void* stream);
 int carca_recommend_lists(const CarcaListsDesc* desc, void* stream);
 
+/* ---- which profile slots drive a cross-attention score (the decoder's attention, MultiHeadAttention.forward's
+ * return_w, carca.py:253-263, under CrossAttentionBlock.forward's eval path, carca.py:338-347) ---
+ * The model-side fields (B .. ffn_b) and the list (items / n_list / ld_items) mean exactly what they mean in
+ * CarcaListsDesc; k and the exclusion list are carried so that one model side fills both and are not read.  decoder must
+ * be 0: a dot decoder's eval score reads the last profile slot only (carca.py:362).  For user u and list entry j, with
+ * id = items[u][j], over the user's valid slots t (p_ids[u][t] != 0):
+ *   w_h(t)   = softmax over the valid slots of (q_h(id) + dq_h(u)) . K_h[u][t] / sqrt(d / H): head h's attention weight;
+ *   c(t)     = sum_h w_h(t) * user_u[u * L + t][h], heads in ascending order;
+ *   base     = item_w[id] + user_off[u] + ffn_b[0] (the terms that are given);
+ *   logit    = base + sum_t c(t), and scores[u][j] = sigmoid(logit) with carca_score_lists' bits.
+ * An id of 0 or outside [1, n_items) is no item: score 0, base 0, every weight and contribution 0, never read out of
+ * bounds.  A padding slot (interior ones included) and every slot of an empty profile has weight and contribution 0
+ * (carca.py:256).  Which outputs are given selects the form:
+ *   weights != NULL (dense): contrib [B, n_list, ld_contrib] and weights [B, H, n_list, ld_weights], the first L columns
+ *                     of every row written, padding positions as 0 (no memset needed); slots and slot_items NULL;
+ *   slots != NULL (top_m):  per (u, j) the top_m valid slots with the largest c, descending, ties to the LATER slot:
+ *                     slots [B, n_list, ld_slots] their positions in [0, L), slot_items [B, n_list, ld_slot_items] the
+ *                     profile ids there, contrib [B, n_list, ld_contrib] their c -- bit for bit the dense form's
+ *                     entries; fewer than top_m valid slots, and an id that is no item, pad with slot -1, item 0 and
+ *                     contribution 0.  1 <= top_m <= 8.  No [B, n_list, L] buffer exists; weights NULL.
+ * One launch, the user staged once per workgroup, two passes over the staged slots per entry; no atomics, no scratch,
+ * bit-identical run to run.  L up to CARCA_MAX_PROFILE_L as carca_score_lists.  CARCA_ERR_UNSUPPORTED as
+ * carca_score_lists, and a decoder other than 0 or top_m outside 1..8.  CARCA_ERR_BADARG as carca_score_lists, and null
+ * outputs, both forms or neither, or strides shorter than a row. */
+typedef struct CarcaExplainDesc {
+  int B, L, n_items, d, H, k;
+  int decoder;          /* 0 cross-attention (the only one served) */
+  const int32_t* p_ids; /* [B, ld_p_ids] profile ids */
+  int ld_p_ids;
+  const float* item_q; /* [n_items, ld_item_q] */
+  int ld_item_q;
+  const float* item_w; /* [n_items] with stride ld_item_w, or NULL */
+  int ld_item_w;
+  const float* user_k; /* [B*L, ld_user_k] */
+  int ld_user_k;
+  const float* user_u; /* [B*L, ld_user_u] */
+  int ld_user_u;
+  const float* user_q; /* [B, ld_user_q] (may be NULL) */
+  int ld_user_q;
+  const float* user_m; /* not read */
+  int ld_user_m;
+  const float* user_off; /* [B] with stride ld_user_off, or NULL */
+  int ld_user_off;
+  const float* ffn_b; /* float[1] or NULL */
+  const int32_t* exclude; /* not read */
+  int n_exclude, ld_exclude;
+  const int32_t* items; /* [B, ld_items], first n_list columns: each user's own list */
+  int n_list, ld_items;
+  float* scores; /* [B, ld_scores] */
+  int ld_scores;
+  float* base; /* [B, ld_base] */
+  int ld_base;
+  float* contrib; /* dense: [B, n_list, ld_contrib], L columns; top_m: [B, n_list, ld_contrib], top_m columns */
+  int ld_contrib;
+  float* weights; /* dense: [B, H, n_list, ld_weights], L columns; else NULL */
+  int ld_weights;
+  int64_t* slots; /* top_m: [B, n_list, ld_slots]; else NULL */
+  int ld_slots;
+  int64_t* slot_items; /* top_m: [B, n_list, ld_slot_items]; else NULL */
+  int ld_slot_items;
+  int top_m;
+} CarcaExplainDesc;
+int carca_explain_lists(const CarcaExplainDesc* desc, void* stream);
+
 /* ---- KNN baseline: full-catalogue top-k and exact ranks (replace KNN.forward over the catalogue as target groups:
  * knn.py:13-19 over the candidate lists of data.py:180-185, ranked as train.py:15-32 does) ------
  * The catalogue is the rows of the attribute table [n_items, ld_table] (fp32, F features).  For user u and item i >= 1:
