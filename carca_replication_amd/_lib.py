@@ -21,7 +21,7 @@ _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h"]
+           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -273,6 +273,11 @@ class Candidates(C.Structure):
     _fields_ = [("ids", _fp), ("n", C.c_int32)]
 
 
+class ItemGroups(C.Structure):
+    """CarcaItemGroups (carca_recommend_groups / carca_recommend_capped)."""
+    _fields_ = [("order", _fp), ("offsets", _fp), ("pos_of", _fp), ("n", C.c_int32), ("n_groups", C.c_int32)]
+
+
 _KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_user_a", C.c_int64), ("table", _fp),
               ("ld_table", C.c_int32), ("table_i8", _fp), ("ld_table_i8", C.c_int32), ("exclude", _fp),
               ("n_exclude", C.c_int32), ("ld_exclude", C.c_int32)]
@@ -423,6 +428,8 @@ SIGNATURES = {
     "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
     "carca_recommend_among": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), _fp]),
     "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
+    "carca_recommend_groups": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _fp]),
+    "carca_recommend_capped": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _i, _fp]),
     "carca_score_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_recommend_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_explain_lists": (_i, [C.POINTER(ExplainDesc), _fp]),

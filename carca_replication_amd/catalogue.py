@@ -7,7 +7,9 @@ launch (recommend, rank_items).  A model's two descriptors name their model-side
 ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
 (recommend_diverse, ops.mmr_rerank).  score_items / recommend_from serve a candidate list of its
 own per user (CARCA.score_items / recommend_from).  explain_items / explain_top_slots /
-recommend_explained say which profile slots drive a cross-attention score."""
+recommend_explained say which profile slots drive a cross-attention score.  ItemGroups labels
+items with a group; recommend_by_group / recommend_capped are the top-k of every group and the top-k with a cap per group
+(CARCA.recommend_by_group / recommend_capped)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -86,6 +88,146 @@ def _candidates(what: str, candidates, D, keep: list, device):
     ops._need_cuda(ids)
     keep.append(ids)
     return _lib.Candidates(ids.data_ptr() if ids.shape[0] else None, ids.shape[0])
+
+
+GROUPS_MAX = 65535  # most groups of an ItemGroups (csrc: RG_MAX_GROUPS, a grid dimension)
+CAPPED_SCRATCH_MAX = 1 << 30  # bytes of recommend_capped's [B, G, m] key scratch (csrc: RG_MAX_KEY_BYTES)
+
+
+class ItemGroups:
+    """A group label per item (category, brand, price band, shelf) for CARCA.recommend_by_group / recommend_capped
+    (DESIGN.md section 23), shared by every user of a batch.
+
+    group_of: a 1-D integer tensor [n_items]; entry i is the group of item i, in [0, G).  A negative entry puts the item in
+    no group: the two calls never return it.  Entry 0 (the padding item) is ignored.  G = n_groups when given (an entry
+    >= G raises), else the largest label + 1; empty groups are legal, 1 <= G <= GROUPS_MAX.  The constructor normalises
+    once, on the host -- the copy of group_of to the host is its only sync -- so build it once and reuse it across calls.
+    The fields, all int32 and contiguous on `device` (default: where group_of lives): `order` [C], the grouped ids sorted by
+    (group, id); `offsets` [G + 1], group g owning order[offsets[g]:offsets[g + 1]]; `pos_of` [n_items], the position of an
+    id in order or -1; `group_of` [n_items], normalised: -1 for ungrouped items and for id 0.  n_items and n_groups are
+    ints."""
+
+    def __init__(self, group_of: Tensor, n_groups: Optional[int] = None, device=None):
+        if not isinstance(group_of, Tensor) or group_of.dim() != 1 or group_of.is_floating_point() or \
+                group_of.is_complex() or group_of.dtype == torch.bool or group_of.shape[0] < 1:
+            raise CarcaHipError("ItemGroups: group_of must be a 1-D integer tensor [n_items] of group labels")
+        n_items = group_of.shape[0]
+        g = group_of.detach().to("cpu", torch.int64).clamp(min=-1)  # (the only host sync; clamp copies: group_of is kept)
+        g[0] = -1
+        top = int(g.max())
+        if n_groups is None:
+            G = max(top + 1, 1)
+        else:
+            G = int(n_groups)
+            if G < 1:
+                raise CarcaHipError(f"ItemGroups: n_groups = {G} must be positive")
+            if top >= G:
+                raise CarcaHipError(f"ItemGroups: group label {top} outside [0, n_groups = {G})")
+        if G > GROUPS_MAX:
+            raise CarcaHipError(f"ItemGroups: {G} groups exceed {GROUPS_MAX} (the selection launches one grid row per group)")
+        keys, perm = torch.sort(torch.where(g < 0, G, g), stable=True)  # (group, id): ids ascend inside a group
+        n_grouped = int((g >= 0).sum())
+        order = perm[:n_grouped]
+        offsets = torch.searchsorted(keys[:n_grouped].contiguous(), torch.arange(G + 1))
+        pos_of = torch.full((n_items,), -1, dtype=torch.int64)
+        pos_of[order] = torch.arange(n_grouped)
+        device = group_of.device if device is None else device
+        self.n_items, self.n_groups = n_items, G
+        self._bounds = offsets.tolist()  # host copy: members() slices without a sync
+        self.order, self.offsets, self.pos_of, self.group_of = (
+            t.to(dtype=torch.int32, device=device).contiguous() for t in (order, offsets, pos_of, g))
+
+    def __len__(self) -> int:
+        return self.order.shape[0]
+
+    def to(self, device) -> "ItemGroups":
+        """The groups on `device`: itself when they are there already, else a copy of the normalised fields (no host
+        sync)."""
+        order = self.order.to(device)
+        if order is self.order:
+            return self
+        out = object.__new__(ItemGroups)
+        out.n_items, out.n_groups, out._bounds, out.order = self.n_items, self.n_groups, self._bounds, order
+        out.offsets, out.pos_of, out.group_of = self.offsets.to(device), self.pos_of.to(device), self.group_of.to(device)
+        return out
+
+    def members(self, g: int) -> Tensor:
+        """The ids of group g: its slice of `order`, ascending -- a valid CandidateSet argument (no host sync)."""
+        if not 0 <= int(g) < self.n_groups:
+            raise CarcaHipError(f"ItemGroups.members: group {g} outside [0, {self.n_groups})")
+        return self.order[self._bounds[int(g)]:self._bounds[int(g) + 1]]
+
+
+def check_groups(what: str, groups, n_items: Optional[int]) -> None:
+    """groups is an ItemGroups and, where the catalogue size is known, was built for it."""
+    if not isinstance(groups, ItemGroups):
+        raise CarcaHipError(f"{what}: groups must be a catalogue.ItemGroups")
+    if n_items is not None and groups.n_items != n_items:
+        raise CarcaHipError(f"{what}: the item groups were built for n_items = {groups.n_items}, the model has {n_items}")
+
+
+def _groups(what: str, groups: ItemGroups, D, keep: list, device):
+    """-> the CarcaItemGroups struct of the launch."""
+    check_groups(what, groups, D.n_items)
+    gr = groups.to(device)
+    ops._need_cuda(gr.order, gr.offsets, gr.pos_of)
+    keep += [gr.order, gr.offsets, gr.pos_of]
+    return _lib.ItemGroups(gr.order.data_ptr() if len(gr) else None, gr.offsets.data_ptr(), gr.pos_of.data_ptr(), len(gr),
+                           gr.n_groups)
+
+
+def grouped_args(what: str, groups, k: int, max_per_group: int = 1, n_items: Optional[int] = None) -> None:
+    """The argument checks of recommend_by_group / recommend_capped that need no launch."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    if int(max_per_group) < 1:
+        raise CarcaHipError(f"{what}: max_per_group = {max_per_group} must be positive")
+    check_groups(what, groups, n_items)
+
+
+def recommend_by_group(what: str, fill: Callable, profile, groups: ItemGroups, k: int, exclude,
+                       allow_composed: bool = False, n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The k best items of every group per user (carca_recommend_groups): (scores [B, G, k] float32, ids [B, G, k] int64).
+    n_items: the model's catalogue size where the caller knows it without a launch (checked before the model side runs)."""
+    grouped_args(what, groups, k, 1, n_items)
+    with torch.no_grad():
+        D = _lib.RecommendDesc()
+        keep, p_ids = _fill(fill, what, D, allow_composed)
+        D.k = k = int(k)
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        device = profile[0].device
+        gr = _groups(what, groups, D, keep, device)
+        G = groups.n_groups
+        scores = torch.empty(D.B, G, k, dtype=torch.float32, device=device)
+        ids = torch.empty(D.B, G, k, dtype=torch.int64, device=device)
+        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), G * k, ids.data_ptr(), G * k
+        _lib.check(_lib.load().carca_recommend_groups(C.byref(D), C.byref(gr), ops._stream()), what)
+        return scores, ids
+
+
+def recommend_capped(what: str, fill: Callable, profile, groups: ItemGroups, k: int, max_per_group: int, exclude,
+                     allow_composed: bool = False, n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The k best grouped items per user with at most max_per_group of any one group (carca_recommend_capped):
+    (scores [B, k] float32, ids [B, k] int64)."""
+    grouped_args(what, groups, k, max_per_group, n_items)
+    k = int(k)
+    m = min(k, int(max_per_group))
+    B = profile[0].shape[0]
+    if B * groups.n_groups * m * 8 > CAPPED_SCRATCH_MAX:
+        raise CarcaHipError(f"{what}: B = {B} users x G = {groups.n_groups} groups x m = {m} per group: the key scratch "
+                            f"of {B * groups.n_groups * m * 8} bytes exceeds {CAPPED_SCRATCH_MAX} (split the batch)")
+    with torch.no_grad():
+        D = _lib.RecommendDesc()
+        keep, p_ids = _fill(fill, what, D, allow_composed)
+        D.k = k
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        device = profile[0].device
+        gr = _groups(what, groups, D, keep, device)
+        scores = torch.empty(D.B, k, dtype=torch.float32, device=device)
+        ids = torch.empty(D.B, k, dtype=torch.int64, device=device)
+        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), k, ids.data_ptr(), k
+        _lib.check(_lib.load().carca_recommend_capped(C.byref(D), C.byref(gr), m, ops._stream()), what)
+        return scores, ids
 
 
 def carca_route(what: str, d: int, encoder_heads, L: int, decoder_heads: Optional[int], allow_composed: bool) -> str:

@@ -102,6 +102,25 @@ struct UserLists {
   __device__ __forceinline__ ListedRow for_user(int u) const { return ListedRow{ids + (size_t)u * ld, n}; }
 };
 
+// The grouped order of CarcaItemGroups (group_select.h): positions 0 .. n - 1 of `order`, sorted by (group, id).  The
+// sweep reads such an order through ListedItems (it asks only for item(pos)); this map is for the launches that look an id
+// up.  find(id) = pos_of[id]: `order` is not ascending across groups, so ListedItems' binary search does not apply (the
+// caller has checked 1 <= id < n_items = the entries of pos_of; an entry outside [0, n) counts as "not grouped" and is
+// never used as an index).
+struct GroupedItems {
+  static constexpr bool listed = true;
+  const int32_t* order;
+  const int32_t* pos_of;
+  int n;
+  __device__ __forceinline__ GroupedItems for_user(int) const { return *this; }
+  __device__ __forceinline__ int size(int) const { return n; }
+  __device__ __forceinline__ int item(int pos) const { return pos < n ? order[pos] : 0; }
+  __device__ __forceinline__ int find(int id) const {
+    const int p = pos_of[id];
+    return (p >= 0 && p < n) ? p : -1;
+  }
+};
+
 // ---- the scorers ---------------------------------------------------------------------------------------------------
 // A scorer is built per thread from the descriptor and has: User (one user's share, in LDS), Item (one item's share, in
 // registers), load_item (zeros where !live), stage_user (whole workgroup of TILE threads; the caller has synchronised

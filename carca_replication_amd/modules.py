@@ -1426,6 +1426,54 @@ class CARCA(_PackedModule, Model):
         return catalogue.recommend_from("recommend_from", partial(catalogue.carca_model_side, self, profile, context),
                                         profile, items, k, exclude, allow_composed)
 
+    # ---- item groups (include/carca_hip.h: carca_recommend_groups / carca_recommend_capped) -------------
+    def _catalogue_size(self) -> Optional[int]:
+        """n_items where no launch is needed to know it: the id table's rows, else the registered attribute table's."""
+        emb = self.embeds
+        if isinstance(getattr(emb, "items_embed", None), nn.Embedding):
+            return emb.items_embed.num_embeddings
+        table = emb.attr_table() if hasattr(emb, "attr_table") else None
+        return None if table is None else table.shape[0]
+
+    def recommend_by_group(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], groups,
+                           k: int = 10, exclude="profile", allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+        """The k best items of EVERY group per user, in one call: (scores [B, G, k] float32, ids [B, G, k] int64).
+
+        groups: a catalogue.ItemGroups built for this model's n_items (a group label per item; an item without a label
+        is never returned).  Row (u, g) is bit for bit row u of recommend(profile, context, k, exclude,
+        candidates=groups.members(g), allow_composed), in both outputs: logit descending, ties to the smaller id,
+        excluded ids never, padded with id 0 and score 0 where the group has fewer than k eligible items; an empty group
+        is all padding.  The profile side runs once and the catalogue is swept once, in group-major order; one selection
+        launch picks every (user, group) list.  No host sync.  There is no candidates= argument: restrict the call by
+        leaving items ungrouped.  profile, context, exclude, 1 <= k <= 128, the envelope and allow_composed are
+        recommend's."""
+        if self.training:
+            raise CarcaHipError("recommend_by_group: the model is in training mode; recommendation scores with eval "
+                                "semantics (call model.eval() first)")
+        self._check_built()
+        return catalogue.recommend_by_group("recommend_by_group", partial(catalogue.carca_model_side, self, profile, context),
+                                            profile, groups, k, exclude, allow_composed, self._catalogue_size())
+
+    def recommend_capped(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], groups,
+                         k: int = 10, max_per_group: int = 1, exclude="profile",
+                         allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+        """The k best items per user with at most max_per_group from any one group ("at most two per brand"):
+        (scores [B, k] float32, ids [B, k] int64).
+
+        The result is recommend's order over the grouped, non-excluded items walked from the best, skipping an item once
+        its group has max_per_group items in the list, until k are taken; ties go to the smaller id, across groups too;
+        padding as recommend's; items without a label are not eligible.  max_per_group >= k leaves the cap inactive: the
+        call is then recommend over the grouped items.  A returned item's score has recommend's bits.  The device side
+        takes every group's best min(k, max_per_group) and then the k best of their union, through a
+        [B, G, min(k, max_per_group)] buffer of 64-bit keys; a buffer beyond 1 GiB raises CarcaHipError (split the batch).
+        No host sync.  groups, profile, context, exclude, k, the envelope and allow_composed: as recommend_by_group."""
+        if self.training:
+            raise CarcaHipError("recommend_capped: the model is in training mode; recommendation scores with eval "
+                                "semantics (call model.eval() first)")
+        self._check_built()
+        return catalogue.recommend_capped("recommend_capped", partial(catalogue.carca_model_side, self, profile, context),
+                                          profile, groups, k, max_per_group, exclude, allow_composed, self._catalogue_size())
+
     # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists; DESIGN.md 22) ------------------
     def _check_explainable(self, what: str) -> None:
         if self.training:

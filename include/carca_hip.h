@@ -954,6 +954,43 @@ typedef struct CarcaCandidates {
 int carca_recommend_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
 int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* candidates, void* stream);
 
+/* ---- item groups: the k best of EVERY group in one call, and the k best overall with at most m per group (a page of
+ * carousels; "at most two per brand") ----------------------------------------------------------
+ * CarcaItemGroups labels items with one of n_groups groups (category, brand, shelf); an item may carry no label and is
+ * then never returned.  All arrays int32 on the device, the caller's contract:
+ *   order   [n]            the grouped ids, sorted by (group, id): every id in [1, n_items), distinct;
+ *   offsets [n_groups + 1] group g owns positions [offsets[g], offsets[g + 1]) of order; nondecreasing, offsets[0] = 0,
+ *                          offsets[n_groups] = n; an empty group is legal;
+ *   pos_of  [n_items]      the position of an id in order, -1 where it has none (n_items is the descriptor's).
+ * A bound of offsets outside [0, n], or an entry of pos_of outside [-1, n), is clamped or ignored and never used as an
+ * index.  The descriptor is carca_recommend's own.  The catalogue is swept ONCE, in the grouped order, by
+ * carca_recommend_among's scoring launch (the logit of a (user, item) pair does not depend on the position that holds
+ * the item: the same bits), into stream scratch [B, n]; the exclusion launch finds an id's position in pos_of.
+ *
+ * carca_recommend_groups: per (user, group) the k best items of the group minus the excluded ids, in carca_recommend's
+ * order (logit descending, ties to the smaller id), padded with id 0 and score 0 -- list (u, g) is bit for bit row u of
+ * carca_recommend_among over group g's slice of order.  scores / ids_out: row u holds the n_groups lists side by side,
+ * scores[u][g * k + j] (ld_scores, ld_ids_out >= n_groups * k).  One selection launch, grid (B, n_groups).
+ *
+ * carca_recommend_capped: per user carca_recommend's order over the grouped, non-excluded items walked from the best,
+ * skipping an item once max_per_group items of its group are in the list, until k are taken; ties go to the smaller id
+ * across groups too; padding as carca_recommend; max_per_group >= k: no cap.  scores / ids_out [B, k].  Two launches behind
+ * the exclusion: every group's best m = min(k, max_per_group) as 64-bit keys on the item id, [B, n_groups, m] uint64 of
+ * stream scratch, then per user the k largest of them.
+ *
+ * Bit-identical run to run.  Limits and errors as carca_recommend, and CARCA_ERR_UNSUPPORTED for n_groups > 65535 or a key
+ * scratch B * n_groups * m * 8 beyond 1 GiB; CARCA_ERR_BADARG for null groups or arrays, n_groups < 1, n outside
+ * [0, n_items) or max_per_group < 1. */
+typedef struct CarcaItemGroups {
+  const int32_t* order;   /* [n] */
+  const int32_t* offsets; /* [n_groups + 1] */
+  const int32_t* pos_of;  /* [n_items] */
+  int n;                  /* grouped items */
+  int n_groups;
+} CarcaItemGroups;
+int carca_recommend_groups(const CarcaRecommendDesc* desc, const CarcaItemGroups* groups, void* stream);
+int carca_recommend_capped(const CarcaRecommendDesc* desc, const CarcaItemGroups* groups, int max_per_group, void* stream);
+
 /* ---- a candidate list of its own per user (the second stage behind a retriever; the evaluation protocol's 1 + 100
  * candidates, data.py:180-185) ---------------------------------------------------------------
  * The model-side fields (B .. ffn_b), k and the exclusion list mean exactly what they mean in CarcaRecommendDesc, and the
