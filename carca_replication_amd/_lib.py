@@ -400,6 +400,7 @@ SIGNATURES = {
     "carca_feat_dedup_rows_multiplied": (C.c_longlong, []),
     "carca_feat_dedup_rows_computed": (C.c_longlong, []),
     "carca_feat_dedup_rows_grouped": (C.c_longlong, []),
+    "carca_sa_eval_lent": (C.c_longlong, []),
     "carca_feat_cache_arm": (_i, [C.POINTER(FeatCache)]),
     "carca_get_tuning": (_i, [_i]),
     "carca_mha_core_drop": (_i, [_fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, C.POINTER(Dropout),

@@ -235,6 +235,7 @@ enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRA
        CARCA_TUNE_FEAT_DEDUP = 20,
        CARCA_TUNE_FEAT_CACHE = 21,         // 1: the evaluation dedup never uses a per-item cache of P rows (A/B, tests)
        CARCA_TUNE_DEDUP_SOLO = 22,         // 1: every row issues its own compare with its cache entry (ranks taken, unused)
+       CARCA_TUNE_SA_LEND = 23,            // 1: the eval SelfAttentionBlock never lends idle workgroups to four-tile users (A/B, tests)
        CARCA_TUNE_COUNT = 24 };
 // Values of key 0 (CARCA_TUNE_GEMM_VARIANT): A/B switches of the row GEMMs, the weight-gradient GEMMs and the gather, one
 // at a time -- which is why 158 exists.  A value with two meanings switches both.

@@ -1318,6 +1318,14 @@ def feat_dedup_rows_grouped() -> int:
 
 TUNE_FEAT_CACHE = 21  # 1: the evaluation dedup never uses the per-item cache of P rows (A/B, tests)
 TUNE_DEDUP_SOLO = 22  # 1: under that cache every row compares with its entry itself (A/B, tests); the cache stays on
+TUNE_SA_LEND = 23  # 1: the eval SelfAttentionBlock never lends idle workgroups to four-tile users (A/B, tests)
+
+
+def sa_eval_lent() -> int:
+    """Workgroups that the calling thread's last eager eval-mode SelfAttentionBlock launch lent to another user (the
+    idle second workgroup of a one-tile user takes tiles 0 / 1 of a four-tile user; waits for the launch's stream); 0
+    where nothing was lent, -1 before the first such launch."""
+    return int(_lib.load().carca_sa_eval_lent())
 
 
 def get_tuning(key: int) -> int:

@@ -107,7 +107,9 @@ int carca_abi_version(void);
  *          row per group of equal attribute rows (CARCA_EMBED_DEDUP), 1 = over every kept row (A/B, tests)
  *   key 21 1 = the per-item cache of that product (carca_feat_cache_arm) is never used (A/B, tests)
  *   key 22 1 = under that cache every row compares its bytes with its entry itself; 0 = one row of up to four of an item
- *          compares for all of them with one read of the entry (the same results; A/B, tests).  Does not switch the cache off */
+ *          compares for all of them with one read of the entry (the same results; A/B, tests).  Does not switch the cache off
+ *   key 23 eval SelfAttentionBlock with two workgroups per user and pads_uniform: 0 = the idle second workgroups of one-tile
+ *          users take query tiles of four-tile users, 1 = never (the same bits; A/B, tests) */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
@@ -366,6 +368,11 @@ int carca_sa_block_fwd(const float* x /*[B*L, ldx]*/, int ldx, const int32_t* id
  *   tiles.  0 = no assumption (what carca_sa_block_fwd passes for save == NULL, drop == NULL). */
 int carca_sa_block_eval(const float* x, int ldx, const int32_t* ids, float* y, int ldy, int B, int L, int d, int H,
                         const CarcaSaWeights* w /*host struct*/, int residual, int pads_uniform, void* stream);
+/* Workgroups that the calling thread's last eager eval-mode launch of the block lent to another user: with two workgroups
+ * per user and pads_uniform, the second workgroup of a one-tile user (it has no tile of its own) takes tiles 0 / 1 of a
+ * four-tile user, up to two donors per recipient, both in user order (tuning key 23 = 1: never).  Read back once the
+ * launch's stream has drained; 0 where nothing was lent, -1 before the first such launch. */
+long long carca_sa_eval_lent(void);
 
 /* ---- a5 + a6: final LayerNorm + CrossAttentionBlock.forward, grouped --------------------------
  * Replaces CARCA.forward's final norm (carca.py:421) and, for every target group,
