@@ -19,9 +19,10 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
-           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip"]
+           "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
+           "recommend_users.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h"]
+           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -278,6 +279,11 @@ class ItemGroups(C.Structure):
     _fields_ = [("order", _fp), ("offsets", _fp), ("pos_of", _fp), ("n", C.c_int32), ("n_groups", C.c_int32)]
 
 
+class Audience(C.Structure):
+    """CarcaAudience (carca_recommend_users)."""
+    _fields_ = [("keys", _fp), ("ld_keys", C.c_int32), ("user_ids", _fp), ("user_base", C.c_int32)]
+
+
 _KNN_MODEL = [("p_ids", _fp), ("ld_p_ids", C.c_int32), ("user_a", _fp), ("ld_user_a", C.c_int64), ("table", _fp),
               ("ld_table", C.c_int32), ("table_i8", _fp), ("ld_table_i8", C.c_int32), ("exclude", _fp),
               ("n_exclude", C.c_int32), ("ld_exclude", C.c_int32)]
@@ -431,6 +437,8 @@ SIGNATURES = {
     "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
     "carca_recommend_groups": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _fp]),
     "carca_recommend_capped": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _i, _fp]),
+    "carca_recommend_users": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Audience), _fp]),
+    "carca_audience_read": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _fp]),
     "carca_score_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_recommend_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_explain_lists": (_i, [C.POINTER(ExplainDesc), _fp]),

@@ -9,10 +9,13 @@ ops.similar_rows).  mmr_rerank is the diversity re-rank of
 own per user (CARCA.score_items / recommend_from).  explain_items / explain_top_slots /
 recommend_explained say which profile slots drive a cross-attention score.  ItemGroups labels
 items with a group; recommend_by_group / recommend_capped are the top-k of every group and the top-k with a cap per group
-(CARCA.recommend_by_group / recommend_capped)."""
+(CARCA.recommend_by_group / recommend_capped).  AudienceTopK / recommend_users turn the question
+round: the k best users of each listed item, kept across batches (CARCA.recommend_users, train.audience; DESIGN.md
+section 24)."""
 from __future__ import annotations
 
 import ctypes as C
+from functools import partial
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -585,6 +588,127 @@ def recommend_explained(what: str, fill: Callable, profile, k: int, m: int, excl
             setattr(E, name, getattr(D, name))
         _, _, _, slot_items, contrib = _explain_launch(what, E, keep, ops._ids32(ids), m, device)  # (id 0: no item)
         return scores, ids, slot_items, contrib
+
+
+# ---- the k best users per listed item (include/carca_hip.h: carca_recommend_users) --------------
+AUDIENCE_ID_END = 1 << 31  # user ids stay below it: the low word of a key holds the complemented id
+
+
+class AudienceTopK:
+    """The running k best users of each of Q listed items, over as many user batches as the caller feeds: the state behind
+    CARCA.recommend_users and train.audience.
+
+    items: a CandidateSet built for n_items, or a 1-D integer tensor / bool mask [n_items], normalised here (one host
+    sync).  `ids` holds the item ids, int32 [Q], ascending and distinct: row q of the state and of every result belongs
+    to item ids[q].  `keys` is the state, int64 [Q, k] holding unsigned 64-bit keys: the high word is the logit's
+    order-preserving bits (csrc: rc::order_bits), the low word 0xFFFFFFFF minus the user id, 0 means empty, and every row is
+    sorted descending (as unsigned) after every update.  A larger key is a larger logit and, between equal logits, the
+    smaller user id; keys are distinct per user, so the state after a set of updates is the same bits however the users
+    were split into updates and in whatever order the updates arrived.  Feeding one user id twice is the caller's error:
+    both entries count.  `rows_seen` counts the rows of every update so far."""
+
+    def __init__(self, items, k: int, n_items: int, device=None):
+        what = "AudienceTopK"
+        if not 1 <= int(k) <= KMAX:
+            raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+        if isinstance(items, CandidateSet):
+            if items.n_items != int(n_items):
+                raise CarcaHipError(f"{what}: the item set was built for n_items = {items.n_items}, the model has "
+                                    f"{int(n_items)}")
+        elif isinstance(items, Tensor):
+            items = CandidateSet(items, n_items, device=device)
+        else:
+            raise CarcaHipError(f"{what}: items must be a CandidateSet or a 1-D integer / bool tensor")
+        if device is not None:
+            items = items.to(device)
+        self.items, self.ids, self.k, self.n_items = items, items.ids, int(k), int(n_items)
+        self.keys = torch.zeros(len(items), self.k, dtype=torch.int64, device=self.ids.device)
+        self.rows_seen = 0
+        self._decoder = None  # the link result() applies: the decoder code of the model that fed the state
+
+    def reset(self) -> None:
+        """Clears the state: no user seen, every entry empty (no host sync)."""
+        self.keys.zero_()
+        self.rows_seen = 0
+        self._decoder = None
+
+    def update(self, model, profile, context: Optional[Tensor], user_ids: Optional[Tensor] = None, exclude="profile",
+               allow_composed: bool = False, _what: str = "AudienceTopK.update") -> None:
+        """Merges one batch of users into the state: no host sync, nothing returned.  profile, context, exclude and
+        allow_composed are CARCA.recommend's (user u is not eligible for an item its exclusion row lists).  user_ids: an
+        int32 / int64 [B] tensor of ids below 2^31, a negative entry dropping its row; None numbers the rows from
+        rows_seen on."""
+        what = _what
+        if not hasattr(model, "_check_built") or not hasattr(model, "_catalogue_size"):
+            raise CarcaHipError(f"{what}: model must be a CARCA ({type(model).__name__} has no users-per-item call)")
+        if model.training:
+            raise CarcaHipError(f"{what}: the model is in training mode; recommendation scores with eval semantics "
+                                "(call model.eval() first)")
+        model._check_built()
+        B, Q = profile[0].shape[0], len(self.items)
+        n_known = model._catalogue_size()
+        if n_known is not None and n_known != self.n_items:
+            raise CarcaHipError(f"{what}: the item set was built for n_items = {self.n_items}, the model has {n_known}")
+        if user_ids is not None:
+            if not isinstance(user_ids, Tensor) or user_ids.dtype not in (torch.int32, torch.int64) or \
+                    tuple(user_ids.shape) != (B,):
+                raise CarcaHipError(f"{what}: user_ids must be an int32 / int64 [B = {B}] tensor")
+        elif self.rows_seen + B >= AUDIENCE_ID_END:
+            raise CarcaHipError(f"{what}: {self.rows_seen} rows seen + {B}: a row id would reach 2^31 (pass user_ids)")
+        if B * Q >= 1 << 31:
+            raise CarcaHipError(f"{what}: B * Q = {B * Q} does not fit an int (split the users)")
+        with torch.no_grad():
+            D = _lib.RecommendDesc()
+            keep, p_ids = _fill(partial(carca_model_side, model, profile, context), what, D, allow_composed)
+            if D.n_items != self.n_items:
+                raise CarcaHipError(f"{what}: the item set was built for n_items = {self.n_items}, the model has "
+                                    f"{D.n_items}")
+            if self._decoder not in (None, D.decoder):
+                raise CarcaHipError(f"{what}: the state was fed by a model with another decoder (reset() it first)")
+            D.k = self.k
+            _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+            ids = self.ids
+            if ids.device != profile[0].device or self.keys.device != ids.device:
+                raise CarcaHipError(f"{what}: the state lives on {ids.device}, the batch on {profile[0].device}")
+            ops._need_cuda(ids, self.keys)
+            cand = _lib.Candidates(ids.data_ptr() if Q else None, Q)
+            state = _lib.Audience(self.keys.data_ptr() if Q else None, self.k, None, self.rows_seen)
+            if user_ids is not None:
+                ops._need_cuda(user_ids)
+                # (clamped before the cast: no int64 id below -2^31 wraps into a user)
+                u32 = ops._ids32(user_ids if user_ids.dtype == torch.int32 else user_ids.clamp(min=-1))
+                keep.append(u32)
+                state.user_ids, state.user_base = u32.data_ptr(), 0
+            _lib.check(_lib.load().carca_recommend_users(C.byref(D), C.byref(cand), C.byref(state), ops._stream()), what)
+            self._decoder = D.decoder
+        self.rows_seen += B
+
+    def result(self) -> Tuple[Tensor, Tensor, Tensor]:
+        """(scores [Q, k] float32, users [Q, k] int64, item_ids [Q] int64): row q the k best eligible users seen so far for
+        item item_ids[q], best first -- larger logit first, ties to the smaller user id; scores[q, j] is recommend's score
+        of (users[q, j], item_ids[q]), bit for bit; fewer than k eligible users pad with user -1 and score 0.  The state
+        is left as it is (no host sync)."""
+        Q, k = self.keys.shape
+        scores = torch.empty(Q, k, dtype=torch.float32, device=self.keys.device)
+        users = torch.empty(Q, k, dtype=torch.int64, device=self.keys.device)
+        if Q:
+            ops._need_cuda(self.keys)
+            rc = _lib.load().carca_audience_read(self.keys.data_ptr(), k, Q, k, self._decoder or 0, scores.data_ptr(),
+                                                 users.data_ptr(), ops._stream())
+            _lib.check(rc, "AudienceTopK.result")
+        return scores, users, self.ids.to(torch.int64)
+
+
+def recommend_users(model, profile, context: Optional[Tensor], items, k: int, exclude, user_ids: Optional[Tensor],
+                    allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """CARCA.recommend_users: a fresh AudienceTopK on the batch's device, one update, result()."""
+    n_items = model._catalogue_size()
+    if n_items is None:  # (no id table and no registered attribute table to read it from: the cached item table's rows)
+        with torch.no_grad():
+            n_items = model.embeds.item_table().shape[0]
+    state = AudienceTopK(items, k, n_items, device=profile[0].device)
+    state.update(model, profile, context, user_ids, exclude, allow_composed, _what="recommend_users")
+    return state.result()
 
 
 # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md section 17) ------------------------------

@@ -7,7 +7,7 @@
 //   cross-attention  sum_h softmax_l((QT[i]_h . K_hl + beta_hl) / sqrt(dh)) . u_hl  (+ wT[i]) + off_u
 //   dot decoders     p_u . (T[i] + m_u), divided by ||T[i] + m_u|| for the normalised WeightedDotProduct
 // Three launches, no host wait, nothing retained:
-//   1. scoring, the sweep of catalogue_sweep.h with the sink below: workgroups own 256-item tiles (one item per lane, its
+//   1. scoring, the sweep of catalogue_sweep.h with rc::RcStoreSink: workgroups own 256-item tiles (one item per lane, its
 //      row in registers) and walk a chunk of users, each user's keys / folded values / score biases staged in LDS
 //      (recommend_common.h) -- whole for a profile of up to CARCA_MAX_L slots, in chunks of CARCA_MAX_L valid slots
 //      beyond (rc::CaLongScorer under rc::sweep_long_kernel; the dot decoders read no L); raw logits go to a
@@ -16,7 +16,8 @@
 //   3. selection: one workgroup per user, an MSB-first radix select over 64-bit keys (order-preserving logit bits,
 //      then the complemented item id, so ties go to the smaller id), a bitonic sort of the k survivors, and the link
 //      (sigmoid, or (y + 1) / 2) applied to the k selected logits only.
-// Launches 2 and 3 live in catalogue_select.h, shared with carca_knn_recommend (knn_catalogue.hip).
+// Launches 2 and 3 live in catalogue_select.h, shared with carca_knn_recommend (knn_catalogue.hip); the sink and the host
+// side of launches 1 and 2 (rc::rc_score) in recommend_score.h, shared with carca_recommend_users (recommend_users.hip).
 // Integer LDS atomics only (histograms, slot counters); the result does not depend on scheduling.
 //
 // carca_recommend_among runs the same three launches over a candidate list S (ascending, distinct ids) in place of the
@@ -28,29 +29,10 @@
 // CarcaItemGroups::order through rc::ListedItems, carca_recommend_among's scoring launch and so its logit bits -- exclude
 // through rc::GroupedItems (pos_of[id]: the order ascends only inside a group), and select per (user, group) segment with
 // the kernels of group_select.h.
-#include "catalogue_select.h"
-#include "catalogue_sweep.h"
 #include "group_select.h"
+#include "recommend_score.h"
 
 namespace {
-
-// the sweep's sink: the raw logit into the [B, n_items] buffer -- or, under a candidate list, into the [B, C] buffer at
-// the item's position, a listed id outside the catalogue as the exclusion sentinel
-template <class Map>
-struct RcStoreSink {
-  using Desc = CarcaRecommendDesc;
-  struct Lds {};
-  float* logits;
-  int ld_s;
-  __device__ __forceinline__ void begin_user(const Desc&, int, Lds&) const {}
-  __device__ __forceinline__ void put(const Desc&, int u, int pos, int, bool live, float logit, Lds&) const {
-    if constexpr (Map::listed) {
-      if (pos < ld_s) logits[(size_t)u * ld_s + pos] = live ? logit : __uint_as_float(rc::RC_SENTINEL);
-    } else {
-      if (live) logits[(size_t)u * ld_s + pos] = logit;
-    }
-  }
-};
 
 // the checks of a top-k call; out_cols: the columns a user's row of the two outputs holds
 int rc_check(const CarcaRecommendDesc& D, long long out_cols) {
@@ -62,45 +44,11 @@ int rc_check(const CarcaRecommendDesc& D, long long out_cols) {
   return CARCA_OK;
 }
 
-// The scoring and exclusion launches.  n_slots: the columns of the logit buffer, n_items or the listed count; map: which
-// item a column holds (the sweep asks it only for item(pos)); finder: where the exclusion launch finds an id's column --
-// the map itself, or rc::GroupedItems over a grouped order, which is not ascending.  *out: the [B, n_slots] raw logits.
-template <class Map, class Finder>
-int rc_score(const CarcaRecommendDesc& D, Map map, Finder finder, int n_slots, hipStream_t stream, float** out) {
-  // raw logits [B, n_slots]: stream scratch (or the capture's memory), consumed by the launches behind the scoring one
-  const int ld_s = n_slots;
-  const size_t bytes = std::max((size_t)D.B * (size_t)ld_s, (size_t)1) * sizeof(float);
-  float* logits = (float*)(carca_stream_capturing(stream) ? carca_capture_alloc(stream, bytes, false, nullptr)
-                                                          : carca_stream_scratch(stream, CARCA_SCRATCH_RECOMMEND, bytes));
-  CARCA_CHECK_ARG(logits, "recommend: scratch allocation of %zu bytes failed", bytes);
-  *out = logits;
-  if (n_slots > 0) {  // (an empty candidate list: no tile to sweep, selection finds no eligible item)
-    const rc::SweepGrid G = rc::sweep_grid(n_slots, D.B);
-    const int rc = rc::dispatch_scorer(D, "recommend", [&](auto scorer) -> int {
-      using Scorer = typename decltype(scorer)::type;
-      if constexpr (Scorer::chunked) {  // cross-attention over a profile of more than CARCA_MAX_L slots
-        hipLaunchKernelGGL((rc::sweep_long_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
-                           RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
-      } else {
-        hipLaunchKernelGGL((rc::sweep_kernel<Scorer, RcStoreSink<Map>, Map>), G.grid, dim3(rc::TILE), 0, stream, D,
-                           RcStoreSink<Map>{logits, ld_s}, G.users_per_block, map);
-      }
-      CARCA_LAUNCH_CHECK();
-      return CARCA_OK;
-    });
-    if (rc != CARCA_OK) return rc;
-    hipLaunchKernelGGL((rc::rc_exclude_kernel<CarcaRecommendDesc, Finder>), dim3(D.B), dim3(64), 0, stream, D, logits, ld_s,
-                       finder);
-    CARCA_LAUNCH_CHECK();
-  }
-  return CARCA_OK;
-}
-
 template <class Map>
 int rc_run(const CarcaRecommendDesc& D, Map map, int n_slots, hipStream_t stream) {
   if (int rc = rc_check(D, D.k)) return rc;
   float* logits = nullptr;
-  if (int rc = rc_score(D, map, map, n_slots, stream, &logits)) return rc;
+  if (int rc = rc::rc_score(D, map, map, n_slots, stream, &logits)) return rc;
   hipLaunchKernelGGL((rc::rc_select_kernel<CarcaRecommendDesc, Map>), dim3(D.B), dim3(rc::RC_SEL_THREADS), 0, stream, D,
                      logits, n_slots, map);
   CARCA_LAUNCH_CHECK();
@@ -124,7 +72,7 @@ int rg_check(const CarcaRecommendDesc& D, const CarcaItemGroups* g, const char* 
 // the sweep over the grouped order through rc::ListedItems -- carca_recommend_among's instantiation, so a pair's logit
 // bits are carca_recommend's -- and the exclusion through rc::GroupedItems
 int rg_score(const CarcaRecommendDesc& D, const CarcaItemGroups& g, hipStream_t stream, float** logits) {
-  return rc_score(D, rc::ListedItems{g.order, g.n}, rc::GroupedItems{g.order, g.pos_of, g.n}, g.n, stream, logits);
+  return rc::rc_score(D, rc::ListedItems{g.order, g.n}, rc::GroupedItems{g.order, g.pos_of, g.n}, g.n, stream, logits);
 }
 
 }  // namespace

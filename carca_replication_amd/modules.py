@@ -1474,6 +1474,30 @@ class CARCA(_PackedModule, Model):
         return catalogue.recommend_capped("recommend_capped", partial(catalogue.carca_model_side, self, profile, context),
                                           profile, groups, k, max_per_group, exclude, allow_composed, self._catalogue_size())
 
+    # ---- the k best users per listed item (include/carca_hip.h: carca_recommend_users) ------------------
+    def recommend_users(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items,
+                        k: int = 10, exclude="profile", user_ids: Optional[Tensor] = None,
+                        allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """The k best USERS of the batch for each listed item ("who should hear about these Q items"):
+        (scores [Q, k] float32, users [Q, k] int64, item_ids [Q] int64).
+
+        items: a catalogue.CandidateSet built for this model's n_items, or a raw 1-D integer tensor / bool mask
+        [n_items], which builds one for this call and so costs a host sync, as recommend(candidates=) does.  Rows follow
+        the set's ascending distinct ids, returned as item_ids; an empty set returns empty outputs.  Row q holds the k
+        eligible users with the largest LOGIT for item item_ids[q], best first, ties to the smaller user id;
+        scores[q, j] is bit for bit score_items' / recommend's score of that (user, item) pair; fewer than k eligible
+        users pad with user -1 and score 0.  User u is not eligible for item i where `exclude` lists i for u (recommend's
+        three forms; "profile" reads as "has it already"), nor where user_ids[u] is negative (a row dropped without
+        reshaping the batch).  user_ids: an int32 / int64 [B] tensor of ids below 2^31 naming the rows, None = the row
+        index.  The result does not depend on scheduling, and a larger audience over many batches comes from
+        catalogue.AudienceTopK (train.audience walks a loader), whose result does not depend on the batching either.
+        1 <= k <= 128; eval mode; profile, context, the envelope and allow_composed are recommend's."""
+        if self.training:
+            raise CarcaHipError("recommend_users: the model is in training mode; recommendation scores with eval "
+                                "semantics (call model.eval() first)")
+        self._check_built()
+        return catalogue.recommend_users(self, profile, context, items, k, exclude, user_ids, allow_composed)
+
     # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists; DESIGN.md 22) ------------------
     def _check_explainable(self, what: str) -> None:
         if self.training:

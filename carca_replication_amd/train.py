@@ -192,6 +192,33 @@ def evaluate_listed(model: Model, loader: DataLoader, device: str, k: int) -> Tu
     return hr / max(users, 1.0), ndcg / max(users, 1.0)
 
 
+def audience(model: Model, loader: DataLoader, device: str, items, k: int = 10
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The k best users of the loader for each listed item (CARCA.recommend_users over every batch; DESIGN.md section
+    24): (scores [Q, k] float32, users [Q, k] int64, item_ids [Q] int64).  Walks the loader the way evaluate_full does and
+    feeds each batch's profile with the held-out context o_c[:, 0] to one catalogue.AudienceTopK; a user's id is its
+    running position in the loader, and a user is not eligible for an item of its profile.  items: a CandidateSet or a raw
+    tensor normalised once here.  The result does not depend on the loader's batch size.  One host sync at the end."""
+    from .catalogue import AudienceTopK
+
+    model = model.eval().to(device)
+    if not hasattr(model, "recommend_users"):
+        raise CarcaHipError(f"audience: {type(model).__name__} has no recommend_users (the call is CARCA's)")
+    n_items = model._catalogue_size()
+    with torch.no_grad():
+        if n_items is None:
+            n_items = model.embeds.item_table().shape[0]  # (the table the updates below score against, cached)
+        state = AudienceTopK(items, k, n_items, device=device)
+        for batch in loader:
+            p_x, p_a, p_c, _o_x, _o_a, o_c, _y = to(*engine.as_batch7(batch), device=device)
+            state.update(model, (p_x, p_a, p_c), o_c[:, 0], allow_composed=True, _what="audience")
+        out = state.result()
+    if torch.device(device).type == "cuda":
+        torch.cuda.current_stream().synchronize()
+        ops.poll_errors()
+    return out
+
+
 def evaluate_full_diverse(model: Model, loader: DataLoader, device: str, k: int, pool: int = 128, lam: float = 0.7,
                           metric: str = "cosine", candidates=None) -> dict:
     """evaluate_full's protocol over the diversity re-ranked list (model.recommend_diverse: recommend's `pool` best items

@@ -998,6 +998,44 @@ typedef struct CarcaItemGroups {
 int carca_recommend_groups(const CarcaRecommendDesc* desc, const CarcaItemGroups* groups, void* stream);
 int carca_recommend_capped(const CarcaRecommendDesc* desc, const CarcaItemGroups* groups, int max_per_group, void* stream);
 
+/* ---- the k best USERS per listed item ("which k users should hear about each of these Q items": a campaign, new
+ * arrivals, overstock) ---------------------------------------------------------------------------
+ * The descriptor is carca_recommend's own (scores / ld_scores / ids_out / ld_ids_out are not read and may be null; k is
+ * the audience size), `items` a CarcaCandidates of Q ascending, distinct ids.  CarcaAudience is the running result, one row
+ * of k 64-bit keys per listed item, best first:
+ *   key = (order-preserving bits of the raw logit) << 32 | (0xFFFFFFFF - user id); 0 = no entry.
+ * A larger key is a larger logit, and between equal logits the smaller user id; keys of a row are distinct as long as no
+ * user id is fed twice (a repeated id is the caller's error: both entries count).  Row u of the batch is user
+ * user_ids[u], or user_base + u where user_ids is null; a negative user id drops the row.  User u is not eligible for
+ * item i where the exclusion list of row u holds i (the descriptor's exclude, as carca_recommend's).
+ *
+ * carca_recommend_users: scores the B users against the Q items with carca_recommend_among's scoring and exclusion
+ * launches (stream scratch [B, Q]; the logit of a pair is bit-identical to carca_recommend's) and merges them into the
+ * state: afterwards row q holds the k largest keys of its old keys and the batch's eligible users, descending, zeros
+ * last.  The caller zeroes the state before the first call and must have the rows sorted as this call leaves them.
+ * Because the keys are distinct and totally ordered, the state after a sequence of calls depends only on the set of
+ * (user, logit) pairs fed -- not on how the users were split into calls, nor on the order of the calls.  One merge launch
+ * behind the two shared ones (a workgroup per 16 adjacent items walks the users; integer LDS atomics only), no host wait.
+ * Q = 0 is legal and launches nothing.
+ *
+ * carca_audience_read: keys [n_rows, ld_keys] -> scores [n_rows, k] = sigmoid(logit) ((logit + 1) / 2 for decoder 2) --
+ * carca_recommend's score of that (user, item), bit for bit -- and users [n_rows, k]; an empty entry gives score 0 and
+ * user -1.  Both outputs are dense.
+ *
+ * Limits and errors as carca_recommend (L up to CARCA_MAX_PROFILE_L, 1 <= k <= 128), and CARCA_ERR_UNSUPPORTED for
+ * B * Q (n_rows * k) of 2^31 or more; CARCA_ERR_BADARG for a null list / state / keys, ld_keys < k, or a user_base that
+ * lets a row id reach 2^31. */
+typedef struct CarcaAudience {
+  unsigned long long* keys; /* [Q, ld_keys], the first k of a row used */
+  int ld_keys;
+  const int32_t* user_ids;  /* [B], or NULL: row u is user user_base + u */
+  int user_base;
+} CarcaAudience;
+int carca_recommend_users(const CarcaRecommendDesc* desc, const CarcaCandidates* items, const CarcaAudience* state,
+                          void* stream);
+int carca_audience_read(const unsigned long long* keys, int ld_keys, int n_rows, int k, int decoder, float* scores,
+                        int64_t* users, void* stream);
+
 /* ---- a candidate list of its own per user (the second stage behind a retriever; the evaluation protocol's 1 + 100
  * candidates, data.py:180-185) ---------------------------------------------------------------
  * The model-side fields (B .. ffn_b), k and the exclusion list mean exactly what they mean in CarcaRecommendDesc, and the
