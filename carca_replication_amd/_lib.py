@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip"]
+           "recommend_users.hip", "recommend_contexts.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h"]
 
@@ -274,6 +274,12 @@ class Candidates(C.Structure):
     _fields_ = [("ids", _fp), ("n", C.c_int32)]
 
 
+class Contexts(C.Structure):
+    """CarcaContexts (carca_score_lists_at / carca_recommend_at / carca_recommend_among_at)."""
+    _fields_ = [("n_contexts", C.c_int32), ("user_q", _fp), ("ld_user_q", C.c_int32), ("user_off", _fp),
+                ("ld_user_off", C.c_int32), ("user_m", _fp), ("ld_user_m", C.c_int32)]
+
+
 class ItemGroups(C.Structure):
     """CarcaItemGroups (carca_recommend_groups / carca_recommend_capped)."""
     _fields_ = [("order", _fp), ("offsets", _fp), ("pos_of", _fp), ("n", C.c_int32), ("n_groups", C.c_int32)]
@@ -441,6 +447,9 @@ SIGNATURES = {
     "carca_audience_read": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _fp]),
     "carca_score_lists": (_i, [C.POINTER(ListsDesc), _fp]),
     "carca_recommend_lists": (_i, [C.POINTER(ListsDesc), _fp]),
+    "carca_score_lists_at": (_i, [C.POINTER(ListsDesc), C.POINTER(Contexts), _fp, _i, _fp]),
+    "carca_recommend_at": (_i, [C.POINTER(RecommendDesc), C.POINTER(Contexts), _fp]),
+    "carca_recommend_among_at": (_i, [C.POINTER(RecommendDesc), C.POINTER(Contexts), C.POINTER(Candidates), _fp]),
     "carca_explain_lists": (_i, [C.POINTER(ExplainDesc), _fp]),
     "carca_knn_recommend": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_knn_rank_items": (_i, [C.POINTER(KnnRankDesc), _fp]),

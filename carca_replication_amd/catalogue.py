@@ -11,7 +11,8 @@ recommend_explained say which profile slots drive a cross-attention score (DESIG
 items with a group; recommend_by_group / recommend_capped are the top-k of every group and the top-k with a cap per group
 (CARCA.recommend_by_group / recommend_capped).  AudienceTopK / recommend_users turn the question
 round: the k best users of each listed item, kept across batches (CARCA.recommend_users, train.audience; DESIGN.md
-section 24)."""
+section 24).  score_items_at / best_context / recommend_at serve several request contexts per user from one run of the
+profile side (CARCA.score_items_at / best_context / recommend_at)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -260,13 +261,65 @@ def carca_route(what: str, d: int, encoder_heads, L: int, decoder_heads: Optiona
     return "composed" if ops.use_composed(d, encoder_heads, L) else "fused"
 
 
+def _context_stages(model, M: Tensor, n_ctx: int) -> list:
+    """The row products through which a request context enters a score, as (result, operand, weight, N, K, out_ld) in
+    the order they run: M c; for a cross-attention decoder dq = (M c) W_Q^T, and w_ffn . M c where it has its residual."""
+    from .modules import CrossAttentionBlock
+
+    dec, d = model.decoder, model.embeds.d
+    ld = ops.row_ld(d)
+    stages = [("mc", "context", M, d, n_ctx, ld)]
+    if isinstance(dec, CrossAttentionBlock):
+        stages.append(("dq", "mc", dec.attn.WQ.weight.detach(), d, d, ld))  # (M c_u) W_Q^T
+        if dec.residual:
+            stages.append(("off", "mc", dec.ffn.weight.detach(), 1, d, 4))  # w_ffn . M c_u
+    return stages
+
+
+def carca_context_rows(model, M: Tensor, context: Tensor) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """One request context per user, context [B, n_ctx] -> (M c [B, ld]; dq [B, ld] or None; w_ffn . M c [B, 4] or None):
+    _context_stages, one row product each."""
+    rows = {"context": ops._f32(context)}
+    for name, src, w, N, K, out_ld in _context_stages(model, M, context.shape[-1]):
+        (rows[name],) = ops.gemm_rows([dict(a0=rows[src])], w, N, K, out_ld)
+    return rows["mc"], rows.get("dq"), rows.get("off")
+
+
+def carca_context_rows_at(model, M: Tensor, by_context: Tensor) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """C request contexts per user, by_context [C, B, n_ctx] dense -> carca_context_rows' three results stacked over the
+    contexts, [C, B, ld] each.  The row product picks its kernel by shape, so a stage is NOT one [C * B, K] product: it is
+    C products, each with the descriptor carca_context_rows builds for a [B, K] operand -- built once, its operand and
+    output pointers advanced per context -- handed to carca_gemm_rows_group, which chooses a kernel per product as
+    carca_gemm_rows does and lets those that choose the narrow kernel share launches (the same body over the same shapes:
+    the single-context call's bits, four products to a launch)."""
+    n_c = by_context.shape[0]
+    rows = {"context": by_context}
+    lib, stream = _lib.load(), ops._stream()
+    for name, src, w, N, K, out_ld in _context_stages(model, M, by_context.shape[-1]):
+        a = rows[src]
+        out = torch.empty(n_c, a.shape[1], out_ld, dtype=torch.float32, device=a.device)
+        D0, _, keep = ops._gemm_desc([dict(a0=a[0], out=out[0])], w, N, K, out_ld)
+        arr = (_lib.GemmDesc * n_c)()
+        for c in range(n_c):
+            arr[c] = D0
+            arr[c].seg[0].a0 = a.data_ptr() + 4 * c * a.stride(0)
+            arr[c].seg[0].c = out.data_ptr() + 4 * c * out.stride(0)
+        _lib.check(lib.carca_gemm_rows_group(arr, n_c, stream), "context rows")
+        rows[name] = out
+    return rows["mc"], rows.get("dq"), rows.get("off")
+
+
 def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
-                     allow_composed: bool = False) -> Tuple[list, Tensor]:
+                     allow_composed: bool = False, several=None) -> Tuple[list, Tensor]:
     """Checks the envelope of CARCA.recommend / rank_items (carca_route) and fills the model-side fields of D (RecommendDesc
     or RankDesc) -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path of
     forward (embed_segments, then the fused blocks + the final LayerNorm, or long_profile.encode where the route is
-    composed), then K, V -> u, M c, dq and w . M c.  Returns (the tensors D points into, kept alive by the caller until
-    the launch is queued; the profile ids as int32).  Call under no_grad."""
+    composed), then K, V -> u or the dot decoders' scored last slot -- everything that reads no request context -- and
+    last the rows through which the context enters a score, M c, dq and w . M c (carca_context_rows).  several: None, or
+    an empty CarcaContexts (carca_model_side_at); `context` is then [B, C, n_ctx], the context-free share runs once all the
+    same, the rows of every (user, context) pair (carca_context_rows_at) go to `several` as row u * C + c, and D's own
+    context rows stay null.  Returns (the tensors D and `several` point into, kept alive by the caller until the launch
+    is queued; the profile ids as int32).  Call under no_grad."""
     from .modules import CrossAttentionBlock, DotProduct, WeightedDotProduct
 
     p_x, p_a, p_c = profile
@@ -279,7 +332,7 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
     if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
         raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
     n_ctx = context.shape[-1] if context is not None else 0
-    if context is not None and tuple(context.shape) != (B, n_ctx):
+    if several is None and context is not None and tuple(context.shape) != (B, n_ctx):
         raise CarcaHipError(f"{what}: context must be [B, n_ctx], got {tuple(context.shape)}")
     T = emb.item_table()
     n_items = T.shape[0]
@@ -300,11 +353,8 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
             blk._check_mode()
             x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
         p_n = ops.layernorm_fwd(x.reshape(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)
-    mc = None
-    if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
-        (mc,) = ops.gemm_rows([dict(a0=ops._f32(context))], M, d, n_ctx, ld)
     p_ids = ops._ids32(p_x)
-    keep = [T, p_ids, p_n, mc]
+    keep = [T, p_ids, p_n]
     D.B, D.L, D.n_items, D.d, D.H = B, L, n_items, d, H
     D.p_ids, D.ld_p_ids = p_ids.data_ptr(), L
     if ca:
@@ -320,14 +370,6 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
         D.ffn_b = dec.ffn.bias.data_ptr()
         if dec.residual:
             D.item_w, D.ld_item_w = wt.data_ptr(), wt.stride(0)
-        if mc is not None:
-            (dq,) = ops.gemm_rows([dict(a0=mc)], a.WQ.weight.detach(), d, d, ld)  # (M c_u) W_Q^T
-            keep.append(dq)
-            D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
-            if dec.residual:
-                (off,) = ops.gemm_rows([dict(a0=mc)], dec.ffn.weight.detach(), 1, d, 4)  # w_ffn . M c_u
-                keep.append(off)
-                D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
     else:
         rows = p_n
         D.decoder = 1
@@ -340,8 +382,33 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
         last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
         D.item_q, D.ld_item_q = T.data_ptr(), T.stride(0)
         D.user_q, D.ld_user_q = last.data_ptr(), last.stride(0)
-        if mc is not None:
+    if M is not None and several is None:  # M c_u [B, d]: the context's share of every candidate's embedding
+        mc, dq, off = carca_context_rows(model, M, context)
+        keep += [mc, dq, off]
+        if ca:
+            D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
+            if off is not None:
+                D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
+        else:
             D.user_m, D.ld_user_m = mc.data_ptr(), mc.stride(0)
+    elif M is not None:
+        by_context = ops._f32(context.transpose(0, 1))  # [C, B, n_ctx]: each context a dense [B, n_ctx] operand
+        mc, dq, off = carca_context_rows_at(model, M, by_context)
+
+        def by_user(t):  # [C, B, ld] -> [B, C, ld] dense: row u * C + c, row stride ld = shape[2] (C = 1: the same memory)
+            t = t.transpose(0, 1).contiguous()
+            keep.append(t)
+            return t
+        several.n_contexts = context.shape[1]
+        if ca:
+            dq = by_user(dq)
+            several.user_q, several.ld_user_q = dq.data_ptr(), dq.shape[2]
+            if off is not None:
+                off = by_user(off)
+                several.user_off, several.ld_user_off = off.data_ptr(), off.shape[2]
+        else:
+            mc = by_user(mc)
+            several.user_m, several.ld_user_m = mc.data_ptr(), mc.shape[2]
     return keep, p_ids
 
 
@@ -511,6 +578,143 @@ def recommend_from(what: str, fill: Callable, profile, items: Tensor, k: int, ex
         D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = outs[0].data_ptr(), int(k), outs[1].data_ptr(), int(k)
         _lists_launch(what, D, keep, lst, "carca_recommend_lists")
         return outs
+
+
+# ---- several request contexts per user (include/carca_hip.h: CarcaContexts) ---------------------
+def contexts_args(what: str, single: str, profile, contexts) -> Tuple[int, int]:
+    """The checks of `contexts` that touch no device: a float [B, C, n_ctx] tensor, C >= 1 -> (C, n_ctx).  single: the
+    single-context call the messages name."""
+    if not isinstance(contexts, Tensor) or contexts.dim() != 3 or not contexts.is_floating_point():
+        raise CarcaHipError(f"{what}: contexts must be a float [B, C, n_ctx] tensor, the C request contexts of each user "
+                            f"({single} takes one [B, n_ctx] context)")
+    B = profile[0].shape[0]
+    if contexts.shape[0] != B:
+        raise CarcaHipError(f"{what}: contexts has {contexts.shape[0]} rows, the profile has B = {B} users")
+    if contexts.shape[1] < 1:
+        raise CarcaHipError(f"{what}: contexts holds C = 0 contexts per user; C must be at least 1")
+    return contexts.shape[1], contexts.shape[2]
+
+
+def carca_model_side_at(model, profile, contexts: Tensor, what: str, single: str, D,
+                        allow_composed: bool = False) -> Tuple[list, Tensor, "_lib.Contexts"]:
+    """carca_model_side for the C request contexts of each user, contexts [B, C, n_ctx] (contexts_args has checked it):
+    the share that reads no context runs ONCE, and the context rows of every (user, context) pair come back as a
+    CarcaContexts, row u * C + c (carca_model_side's `several`).  Two differences of envelope, both raised before anything
+    is launched and naming `single`, the single-context call: an embedding without a context matrix, and a cross-attention
+    decoder over more than CARCA_MAX_L slots.  Returns (the tensors kept alive, the profile ids as int32, the
+    CarcaContexts)."""
+    from .modules import CrossAttentionBlock
+
+    ops._need_cuda(*profile, contexts)
+    L = profile[0].shape[1]
+    if model.embeds.context_matrix(contexts.shape[2]) is None:
+        raise CarcaHipError(f"{what}: {type(model.embeds).__name__} has no context matrix: its scores do not depend on the "
+                            f"candidate's context, so every context gives what {single} gives (call {single})")
+    if isinstance(model.decoder, CrossAttentionBlock) and L > _lib.MAX_L:
+        raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}: the chunked scorer of "
+                            f"longer profiles is not served under several contexts (call {single} per context)")
+    X = _lib.Contexts()
+    keep, p_ids = carca_model_side(model, profile, contexts, what, D, allow_composed, several=X)
+    return keep, p_ids, X
+
+
+def _lists_at(what: str, single: str, model, profile, contexts: Tensor, items: Tensor, allow_composed: bool):
+    """_lists under several contexts: -> (D, keep, the lists as int32, the CarcaContexts)."""
+    n_c, _ = contexts_args(what, single, profile, contexts)
+    if isinstance(items, Tensor) and items.dim() == 2 and n_c * items.shape[1] >= 2 ** 31:
+        raise CarcaHipError(f"{what}: C * N = {n_c * items.shape[1]} does not fit an int")
+    box = []
+
+    def fill(what_, D, allow_composed=False):
+        keep, p_ids, X = carca_model_side_at(model, profile, contexts, what_, single, D, allow_composed)
+        box.append(X)
+        return keep, p_ids
+    D, keep, _, lst = _lists(what, fill, profile, items, allow_composed)
+    keep.append(lst)
+    D.items, D.n_list, D.ld_items = lst.data_ptr(), lst.shape[1], lst.stride(0)
+    return D, keep, lst, box[0]
+
+
+def score_items_at(what: str, model, profile, contexts: Tensor, items: Tensor, allow_composed: bool = False) -> Tensor:
+    """score_items under each of a user's C contexts (carca_score_lists_at): scores [B, C, N] float32."""
+    with torch.no_grad():
+        D, keep, lst, X = _lists_at(what, "score_items", model, profile, contexts, items, allow_composed)
+        n_c, N = X.n_contexts, lst.shape[1]
+        scores = torch.empty(D.B, n_c, N, dtype=torch.float32, device=profile[0].device)
+        D.scores, D.ld_scores = scores.data_ptr(), n_c * N
+        _lib.check(_lib.load().carca_score_lists_at(C.byref(D), C.byref(X), None, 0, ops._stream()), what)
+        return scores
+
+
+def best_context(what: str, model, profile, contexts: Tensor, items: Tensor,
+                 allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+    """Per (user, list entry) the context of the largest logit (carca_score_lists_at with best_context): (scores [B, N]
+    float32, which [B, N] int64); no [B, C, N] buffer is formed."""
+    with torch.no_grad():
+        D, keep, lst, X = _lists_at(what, "score_items", model, profile, contexts, items, allow_composed)
+        N, dev = lst.shape[1], profile[0].device
+        scores = torch.empty(D.B, N, dtype=torch.float32, device=dev)
+        which = torch.empty(D.B, N, dtype=torch.int64, device=dev)
+        D.scores, D.ld_scores = scores.data_ptr(), N
+        _lib.check(_lib.load().carca_score_lists_at(C.byref(D), C.byref(X), which.data_ptr(), N, ops._stream()), what)
+        return scores, which
+
+
+def _user_rows(D, X, lo: int, hi: int):
+    """Copies of a RecommendDesc and its CarcaContexts that cover users [lo, hi): every per-user pointer advanced by lo
+    rows of its own stride (the exclusion list and the outputs hold C rows per user)."""
+    n_c = X.n_contexts
+    Dc, Xc = type(D).from_buffer_copy(D), type(X).from_buffer_copy(X)
+    Dc.B = hi - lo
+    for S, Sc, fields in ((D, Dc, (("p_ids", 4 * D.ld_p_ids), ("user_k", 4 * D.L * D.ld_user_k),
+                                   ("user_u", 4 * D.L * D.ld_user_u), ("user_q", 4 * D.ld_user_q),
+                                   ("exclude", 4 * n_c * D.ld_exclude), ("scores", 4 * D.ld_scores),
+                                   ("ids_out", 8 * D.ld_ids_out))),
+                          (X, Xc, (("user_q", 4 * n_c * X.ld_user_q), ("user_off", 4 * n_c * X.ld_user_off),
+                                   ("user_m", 4 * n_c * X.ld_user_m)))):
+        for name, row_bytes in fields:
+            p = getattr(S, name)
+            if p:
+                setattr(Sc, name, p + lo * row_bytes)
+    return Dc, Xc
+
+
+def recommend_at(what: str, model, profile, contexts: Tensor, k: int, exclude, candidates=None,
+                 allow_composed: bool = False, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+    """recommend under each of a user's C contexts (carca_recommend_at / carca_recommend_among_at): (scores [B, C, k]
+    float32, ids [B, C, k] int64).  The users go in chunks whose [users, C, n_slots] fp32 logit scratch stays within
+    max_scratch_bytes, with no sync between them, each writing its rows of the outputs."""
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    n_c, _ = contexts_args(what, "recommend", profile, contexts)
+    k, dev = int(k), profile[0].device
+    with torch.no_grad():
+        D = _lib.RecommendDesc()
+        keep, p_ids, X = carca_model_side_at(model, profile, contexts, what, "recommend", D, allow_composed)
+        D.k = k
+        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        if D.n_exclude and n_c > 1:  # user u's row for each of its contexts: row u * C + c of the launch's B * C users
+            excl = keep[-1][:, :D.n_exclude].repeat_interleave(n_c, dim=0).contiguous()
+            keep.append(excl)
+            D.exclude, D.ld_exclude = excl.data_ptr(), excl.stride(0)
+        cand = _candidates(what, candidates, D, keep, dev)
+        n_slots = D.n_items if cand is None else cand.n
+        users = int(max_scratch_bytes) // (4 * n_c * max(n_slots, 1))
+        if users < 1:
+            raise CarcaHipError(f"{what}: one user's [C, n_slots] = [{n_c}, {n_slots}] fp32 logits need "
+                                f"{4 * n_c * max(n_slots, 1)} bytes, max_scratch_bytes is {int(max_scratch_bytes)}")
+        scores = torch.empty(D.B, n_c, k, dtype=torch.float32, device=dev)
+        ids = torch.empty(D.B, n_c, k, dtype=torch.int64, device=dev)
+        D.scores, D.ids_out, D.ld_scores, D.ld_ids_out = scores.data_ptr(), ids.data_ptr(), n_c * k, n_c * k
+        lib, stream = _lib.load(), ops._stream()
+        for lo in range(0, D.B, users):
+            Dc, Xc = _user_rows(D, X, lo, min(D.B, lo + users))
+            if cand is None:
+                rc = lib.carca_recommend_at(C.byref(Dc), C.byref(Xc), stream)
+            else:
+                rc = lib.carca_recommend_among_at(C.byref(Dc), C.byref(Xc), C.byref(cand), stream)
+            _lib.check(rc, what)
+        return scores, ids
 
 
 # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists; DESIGN.md section 22) --------------

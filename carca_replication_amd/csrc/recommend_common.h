@@ -1,9 +1,10 @@
 // Per-(user, item) logit arithmetic and the item order shared by the full-catalogue kernels: the top-k sweep of
 // recommend.hip and the list scoring / counting sweep of rank.hip (both through catalogue_sweep.h), and the per-user list
-// kernels of recommend_lists.hip and explain_lists.hip.  The calls order items
+// kernels of recommend_lists.hip, explain_lists.hip and recommend_contexts.hip.  The calls order items
 // by the same 64-bit key (order-preserving logit bits, then the complemented id), so they must produce the same logit bits
 // for the same (user, item): every kernel stages a user and scores an item through one of the scorers below
-// (CaScorer, DotScorer: the same five members; CaLongScorer, CaScorer's arithmetic over a profile staged in chunks),
+// (CaScorer, DotScorer: the same five members; CaLongScorer, CaScorer's arithmetic over a profile staged in chunks;
+// CaContextScorer, DotContextScorer: the same pieces of arithmetic under several request contexts of one user),
 // never through a copy of their arithmetic.  Desc is CarcaRecommendDesc or CarcaRankDesc (the model-side fields carry
 // the same names and meanings, include/carca_hip.h).
 #pragma once
@@ -127,13 +128,25 @@ struct GroupedItems {
 // since the previous user's LDS was last read; ends with a barrier) and logit.  `chunked` says which protocol a kernel
 // runs: false = stage_user + logit, true = CaLongScorer's chunk loop.
 
-// ---- what the two cross-attention scorers share ------------------------------------------------------------------
-// Stages n <= CARCA_MAX_L profile slots of user u, slot[0 .. n), into S (any User with Ks4 / Us / Bs): their K rows
-// head-padded, their folded values and the pre-scaled score biases.  Whole workgroup of TILE threads; n is
-// workgroup-uniform; the caller has synchronised since S was last read and has published slot[].  Two barriers: the
-// first publishes Ks / Us (beta reads Ks), the second Bs.
+// ---- what the cross-attention scorers share ----------------------------------------------------------------------
+// beta_hl = (M c W_Q^T)_h . K_hl, pre-scaled: the score bias of staged slot j (row j of Ks, head-padded) and head h under
+// the context whose row of (M c) W_Q^T is dq (null: no context term).  ca_stage_slots runs it over the descriptor's
+// row of user u, CaContextScorer over each of the user's context rows.
+template <int DHP, int H>
+__device__ __forceinline__ float ca_slot_beta(const float* dq, const float* Ks, int j, int h, int dh, float sc) {
+  float b = 0.f;
+  if (dq) {
+    const float* r = dq + h * dh;
+    for (int c = 0; c < dh; ++c) b = fmaf(r[c], Ks[j * DHP * H + h * DHP + c], b);
+  }
+  return b * sc;
+}
+
+// The context-free share of ca_stage_slots: the K rows of slot[0 .. n), head-padded, and their folded values into S (any
+// User with Ks4 / Us).  Whole workgroup of TILE threads; n is workgroup-uniform; the caller has synchronised since S was
+// last read and has published slot[].  One barrier: Ks / Us are published.
 template <int DHP, int H, class Desc, class User>
-__device__ __forceinline__ void ca_stage_slots(const Desc& D, int u, const int* slot, int n, float sc, User& S) {
+__device__ __forceinline__ void ca_stage_rows(const Desc& D, int u, const int* slot, int n, User& S) {
   constexpr int DPO = DHP * H;
   const int tid = threadIdx.x, nthr = TILE;
   const int dh = D.d / H;
@@ -147,23 +160,30 @@ __device__ __forceinline__ void ca_stage_slots(const Desc& D, int u, const int* 
     S.Us[j][h] = D.user_u[((size_t)u * D.L + slot[j]) * D.ld_user_u + h];
   }
   __syncthreads();
-  for (int idx = tid; idx < n * H; idx += nthr) {  // beta_hl = (M c_u W_Q^T)_h . K_hl, pre-scaled
+}
+
+// Stages n <= CARCA_MAX_L profile slots of user u, slot[0 .. n), into S (any User with Ks4 / Us / Bs): their K rows
+// head-padded, their folded values and the pre-scaled score biases.  Whole workgroup of TILE threads; n is
+// workgroup-uniform; the caller has synchronised since S was last read and has published slot[].  Two barriers: the
+// first publishes Ks / Us (beta reads Ks), the second Bs.
+template <int DHP, int H, class Desc, class User>
+__device__ __forceinline__ void ca_stage_slots(const Desc& D, int u, const int* slot, int n, float sc, User& S) {
+  const int tid = threadIdx.x, nthr = TILE;
+  const int dh = D.d / H;
+  ca_stage_rows<DHP, H>(D, u, slot, n, S);
+  const float* Ks = reinterpret_cast<const float*>(S.Ks4);
+  const float* dq = D.user_q ? D.user_q + (size_t)u * D.ld_user_q : nullptr;
+  for (int idx = tid; idx < n * H; idx += nthr) {
     const int j = idx / H, h = idx % H;
-    float b = 0.f;
-    if (D.user_q) {
-      const float* dq = D.user_q + (size_t)u * D.ld_user_q + h * dh;
-      for (int c = 0; c < dh; ++c) b = fmaf(dq[c], Ks[j * DPO + h * DHP + c], b);
-    }
-    S.Bs[h][j] = b * sc;
+    S.Bs[h][j] = ca_slot_beta<DHP, H>(dq, Ks, j, h, dh, sc);
   }
   __syncthreads();
 }
 
-// Staged slot j's pre-softmax score of head h, in the exp2 domain (scaled by log2(e) / sqrt(dh), the bias added).  The
-// only copy of this arithmetic: the scorers reach it through ca_slot_step, and explain_lists.hip evaluates it a second
-// time per slot to turn a head's final (m, den) into that slot's softmax weight.
+// The head dot product of a pair: QT[i]_h . K_hl over staged slot j.  It reads no context, so a scorer that serves several
+// contexts of one user (CaContextScorer) computes it once per (head, slot) and runs ca_slot_bias per context.
 template <int DHP, int H, class User>
-__device__ __forceinline__ float ca_slot_score(const float (&q)[DHP], const User& S, int h, int j, float sc) {
+__device__ __forceinline__ float ca_slot_dot(const float (&q)[DHP], const User& S, int h, int j) {
   const float4* kr = S.Ks4 + (j * DHP * H + h * DHP) / 4;
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -174,7 +194,18 @@ __device__ __forceinline__ float ca_slot_score(const float (&q)[DHP], const User
     s0 = fmaf(q[4 * c4 + 2], k4.z, s0);
     s1 = fmaf(q[4 * c4 + 3], k4.w, s1);
   }
-  return fmaf(s0 + s1, sc, S.Bs[h][j]);
+  return s0 + s1;
+}
+// the head dot product scaled into the exp2 domain, the context's pre-scaled bias (Bs) added
+__device__ __forceinline__ float ca_slot_bias(float dot, float sc, float bias) { return fmaf(dot, sc, bias); }
+
+// Staged slot j's pre-softmax score of head h, in the exp2 domain (scaled by log2(e) / sqrt(dh), the bias added): the
+// two pieces above in sequence.  The only copy of this arithmetic: the scorers reach it through ca_slot_step (or through
+// its two pieces), and explain_lists.hip evaluates it a second time per slot to turn a head's final (m, den) into that
+// slot's softmax weight.
+template <int DHP, int H, class User>
+__device__ __forceinline__ float ca_slot_score(const float (&q)[DHP], const User& S, int h, int j, float sc) {
+  return ca_slot_bias(ca_slot_dot<DHP, H>(q, S, h, j), sc, S.Bs[h][j]);
 }
 
 // staged slot j of head h, of score s, joins the head's running (m, den, num)
@@ -195,13 +226,30 @@ __device__ __forceinline__ void ca_slot_step(const float (&q)[DHP], const User& 
   ca_online_update(ca_slot_score<DHP, H>(q, S, h, j, sc), S, h, j, m, den, num);
 }
 
-// the terms of a cross-attention logit that no profile slot enters
+// the terms of a cross-attention logit that no profile slot enters; user_off: the (user, context) pair's w . M c, or null
+__device__ __forceinline__ float ca_logit_offsets(const float* user_off, const float* ffn_b, float item_off) {
+  float logit = item_off;
+  if (user_off) logit += user_off[0];
+  if (ffn_b) logit += ffn_b[0];
+  return logit;
+}
 template <class Desc>
 __device__ __forceinline__ float ca_logit_offsets(const Desc& D, int u, float item_off) {
-  float logit = item_off;
-  if (D.user_off) logit += D.user_off[(size_t)u * D.ld_user_off];
-  if (D.ffn_b) logit += D.ffn_b[0];
-  return logit;
+  return ca_logit_offsets(D.user_off ? D.user_off + (size_t)u * D.ld_user_off : nullptr, D.ffn_b, item_off);
+}
+
+// Compacts the valid slots of user u's profile of D.L <= CARCA_MAX_L positions into S.slot / S.nvalid (leading pad slots
+// and any interior id 0 are skipped).  Whole workgroup; one barrier: slot[] and nvalid are published.
+template <class Desc, class User>
+__device__ __forceinline__ void ca_compact_slots(const Desc& D, int u, User& S) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const bool v = tid < D.L && D.p_ids[(size_t)u * D.ld_p_ids + tid] != 0;
+    const unsigned long long m = __ballot(v);
+    if (v) S.slot[__popcll(m & ((1ull << tid) - 1ull))] = tid;
+    if (tid == 0) S.nvalid = __popcll(m);
+  }
+  __syncthreads();
 }
 
 // cross-attention decoder, profiles of up to CARCA_MAX_L slots: the whole user in LDS
@@ -243,14 +291,7 @@ struct CaScorer {
 
   template <class Desc>
   __device__ __forceinline__ void stage_user(const Desc& D, int u, User& S) {
-    const int tid = threadIdx.x;
-    if (tid < 64) {  // compact the valid slots (leading pad slots and any interior id 0 are skipped)
-      const bool v = tid < D.L && D.p_ids[(size_t)u * D.ld_p_ids + tid] != 0;
-      const unsigned long long m = __ballot(v);
-      if (v) S.slot[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-      if (tid == 0) S.nvalid = __popcll(m);
-    }
-    __syncthreads();
+    ca_compact_slots(D, u, S);
     nv = S.nvalid;
     ca_stage_slots<DHP, H>(D, u, S.slot, nv, sc, S);
   }
@@ -390,6 +431,160 @@ struct CaLongScorer {
   }
 };
 
+// Cross-attention decoder under several request contexts of one user (recommend_contexts.hip), profiles of up to
+// CARCA_MAX_L slots.  K, u and the slot list do not depend on the context and are staged once (stage_user); the score
+// biases of up to NC contexts at a time -- rows u * n_contexts + c0 .. of X.user_q, X a CarcaContexts -- go to
+// Bs4[h][j][c], each through ca_slot_beta as ca_stage_slots computes CaScorer's Bs from the descriptor's row
+// (stage_contexts).  logits walks (head, slot) once: ca_slot_dot once per pair, then per context ca_slot_bias and
+// ca_online_update on that context's (m, den, num), and adds the heads to ca_logit_offsets' sum in CaScorer::logit's
+// order -- per context the sequence of operations CaScorer::logit runs under that context, so the same logit bits.
+// A kernel runs: stage_user; for each pass of NC contexts { if (pass) __syncthreads(); stage_contexts; logits }.
+template <int DHP, int H, int NC_>
+struct CaContextScorer {
+  static constexpr int NC = NC_, HEADS = H, HEAD_PAD = DHP;
+  static_assert(NC % 4 == 0 && (NC & (NC - 1)) == 0, "a slot's biases are read as float4; heads_upto halves NC");
+  using Short = CaScorer<DHP, H>;
+  using Item = typename Short::Item;
+  struct User {
+    float4 Ks4[CARCA_MAX_L * DHP * H / 4];  // compacted valid profile slots, head-padded
+    float Us[CARCA_MAX_L][H];
+    float4 Bs4[H][CARCA_MAX_L][NC / 4];  // the staged contexts' pre-scaled score biases
+    int slot[CARCA_MAX_L];
+    int nvalid;
+  };
+  Short base;
+  int nv;  // valid profile slots of the staged user
+
+  template <class Desc>
+  __device__ __forceinline__ explicit CaContextScorer(const Desc& D) : base(D), nv(0) {}
+
+  template <class Desc>
+  __device__ __forceinline__ void load_item(const Desc& D, int item, bool live, Item& I) const {
+    base.load_item(D, item, live, I);
+  }
+
+  // Two barriers: ca_compact_slots' (the slot list), ca_stage_rows' (Ks / Us).  nv is workgroup-uniform (an LDS word
+  // every thread reads after the first).
+  template <class Desc>
+  __device__ __forceinline__ void stage_user(const Desc& D, int u, User& S) {
+    ca_compact_slots(D, u, S);
+    nv = S.nvalid;
+    ca_stage_rows<DHP, H>(D, u, S.slot, nv, S);
+  }
+
+  // The biases of contexts c0 .. c0 + ncx of user u (ncx <= NC, workgroup-uniform).  The caller has synchronised since
+  // Bs4 was last read; one barrier: Bs4 is published.
+  template <class Desc, class Ctx>
+  __device__ __forceinline__ void stage_contexts(const Desc& D, const Ctx& X, int u, int c0, int ncx, User& S) const {
+    const int dh = D.d / H;
+    const float* Ks = reinterpret_cast<const float*>(S.Ks4);
+    float* Bs = reinterpret_cast<float*>(S.Bs4);
+    for (int idx = threadIdx.x; idx < ncx * nv * H; idx += TILE) {
+      const int c = idx / (nv * H), r = idx % (nv * H), j = r / H, h = r % H;
+      const float* dq = X.user_q ? X.user_q + ((size_t)u * X.n_contexts + c0 + c) * X.ld_user_q : nullptr;
+      Bs[(h * CARCA_MAX_L + j) * NC + c] = ca_slot_beta<DHP, H>(dq, Ks, j, h, dh, base.sc);
+    }
+    __syncthreads();
+  }
+
+  // y[c], c < ncx: the logit of (user u under context c0 + c, item I); y[c] means nothing for c >= ncx
+  template <class Desc, class Ctx>
+  __device__ __forceinline__ void logits(const Desc& D, const Ctx& X, int u, int c0, int ncx, const Item& I, const User& S,
+                                         float (&y)[NC]) const {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      y[c] = 0.f;
+      if (c < ncx)
+        y[c] = ca_logit_offsets(X.user_off ? X.user_off + ((size_t)u * X.n_contexts + c0 + c) * X.ld_user_off : nullptr,
+                                D.ffn_b, I.off);
+    }
+    if (nv > 0) heads_upto<NC>(ncx, I, S, y);  // (a fully masked profile: attention term 0, carca.py:256)
+  }
+
+ private:
+  // The heads' attention terms of the first N staged contexts, added to y[0 .. N): N is a compile-time count, so the
+  // slot loop carries no test per context.  Called with N >= ncx: a context past ncx runs over whatever Bs4 holds for
+  // it and lands in a y the caller never reads.
+  template <int N>
+  __device__ __forceinline__ void heads(const Item& I, const User& S, float (&y)[NC]) const {
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      float m[N], den[N], num[N];
+#pragma unroll
+      for (int c = 0; c < N; ++c) m[c] = -INFINITY, den[c] = 0.f, num[c] = 0.f;
+      for (int j = 0; j < nv; ++j) {
+        const float dot = ca_slot_dot<DHP, H>(I.q[h], S, h, j);
+        float bias[N];
+        if constexpr (N % 4 == 0) {
+#pragma unroll
+          for (int c4 = 0; c4 < N / 4; ++c4) {
+            const float4 b4 = S.Bs4[h][j][c4];
+            bias[4 * c4] = b4.x, bias[4 * c4 + 1] = b4.y, bias[4 * c4 + 2] = b4.z, bias[4 * c4 + 3] = b4.w;
+          }
+        } else {
+          const float* b = reinterpret_cast<const float*>(S.Bs4[h][j]);
+#pragma unroll
+          for (int c = 0; c < N; ++c) bias[c] = b[c];
+        }
+#pragma unroll
+        for (int c = 0; c < N; ++c) ca_online_update(ca_slot_bias(dot, base.sc, bias[c]), S, h, j, m[c], den[c], num[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < N; ++c) y[c] += num[c] / den[c];
+    }
+  }
+  // heads<N'> for the smallest N' = NC, NC / 2, ..., 1 that holds ncx contexts (ncx is workgroup-uniform)
+  template <int N>
+  __device__ __forceinline__ void heads_upto(int ncx, const Item& I, const User& S, float (&y)[NC]) const {
+    if constexpr (N > 1) {
+      if (2 * ncx <= N) {
+        heads_upto<N / 2>(ncx, I, S, y);
+        return;
+      }
+    }
+    heads<N>(I, S, y);
+  }
+};
+
+// ---- what the dot scorers share --------------------------------------------------------------------------------------
+// t . r over a staged row (As4 or Ms4), as two interleaved chains
+template <int DPI>
+__device__ __forceinline__ float dot_row(const float (&t)[DPI], const float4* r4) {
+  float d0 = 0.f, d1 = 0.f;
+#pragma unroll
+  for (int c4 = 0; c4 < DPI / 4; ++c4) {
+    const float4 a4 = r4[c4];
+    d0 = fmaf(t[4 * c4], a4.x, d0);
+    d1 = fmaf(t[4 * c4 + 1], a4.y, d1);
+    d0 = fmaf(t[4 * c4 + 2], a4.z, d0);
+    d1 = fmaf(t[4 * c4 + 3], a4.w, d1);
+  }
+  return d0 + d1;
+}
+// a dot logit from its sums: ta = t . a, tm = t . m (0 without a context term), tn = t . t, am = a . m, mm = m . m
+__device__ __forceinline__ float dot_finish(float ta, float tm, float tn, float am, float mm, bool norm) {
+  float y = ta + am;
+  if (norm) {
+    const float n2 = fmaxf(tn + 2.f * tm + mm, 0.f);
+    y = y / fmaxf(sqrtf(n2), 1e-12f);  // F.normalize(o): o / max(||o||, eps) (carca.py:388-389)
+  }
+  return y;
+}
+// a . m and m . m of a scored row a and a context row m (null: zeros) into am_mm[0 .. 2): one whole wave
+__device__ __forceinline__ void dot_stage_am(const float* a_row, const float* m_row, int d, float* am_mm) {
+  const int lane = threadIdx.x & 63;
+  float a0 = 0.f, m0 = 0.f;
+  for (int c = lane; c < d; c += 64) {
+    const float a = a_row[c];
+    const float mv = m_row ? m_row[c] : 0.f;
+    a0 = fmaf(a, mv, a0);
+    m0 = fmaf(mv, mv, m0);
+  }
+  a0 = wave_sum(a0);
+  m0 = wave_sum(m0);
+  if (lane == 0) am_mm[0] = a0, am_mm[1] = m0;
+}
+
 // dot decoders
 template <int DPI>
 struct DotScorer {
@@ -426,49 +621,79 @@ struct DotScorer {
       As[tid] = tid < D.d ? D.user_q[(size_t)u * D.ld_user_q + tid] : 0.f;
       Ms[tid] = (has_m && tid < D.d) ? D.user_m[(size_t)u * D.ld_user_m + tid] : 0.f;
     }
-    if (tid < 64) {  // a_u . m_u and m_u . m_u, once per user
-      float a0 = 0.f, m0 = 0.f;
-      for (int c = tid; c < D.d; c += 64) {
-        const float a = D.user_q[(size_t)u * D.ld_user_q + c];
-        const float mv = has_m ? D.user_m[(size_t)u * D.ld_user_m + c] : 0.f;
-        a0 = fmaf(a, mv, a0);
-        m0 = fmaf(mv, mv, m0);
-      }
-      a0 = wave_sum(a0);
-      m0 = wave_sum(m0);
-      if (tid == 0) S.am_mm[0] = a0, S.am_mm[1] = m0;
-    }
+    if (tid < 64)  // a_u . m_u and m_u . m_u, once per user
+      dot_stage_am(D.user_q + (size_t)u * D.ld_user_q, has_m ? D.user_m + (size_t)u * D.ld_user_m : nullptr, D.d, S.am_mm);
     __syncthreads();
   }
 
   template <class Desc>
   __device__ __forceinline__ float logit(const Desc& D, int, const Item& I, const User& S) const {
     const bool norm = D.decoder == 2, has_m = D.user_m != nullptr;
-    float dot0 = 0.f, dot1 = 0.f, tm0 = 0.f, tm1 = 0.f;
-#pragma unroll
-    for (int c4 = 0; c4 < DPI / 4; ++c4) {
-      const float4 a4 = S.As4[c4];
-      dot0 = fmaf(I.t[4 * c4], a4.x, dot0);
-      dot1 = fmaf(I.t[4 * c4 + 1], a4.y, dot1);
-      dot0 = fmaf(I.t[4 * c4 + 2], a4.z, dot0);
-      dot1 = fmaf(I.t[4 * c4 + 3], a4.w, dot1);
+    const float ta = dot_row<DPI>(I.t, S.As4);
+    const float tm = (norm && has_m) ? dot_row<DPI>(I.t, S.Ms4) : 0.f;
+    return dot_finish(ta, tm, I.tn, S.am_mm[0], S.am_mm[1], norm);
+  }
+};
+
+// Dot decoders under several request contexts of one user (recommend_contexts.hip): the scored row a_u is staged once
+// (stage_user), the rows m_c = M c of up to NC contexts at a time with their a . m and m . m (stage_contexts: rows
+// u * n_contexts + c0 .. of X.user_m, X a CarcaContexts).  logits computes t . a once per item and per context t . m_c
+// (normalised decoder) and dot_finish -- DotScorer::logit's pieces, so its bits under that context.  The kernels'
+// protocol is CaContextScorer's.
+template <int DPI, int NC_>
+struct DotContextScorer {
+  static constexpr int NC = NC_;
+  using Short = DotScorer<DPI>;
+  using Item = typename Short::Item;
+  struct User {
+    float4 As4[DPI / 4], Ms4[NC][DPI / 4];
+    float am_mm[NC][2];
+  };
+  Short base;
+
+  template <class Desc>
+  __device__ __forceinline__ explicit DotContextScorer(const Desc& D) : base(D) {}
+
+  template <class Desc>
+  __device__ __forceinline__ void load_item(const Desc& D, int item, bool live, Item& I) const {
+    base.load_item(D, item, live, I);
+  }
+
+  // one barrier: As4 is published
+  template <class Desc>
+  __device__ __forceinline__ void stage_user(const Desc& D, int u, User& S) {
+    const int tid = threadIdx.x;
+    float* As = reinterpret_cast<float*>(S.As4);
+    if (tid < DPI) As[tid] = tid < D.d ? D.user_q[(size_t)u * D.ld_user_q + tid] : 0.f;
+    __syncthreads();
+  }
+
+  // Contexts c0 .. c0 + ncx of user u (ncx <= NC, workgroup-uniform): wave w stages contexts w, w + TILE / 64, ... (a
+  // wave-uniform trip count, no barrier inside).  The caller has synchronised since Ms4 / am_mm were last read; one
+  // barrier: they are published.
+  template <class Desc, class Ctx>
+  __device__ __forceinline__ void stage_contexts(const Desc& D, const Ctx& X, int u, int c0, int ncx, User& S) const {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int c = w; c < ncx; c += TILE / 64) {
+      const float* m_row = X.user_m ? X.user_m + ((size_t)u * X.n_contexts + c0 + c) * X.ld_user_m : nullptr;
+      float* Ms = reinterpret_cast<float*>(S.Ms4[c]);
+      for (int i = lane; i < DPI; i += 64) Ms[i] = (m_row && i < D.d) ? m_row[i] : 0.f;
+      dot_stage_am(D.user_q + (size_t)u * D.ld_user_q, m_row, D.d, S.am_mm[c]);
     }
-    float y = dot0 + dot1 + S.am_mm[0];
-    if (norm) {
-      if (has_m) {
+    __syncthreads();
+  }
+
+  template <class Desc, class Ctx>
+  __device__ __forceinline__ void logits(const Desc& D, const Ctx& X, int, int, int ncx, const Item& I, const User& S,
+                                         float (&y)[NC]) const {
+    const bool norm = D.decoder == 2, has_m = X.user_m != nullptr;
+    const float ta = dot_row<DPI>(I.t, S.As4);
 #pragma unroll
-        for (int c4 = 0; c4 < DPI / 4; ++c4) {
-          const float4 m4 = S.Ms4[c4];
-          tm0 = fmaf(I.t[4 * c4], m4.x, tm0);
-          tm1 = fmaf(I.t[4 * c4 + 1], m4.y, tm1);
-          tm0 = fmaf(I.t[4 * c4 + 2], m4.z, tm0);
-          tm1 = fmaf(I.t[4 * c4 + 3], m4.w, tm1);
-        }
+    for (int c = 0; c < NC; ++c)
+      if (c < ncx) {
+        const float tm = (norm && has_m) ? dot_row<DPI>(I.t, S.Ms4[c]) : 0.f;
+        y[c] = dot_finish(ta, tm, I.tn, S.am_mm[c][0], S.am_mm[c][1], norm);
       }
-      const float n2 = fmaxf(I.tn + 2.f * (tm0 + tm1) + S.am_mm[1], 0.f);
-      y = y / fmaxf(sqrtf(n2), 1e-12f);  // F.normalize(o): o / max(||o||, eps) (carca.py:388-389)
-    }
-    return y;
   }
 };
 

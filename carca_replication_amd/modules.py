@@ -1426,6 +1426,56 @@ class CARCA(_PackedModule, Model):
         return catalogue.recommend_from("recommend_from", partial(catalogue.carca_model_side, self, profile, context),
                                         profile, items, k, exclude, allow_composed)
 
+    # ---- several request contexts per user (include/carca_hip.h: CarcaContexts) -------------------------
+    def _check_contexts_call(self, what: str) -> None:
+        if self.training:
+            raise CarcaHipError(f"{what}: the model is in training mode; the scores under a request context use eval "
+                                "semantics (call model.eval() first)")
+        self._check_built()
+
+    def score_items_at(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, items: Tensor,
+                       allow_composed: bool = False) -> Tensor:
+        """score_items under C request contexts per user in one call: [B, C, N] float32.
+
+        contexts: a float [B, C, n_ctx] tensor, C >= 1 -- "tonight, tomorrow morning, at the weekend"; C is not capped.
+        Slice [:, c] is score_items(profile, contexts[:, c], items), bit for bit.  The profile side (embedding, encoder
+        blocks, final norm, K, V -> u) runs once, each (head, slot, item) dot product is computed once, and a further
+        context costs its own three small row products and a bias, two exp2 and two FMAs per (slot, head) (DESIGN.md
+        section 25).  items, the treatment of ids that are no items and allow_composed are score_items'.  The envelope
+        is recommend's with two differences: an embedding without a context matrix (AttrEmbedding, IdEmbedding,
+        MLPIdEmbedding: the score does not depend on the candidate's context) raises -- call score_items -- and so does
+        a cross-attention decoder over a profile of more than 64 slots -- call score_items per context."""
+        self._check_contexts_call("score_items_at")
+        return catalogue.score_items_at("score_items_at", self, profile, contexts, items, allow_composed)
+
+    def best_context(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, items: Tensor,
+                     allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+        """At which of a user's C contexts each listed item scores best: (scores [B, N] float32, which [B, N] int64).
+
+        Per (user, list entry) the largest LOGIT over the C contexts of score_items_at; a tie goes to the smaller context
+        index.  scores is that logit through the model's link, with score_items_at's bits (= its maximum over dim 1);
+        which is its context index.  An id that is no item gives score 0 and index -1.  One launch; no [B, C, N] buffer
+        is formed.  Arguments and envelope: score_items_at's."""
+        self._check_contexts_call("best_context")
+        return catalogue.best_context("best_context", self, profile, contexts, items, allow_composed)
+
+    def recommend_at(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, k: int = 10,
+                     exclude="profile", candidates=None, allow_composed: bool = False,
+                     max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+        """recommend under C request contexts per user in one call: (scores [B, C, k] float32, ids [B, C, k] int64).
+
+        contexts: as score_items_at's.  Slices [:, c] of both outputs are recommend(profile, contexts[:, c], k, exclude,
+        candidates), bit for bit: order, ties to the smaller id, padding with id 0 and score 0; user u's exclusion
+        applies to all its contexts.  The profile side runs once and the catalogue is swept once, the head dot products
+        shared by the contexts; exclusion and selection then run per (user, context).  The raw logits are
+        [users, C, n_slots] floats of stream scratch (n_slots = n_items, or the candidate count): the users go in chunks
+        that keep it within max_scratch_bytes, with no host sync, and the result does not depend on the chunking; a
+        budget that does not hold one user's [C, n_slots] raises.  k, exclude, candidates and allow_composed are
+        recommend's; the envelope is score_items_at's."""
+        self._check_contexts_call("recommend_at")
+        return catalogue.recommend_at("recommend_at", self, profile, contexts, k, exclude, candidates, allow_composed,
+                                      max_scratch_bytes)
+
     # ---- item groups (include/carca_hip.h: carca_recommend_groups / carca_recommend_capped; DESIGN.md 23) -------------
     def _catalogue_size(self) -> Optional[int]:
         """n_items where no launch is needed to know it: the id table's rows, else the registered attribute table's."""

@@ -1091,6 +1091,54 @@ typedef struct CarcaListsDesc {
 int carca_score_lists(const CarcaListsDesc* desc, void* stream);
 int carca_recommend_lists(const CarcaListsDesc* desc, void* stream);
 
+/* ---- several request contexts per user ("tonight, tomorrow morning, at the weekend"; "at which of these send times
+ * does item i score best for user u") -----------------------------------------------------------
+ * The candidate's context (data.py:180-185: every candidate of a user carries the request's context) enters a logit only
+ * through the rows M c: for decoder 0 through user_q = (M c) W_Q^T (the score bias beta_hl = user_q_h . K_hl) and
+ * user_off = w_ffn . M c (carca.py:338-347 over e = T[i] + M c), for decoders 1 and 2 through user_m = M c
+ * (carca.py:361-367, 385-399).  K, u, the scored profile row and the head dot products item_q[i]_h . K_hl do not depend
+ * on it.  CarcaContexts carries those rows for n_contexts = C >= 1 contexts per user: row u * C + c belongs to (user u,
+ * context c).  The entry points below take an existing descriptor plus this struct; the descriptor's own user_q (decoder
+ * 0), user_off and user_m are then NOT read (decoder 1 / 2: the descriptor's user_q is the scored profile row, as
+ * always).  A null row pointer means "no context term", as in the descriptor.  The profile is staged once per
+ * workgroup, the head dot product of a (head, slot, item) is computed once, and the contexts are served eight at a time
+ * (fewer where a geometry's registers ask for it); C is not capped.  The logit of (user u under context c, item i) is
+ * bit-identical to the one carca_recommend / carca_score_lists compute from a descriptor that holds row u * C + c as
+ * user u's row.  Decoder 0 needs L <= CARCA_MAX_L here (the chunked protocol of longer profiles is not served under
+ * several contexts).  No float atomics: bit-identical run to run.
+ *
+ * carca_score_lists_at: carca_score_lists under each context.  best_context == NULL: scores[u][c * n_list + j] is
+ * carca_score_lists' scores[u][j] under context c (ld_scores >= C * n_list).  best_context != NULL ([B, ld_best_context]
+ * int64): no [B, C, n_list] result is formed; scores[u][j] (ld_scores >= n_list) is the link of the largest LOGIT of
+ * entry j over the C contexts and best_context[u][j] its context, a tie going to the smaller context index; an id that is
+ * no item gives score 0 and context -1.  One launch, no scratch.
+ *
+ * carca_recommend_at / carca_recommend_among_at: carca_recommend / carca_recommend_among under each context:
+ * scores[u][c * k + r] and ids_out[u][c * k + r], r < k, are row u of the single-context call under context c.  The two
+ * outputs are dense: ld_scores == ld_ids_out == C * k.  desc->exclude has B * C rows, row u * C + c for (user u, context
+ * c): the caller repeats a user's row for each of its contexts.  The sweep writes raw logits [B * C, n] (n = n_items or
+ * the candidate count) to stream scratch, or the capture's memory; then carca_recommend's exclusion and selection
+ * launches run over the B * C rows.  Three launches, no host wait.
+ *
+ * CARCA_ERR_UNSUPPORTED as the single-context calls, and decoder 0 with L > CARCA_MAX_L, or B * C (C * n_list, C * k) of
+ * 2^31 or more.  CARCA_ERR_BADARG as the single-context calls, and a null CarcaContexts, n_contexts < 1, a context row
+ * stride shorter than its row or (user_q, user_m) not a multiple of 4, ld_scores / ld_best_context shorter than their
+ * rows, or (recommend) output strides other than C * k. */
+typedef struct CarcaContexts {
+  int n_contexts;        /* C >= 1 */
+  const float* user_q;   /* [B * C, ld_user_q] (M c) W_Q^T, read by decoder 0, or NULL */
+  int ld_user_q;
+  const float* user_off; /* [B * C] with stride ld_user_off: w_ffn . M c, read by decoder 0, or NULL */
+  int ld_user_off;
+  const float* user_m;   /* [B * C, ld_user_m] M c, read by decoders 1 and 2, or NULL */
+  int ld_user_m;
+} CarcaContexts;
+int carca_score_lists_at(const CarcaListsDesc* desc, const CarcaContexts* contexts, int64_t* best_context,
+                         int ld_best_context, void* stream);
+int carca_recommend_at(const CarcaRecommendDesc* desc, const CarcaContexts* contexts, void* stream);
+int carca_recommend_among_at(const CarcaRecommendDesc* desc, const CarcaContexts* contexts,
+                             const CarcaCandidates* candidates, void* stream);
+
 /* ---- which profile slots drive a cross-attention score (the decoder's attention, MultiHeadAttention.forward's
  * return_w, carca.py:253-263, under CrossAttentionBlock.forward's eval path, carca.py:338-347) ---
  * The model-side fields (B .. ffn_b) and the list (items / n_list / ld_items) mean exactly what they mean in
