@@ -1,10 +1,10 @@
 """Host side of the full-catalogue top-k and rank calls (CARCA.recommend / rank_items, KNN.recommend / rank_items;
-DESIGN.md sections 10-12).  A call fills the model side of a descriptor (carca_model_side or knn_model_side: what scores
-a (user, item) pair), then does what the four share -- the k / items checks, the exclusion list, the outputs and the
-launch (recommend, rank_items).  A model's two descriptors name their model-side and exclusion fields alike
-(include/carca_hip.h), so one function fills both.  CandidateSet is the item set the CARCA calls can be restricted to
-(DESIGN.md section 15).  similar_items is the item-to-item top-k over a row table (CARCA.similar_items, KNN.similar_items,
-ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
+DESIGN.md sections 10-12).  A call checks its arguments, builds the model side (carca_model_side or knn_model_side: a
+ModelSide, what scores a (user, item) pair), asks it for a descriptor (ModelSide.desc) and does what the calls share --
+the exclusion list, the outputs and the launch (recommend, rank_items).  A model's descriptors name their model-side
+fields alike (include/carca_hip.h), so one side fills any of them.  CandidateSet is the item set the CARCA calls can be
+restricted to.  similar_items is the item-to-item top-k over a row table (CARCA.similar_items,
+KNN.similar_items, ops.similar_rows).  mmr_rerank is the diversity re-rank of a top-k pool over such a table
 (recommend_diverse, ops.mmr_rerank).  score_items / recommend_from serve a candidate list of its
 own per user (CARCA.score_items / recommend_from).  explain_items / explain_top_slots /
 recommend_explained say which profile slots drive a cross-attention score.  ItemGroups labels
@@ -16,7 +16,8 @@ profile side (CARCA.score_items_at / best_context / recommend_at; DESIGN.md sect
 from __future__ import annotations
 
 import ctypes as C
-from functools import partial
+import math
+from types import SimpleNamespace
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -26,6 +27,12 @@ from . import _lib, ops
 from ._lib import CarcaHipError
 
 KMAX = 128  # largest k of recommend and largest list of rank_items (csrc: rc::RC_KMAX, rc::LIST_MAX)
+
+
+def _check_k(what: str, k: int) -> int:
+    if not 1 <= int(k) <= KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    return int(k)
 
 
 class CandidateSet:
@@ -182,56 +189,44 @@ def _groups(what: str, groups: ItemGroups, D, keep: list, device):
 
 def grouped_args(what: str, groups, k: int, max_per_group: int = 1, n_items: Optional[int] = None) -> None:
     """The argument checks of recommend_by_group / recommend_capped that need no launch."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    _check_k(what, k)
     if int(max_per_group) < 1:
         raise CarcaHipError(f"{what}: max_per_group = {max_per_group} must be positive")
     check_groups(what, groups, n_items)
 
 
-def recommend_by_group(what: str, fill: Callable, profile, groups: ItemGroups, k: int, exclude,
-                       allow_composed: bool = False, n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+def recommend_by_group(what: str, model_side: Callable, profile, groups: ItemGroups, k: int, exclude,
+                       n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """The k best items of every group per user (carca_recommend_groups): (scores [B, G, k] float32, ids [B, G, k] int64).
-    n_items: the model's catalogue size where the caller knows it without a launch (checked before the model side runs)."""
+    model_side() -> the ModelSide; n_items: the model's catalogue size where the caller knows it without a launch (checked
+    before the model side runs)."""
     grouped_args(what, groups, k, 1, n_items)
     with torch.no_grad():
-        D = _lib.RecommendDesc()
-        keep, p_ids = _fill(fill, what, D, allow_composed)
-        D.k = k = int(k)
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        D, keep = _topk_desc(what, model_side(), k, exclude)
         device = profile[0].device
         gr = _groups(what, groups, D, keep, device)
-        G = groups.n_groups
-        scores = torch.empty(D.B, G, k, dtype=torch.float32, device=device)
-        ids = torch.empty(D.B, G, k, dtype=torch.int64, device=device)
-        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), G * k, ids.data_ptr(), G * k
+        outs = _outputs(D, "ids_out", (D.B, groups.n_groups, D.k), device)
         _lib.check(_lib.load().carca_recommend_groups(C.byref(D), C.byref(gr), ops._stream()), what)
-        return scores, ids
+        return outs
 
 
-def recommend_capped(what: str, fill: Callable, profile, groups: ItemGroups, k: int, max_per_group: int, exclude,
-                     allow_composed: bool = False, n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+def recommend_capped(what: str, model_side: Callable, profile, groups: ItemGroups, k: int, max_per_group: int, exclude,
+                     n_items: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """The k best grouped items per user with at most max_per_group of any one group (carca_recommend_capped):
     (scores [B, k] float32, ids [B, k] int64)."""
     grouped_args(what, groups, k, max_per_group, n_items)
-    k = int(k)
-    m = min(k, int(max_per_group))
+    m = min(int(k), int(max_per_group))
     B = profile[0].shape[0]
     if B * groups.n_groups * m * 8 > CAPPED_SCRATCH_MAX:
         raise CarcaHipError(f"{what}: B = {B} users x G = {groups.n_groups} groups x m = {m} per group: the key scratch "
                             f"of {B * groups.n_groups * m * 8} bytes exceeds {CAPPED_SCRATCH_MAX} (split the batch)")
     with torch.no_grad():
-        D = _lib.RecommendDesc()
-        keep, p_ids = _fill(fill, what, D, allow_composed)
-        D.k = k
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        D, keep = _topk_desc(what, model_side(), k, exclude)
         device = profile[0].device
         gr = _groups(what, groups, D, keep, device)
-        scores = torch.empty(D.B, k, dtype=torch.float32, device=device)
-        ids = torch.empty(D.B, k, dtype=torch.int64, device=device)
-        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = scores.data_ptr(), k, ids.data_ptr(), k
+        outs = _outputs(D, "ids_out", (D.B, D.k), device)
         _lib.check(_lib.load().carca_recommend_capped(C.byref(D), C.byref(gr), m, ops._stream()), what)
-        return scores, ids
+        return outs
 
 
 def carca_route(what: str, d: int, encoder_heads, L: int, decoder_heads: Optional[int], allow_composed: bool) -> str:
@@ -309,31 +304,51 @@ def carca_context_rows_at(model, M: Tensor, by_context: Tensor) -> Tuple[Tensor,
     return rows["mc"], rows.get("dq"), rows.get("off")
 
 
-def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
-                     allow_composed: bool = False, several=None) -> Tuple[list, Tensor]:
-    """Checks the envelope of CARCA.recommend / rank_items (carca_route) and fills the model-side fields of D (RecommendDesc
-    or RankDesc) -- the item-side tables from their per-weight-version caches, and the profile side: the encoder path of
-    forward (embed_segments, then the fused blocks + the final LayerNorm, or long_profile.encode where the route is
-    composed), then K, V -> u or the dot decoders' scored last slot -- everything that reads no request context -- and
-    last the rows through which the context enters a score, M c, dq and w . M c (carca_context_rows).  several: None, or
-    an empty CarcaContexts (carca_model_side_at); `context` is then [B, C, n_ctx], the context-free share runs once all the
-    same, the rows of every (user, context) pair (carca_context_rows_at) go to `several` as row u * C + c, and D's own
-    context rows stay null.  Returns (the tensors D and `several` point into, kept alive by the caller until the launch
-    is queued; the profile ids as int32).  Call under no_grad."""
+class ModelSide(SimpleNamespace):
+    """What scores a (user, item) pair, as a value: the result of carca_model_side, carca_model_side_at and
+    knn_model_side, built from keywords.  `fields`: the model-side fields of the model's descriptors that are set, by
+    their header names (CARCA: B, L, n_items, d, H, decoder, the pointers and their ld_; KNN: B, L, n_items, F and the
+    _KNN_MODEL names).  `p_ids`: the profile ids as int32.  `contexts`: the filled CarcaContexts of the _at form, else
+    None.  Every other attribute is a tensor the pointers point into, by name -- CARCA: T, p_n, then qt, wt, kk, uu
+    (cross-attention) or rows (the dot decoders' scored rows), and mc, dq, off where a context enters; KNN: table, and q
+    or table_i8.  The side owns them: holding it keeps them alive, and a caller holds it until its launch is queued.  No
+    call writes into a side, so one side fills any number of descriptors."""
+    contexts = None
+
+    def desc(self, cls):
+        """A zeroed descriptor of class cls with the model-side fields set.  A class that lacks one of them raises: a
+        KNN side does not go into a CARCA descriptor."""
+        D = cls(**self.fields)
+        if vars(D):  # (ctypes keeps a keyword that names no field as a plain attribute of the instance)
+            raise CarcaHipError(f"{cls.__name__} has no field {sorted(vars(D))[0]}: this model side does not fit it")
+        return D
+
+
+def _carca_envelope(model, profile, what: str, allow_composed: bool) -> str:
+    """The envelope of the CARCA calls (carca_route, a covered decoder) -> the route.  No tensor is touched."""
     from .modules import CrossAttentionBlock, DotProduct, WeightedDotProduct
 
+    dec = model.decoder
+    ca = isinstance(dec, CrossAttentionBlock)
+    route = carca_route(what, model.embeds.d, [b.attn.H for b in model.encoder], profile[0].shape[1],
+                        dec.attn.H if ca else None, allow_composed)
+    if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
+        raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
+    return route
+
+
+def _carca_context_free(model, profile, n_ctx: int, route: str) -> Tuple[ModelSide, Optional[Tensor]]:
+    """Everything of a CARCA model side that reads no request context: the item-side tables from their
+    per-weight-version caches, and the profile side -- the encoder path of forward (embed_segments, then the fused blocks +
+    the final LayerNorm, or long_profile.encode where the route is composed), then K, V -> u or the dot decoders' scored
+    last slot.  -> (the side, its context rows still null; the context matrix M, None where the embedding has none)."""
+    from .modules import CrossAttentionBlock, WeightedDotProduct
+
     p_x, p_a, p_c = profile
-    ops._need_cuda(p_x, p_a, p_c, context)
     B, L = p_x.shape
     emb, dec = model.embeds, model.decoder
     d = emb.d
     ca = isinstance(dec, CrossAttentionBlock)
-    route = carca_route(what, d, [b.attn.H for b in model.encoder], L, dec.attn.H if ca else None, allow_composed)
-    if not ca and not isinstance(dec, (DotProduct, WeightedDotProduct)):
-        raise CarcaHipError(f"{what}: decoder {type(dec).__name__} is not covered")
-    n_ctx = context.shape[-1] if context is not None else 0
-    if several is None and context is not None and tuple(context.shape) != (B, n_ctx):
-        raise CarcaHipError(f"{what}: context must be [B, n_ctx], got {tuple(context.shape)}")
     T = emb.item_table()
     n_items = T.shape[0]
     M = emb.context_matrix(n_ctx)
@@ -354,68 +369,55 @@ def carca_model_side(model, profile, context: Optional[Tensor], what: str, D,
             x = ops.sa_block_fwd(x, p_x, blk.weights_struct(x.device), d, blk.attn.H, blk.residual)
         p_n = ops.layernorm_fwd(x.reshape(B * L, -1), model.norm.weight, model.norm.bias, d, dpi)
     p_ids = ops._ids32(p_x)
-    keep = [T, p_ids, p_n]
-    D.B, D.L, D.n_items, D.d, D.H = B, L, n_items, d, H
-    D.p_ids, D.ld_p_ids = p_ids.data_ptr(), L
+    f = dict(B=B, L=L, n_items=n_items, d=d, H=H, p_ids=p_ids.data_ptr(), ld_p_ids=L)
     if ca:
         qt, wt, wd = dec.recommend_tables(T)
         a = dec.attn
         (kk,) = ops.gemm_rows([dict(a0=p_n)], a.WK.weight.detach(), d, d, ld, bias=a.WK.bias.detach())
         (vv,) = ops.gemm_rows([dict(a0=p_n)], a.WV.weight.detach(), d, d, ld, bias=a.WV.bias.detach())
         (uu,) = ops.gemm_rows([dict(a0=vv)], wd, H, d, 4)  # u_lh = w_h . V_lh (the decoder FFN folded in)
-        keep += [qt, wt, kk, uu]
-        D.decoder = 0
-        D.item_q, D.ld_item_q = qt.data_ptr(), qt.stride(0)
-        D.user_k, D.ld_user_k, D.user_u, D.ld_user_u = kk.data_ptr(), kk.stride(0), uu.data_ptr(), uu.stride(0)
-        D.ffn_b = dec.ffn.bias.data_ptr()
+        f.update(decoder=0, item_q=qt.data_ptr(), ld_item_q=qt.stride(0), user_k=kk.data_ptr(), ld_user_k=kk.stride(0),
+                 user_u=uu.data_ptr(), ld_user_u=uu.stride(0), ffn_b=dec.ffn.bias.data_ptr())
         if dec.residual:
-            D.item_w, D.ld_item_w = wt.data_ptr(), wt.stride(0)
-    else:
-        rows = p_n
-        D.decoder = 1
-        if isinstance(dec, WeightedDotProduct):  # carca.py:385-389
-            rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi)
-            if dec.norm:
-                rows = ops.l2norm_fwd(rows, d, dpi)
-                D.decoder = 2
-        keep.append(rows)
-        last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
-        D.item_q, D.ld_item_q = T.data_ptr(), T.stride(0)
-        D.user_q, D.ld_user_q = last.data_ptr(), last.stride(0)
-    if M is not None and several is None:  # M c_u [B, d]: the context's share of every candidate's embedding
-        mc, dq, off = carca_context_rows(model, M, context)
-        keep += [mc, dq, off]
-        if ca:
-            D.user_q, D.ld_user_q = dq.data_ptr(), dq.stride(0)
+            f.update(item_w=wt.data_ptr(), ld_item_w=wt.stride(0))
+        return ModelSide(fields=f, p_ids=p_ids, T=T, p_n=p_n, qt=qt, wt=wt, kk=kk, uu=uu), M
+    rows = p_n
+    f["decoder"] = 1
+    if isinstance(dec, WeightedDotProduct):  # carca.py:385-389
+        rows = ops.slot_decay_scale(p_n, B, L, d, dec.gamma, dpi)
+        if dec.norm:
+            rows = ops.l2norm_fwd(rows, d, dpi)
+            f["decoder"] = 2
+    last = rows.view(B, L, dpi)[:, L - 1]  # the last profile slot scores every candidate (carca.py:364,393)
+    f.update(item_q=T.data_ptr(), ld_item_q=T.stride(0), user_q=last.data_ptr(), ld_user_q=last.stride(0))
+    return ModelSide(fields=f, p_ids=p_ids, T=T, p_n=p_n, rows=rows), M
+
+
+def carca_model_side(model, profile, context: Optional[Tensor], what: str, allow_composed: bool = False) -> ModelSide:
+    """The model side of the CARCA calls under one request context per user, context [B, n_ctx] or None: the envelope
+    checks (_carca_envelope), the share that reads no context (_carca_context_free), and last the rows through which the
+    context enters a score, M c, dq and w . M c (carca_context_rows; side.mc, side.dq, side.off).  Call under no_grad."""
+    ops._need_cuda(*profile, context)
+    route = _carca_envelope(model, profile, what, allow_composed)
+    n_ctx = context.shape[-1] if context is not None else 0
+    if context is not None and tuple(context.shape) != (profile[0].shape[0], n_ctx):
+        raise CarcaHipError(f"{what}: context must be [B, n_ctx], got {tuple(context.shape)}")
+    side, M = _carca_context_free(model, profile, n_ctx, route)
+    if M is not None:  # M c_u [B, d]: the context's share of every candidate's embedding
+        side.mc, side.dq, side.off = mc, dq, off = carca_context_rows(model, M, context)
+        if dq is not None:  # (a cross-attention decoder)
+            side.fields.update(user_q=dq.data_ptr(), ld_user_q=dq.stride(0))
             if off is not None:
-                D.user_off, D.ld_user_off = off.data_ptr(), off.stride(0)
+                side.fields.update(user_off=off.data_ptr(), ld_user_off=off.stride(0))
         else:
-            D.user_m, D.ld_user_m = mc.data_ptr(), mc.stride(0)
-    elif M is not None:
-        by_context = ops._f32(context.transpose(0, 1))  # [C, B, n_ctx]: each context a dense [B, n_ctx] operand
-        mc, dq, off = carca_context_rows_at(model, M, by_context)
-
-        def by_user(t):  # [C, B, ld] -> [B, C, ld] dense: row u * C + c, row stride ld = shape[2] (C = 1: the same memory)
-            t = t.transpose(0, 1).contiguous()
-            keep.append(t)
-            return t
-        several.n_contexts = context.shape[1]
-        if ca:
-            dq = by_user(dq)
-            several.user_q, several.ld_user_q = dq.data_ptr(), dq.shape[2]
-            if off is not None:
-                off = by_user(off)
-                several.user_off, several.ld_user_off = off.data_ptr(), off.shape[2]
-        else:
-            mc = by_user(mc)
-            several.user_m, several.ld_user_m = mc.data_ptr(), mc.shape[2]
-    return keep, p_ids
+            side.fields.update(user_m=mc.data_ptr(), ld_user_m=mc.stride(0))
+    return side
 
 
-def knn_model_side(model, profile, what: str, D) -> Tuple[list, Tensor]:
-    """Fills the model-side fields of a KnnRecommendDesc / KnnRankDesc: the catalogue is the registered table [n_items, F]
-    (fp32, contiguous rows) with its int8 copy where it qualifies (table mode only), the query p_a[:, L-1] when p_a is
-    given (dense), else the table row of p_x[:, L-1].  Returns (the tensors D points into, p_x as int32)."""
+def knn_model_side(model, profile, what: str) -> ModelSide:
+    """The model side of KNN.recommend / rank_items: the catalogue is the registered table [n_items, F] (fp32, contiguous
+    rows) with its int8 copy where it qualifies (table mode only), the query p_a[:, L-1] when p_a is given (dense), else
+    the table row of p_x[:, L-1]."""
     table = model._attr_table
     if table is None:
         raise CarcaHipError(f"{what}: no attribute table registered -- call register_attr_table(attrs) with the "
@@ -425,56 +427,71 @@ def knn_model_side(model, profile, what: str, D) -> Tuple[list, Tensor]:
     B, L = p_x.shape
     n_items, F = table.shape
     p_ids = ops._ids32(p_x)
-    keep = [table, p_ids]
-    D.B, D.L, D.n_items, D.F = B, L, n_items, F
-    D.p_ids, D.ld_p_ids = p_ids.data_ptr(), p_ids.stride(0)
-    D.table, D.ld_table = table.data_ptr(), table.stride(0)
+    f = dict(B=B, L=L, n_items=n_items, F=F, p_ids=p_ids.data_ptr(), ld_p_ids=p_ids.stride(0),
+             table=table.data_ptr(), ld_table=table.stride(0))
     if p_a is not None:
         if p_a.dim() != 3 or p_a.shape[0] != B or p_a.shape[2] != F:
             raise CarcaHipError(f"{what}: p_a {tuple(p_a.shape)} does not match [B, L, F] = [{B}, {L}, {F}]")
         q = p_a[:, -1]
         if q.dtype != torch.float32 or q.stride(-1) != 1:
             q = q.to(torch.float32).contiguous()
-        keep.append(q)
-        D.user_a, D.ld_user_a = q.data_ptr(), q.stride(0)
-    else:
-        table_i8 = model.int8_table()
-        if table_i8 is not None:
-            keep.append(table_i8)
-            D.table_i8, D.ld_table_i8 = table_i8.data_ptr(), table_i8.stride(0)
-    return keep, p_ids
+        f.update(user_a=q.data_ptr(), ld_user_a=q.stride(0))
+        return ModelSide(fields=f, p_ids=p_ids, table=table, q=q)
+    table_i8 = model.int8_table()
+    if table_i8 is not None:
+        f.update(table_i8=table_i8.data_ptr(), ld_table_i8=table_i8.stride(0))
+    return ModelSide(fields=f, p_ids=p_ids, table=table, table_i8=table_i8)
 
 
 def _ids32_clamped(ids: Tensor, n_items: int) -> Tensor:  # (clamped first: no int64 id wraps into range on the way to int32)
     return ops._ids32(ids if ids.dtype == torch.int32 else ids.clamp(-1, n_items))
 
 
-def _exclusion(what: str, exclude, p_ids: Tensor, D, keep: list, clamp: bool) -> None:
-    """exclude ("profile", None or an int [B, E] tensor) -> D.exclude / n_exclude / ld_exclude.  clamp: as _ids32_clamped
-    (the rank call; the top-k call casts as it always has, without the extra launch)."""
+def _exclusion(what: str, exclude, p_ids: Tensor, D, clamp: bool) -> Optional[Tensor]:
+    """exclude ("profile", None or an int [B, E] tensor) -> D.exclude / n_exclude / ld_exclude, and the int32 tensor they
+    point into (None: no list), which the caller keeps.  clamp: as _ids32_clamped (the rank call; the top-k call casts as
+    it always has, without the extra launch)."""
     if isinstance(exclude, str):
         if exclude != "profile":
             raise CarcaHipError(f'{what}: exclude must be "profile", None or an int [B, E] tensor')
         excl = p_ids
     elif exclude is None:
-        return
+        return None
     else:
         ops._need_cuda(exclude)
         if exclude.dim() != 2 or exclude.shape[0] != D.B or exclude.is_floating_point():
             raise CarcaHipError(f"{what}: exclude must be an int [B, E] tensor")
         excl = _ids32_clamped(exclude, D.n_items) if clamp else ops._ids32(exclude)
-    if excl.shape[1] > 0:
-        keep.append(excl)
-        D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
+    if excl.shape[1] == 0:
+        return None
+    D.exclude, D.n_exclude, D.ld_exclude = excl.data_ptr(), excl.shape[1], excl.stride(0)
+    return excl
+
+
+def _topk_desc(what: str, side: ModelSide, k: int, exclude, desc=_lib.RecommendDesc):
+    """-> (side's descriptor of class desc with k and the exclusion list set; the list of what it points into, the side
+    first, held by the call until its launch is queued)."""
+    D = side.desc(desc)
+    D.k = int(k)
+    return D, [side, _exclusion(what, exclude, side.p_ids, D, clamp=False)]
+
+
+def _outputs(D, second: Optional[str], shape, device) -> Tuple[Tensor, Tensor]:
+    """Fresh outputs of `shape` (float32, int64), one row per user; D.scores and, where named, D.<second> point at them,
+    their ld_ a user's row."""
+    outs = (torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.int64, device=device))
+    ld = math.prod(shape[1:])
+    D.scores, D.ld_scores = outs[0].data_ptr(), ld
+    if second is not None:
+        setattr(D, second, outs[1].data_ptr())
+        setattr(D, "ld_" + second, ld)
+    return outs
 
 
 def _launch(what: str, D, entry: str, second: str, n: int, device, cand=None) -> Tuple[Tensor, Tensor]:
-    """Points D.scores and D.<second> at fresh [B, n] outputs (float32, int64) and queues the C entry point -- with a
-    candidate list `cand`, its _among form."""
-    outs = (torch.empty(D.B, n, dtype=torch.float32, device=device), torch.empty(D.B, n, dtype=torch.int64, device=device))
-    for name, t in zip(("scores", second), outs):
-        setattr(D, name, t.data_ptr())
-        setattr(D, "ld_" + name, n)
+    """Points D at fresh [B, n] outputs (_outputs) and queues the C entry point -- with a candidate list `cand`, its
+    _among form."""
+    outs = _outputs(D, second, (D.B, n), device)
     if cand is None:
         rc = getattr(_lib.load(), entry)(C.byref(D), ops._stream())
     else:
@@ -483,29 +500,19 @@ def _launch(what: str, D, entry: str, second: str, n: int, device, cand=None) ->
     return outs
 
 
-def _fill(fill: Callable, what: str, D, allow_composed: bool):
-    """fill(what, D) -> (keep, p_ids); the keyword goes only to a model side that was asked for it (carca_model_side)."""
-    return fill(what, D, allow_composed=True) if allow_composed else fill(what, D)
-
-
-def recommend(what: str, desc, entry: str, fill: Callable, profile, k: int, exclude,
-              candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
-    """The top-k call: desc the descriptor class, entry its C entry point, fill(what, D) -> (keep, p_ids) the model side;
-    candidates: None, or the set the call is restricted to (entry + "_among"); allow_composed: CARCA's wider envelope
-    (carca_route), handed to fill."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+def recommend(what: str, desc, entry: str, model_side: Callable, profile, k: int, exclude,
+              candidates=None) -> Tuple[Tensor, Tensor]:
+    """The top-k call: desc the descriptor class, entry its C entry point, model_side() -> the ModelSide, run after the
+    argument checks; candidates: None, or the set the call is restricted to (entry + "_among")."""
+    _check_k(what, k)
     with torch.no_grad():
-        D = desc()
-        keep, p_ids = _fill(fill, what, D, allow_composed)
-        D.k = int(k)
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        D, keep = _topk_desc(what, model_side(), k, exclude, desc)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
-        return _launch(what, D, entry, "ids_out", int(k), profile[0].device, cand)
+        return _launch(what, D, entry, "ids_out", D.k, profile[0].device, cand)
 
 
-def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tensor, exclude,
-               candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+def rank_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, exclude,
+               candidates=None) -> Tuple[Tensor, Tensor]:
     """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""
     ops._need_cuda(items)
     if items.dim() != 2 or items.is_floating_point() or items.shape[0] != profile[0].shape[0]:
@@ -514,12 +521,11 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
     if not 1 <= N <= KMAX:
         raise CarcaHipError(f"{what}: N = {N} items per user outside 1..{KMAX}")
     with torch.no_grad():
-        D = desc()
-        keep, p_ids = _fill(fill, what, D, allow_composed)
-        _exclusion(what, exclude, p_ids, D, keep, clamp=True)
+        side = model_side()
+        D = side.desc(desc)
+        keep = [side, _exclusion(what, exclude, side.p_ids, D, clamp=True)]
         lst = _ids32_clamped(items, D.n_items)
-        keep.append(lst)
-        D.items, D.n_list, D.ld_items = lst.data_ptr(), N, lst.stride(0)
+        _set_list(D, lst)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
         return _launch(what, D, entry, "ranks", N, profile[0].device, cand)
 
@@ -528,55 +534,50 @@ def rank_items(what: str, desc, entry: str, fill: Callable, profile, items: Tens
 LIST_FUSED_MAX = 1024  # longest list of the one-launch top-k (csrc: LS_FUSED_MAX); read at call time
 
 
-def _lists(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool, desc=_lib.ListsDesc):
+def _lists(what: str, model_side: Callable, profile, items: Tensor, desc=_lib.ListsDesc):
     """The checks and the descriptor score_items and recommend_from share (desc: explain's, which carries the same list
-    fields): -> (D, keep, p_ids, the lists as int32)."""
+    fields): -> (D, the ModelSide that model_side() built once the list passed, the lists as int32)."""
     if not isinstance(items, Tensor) or items.dim() != 2 or items.is_floating_point() or items.is_complex() or \
             items.dtype == torch.bool or items.shape[0] != profile[0].shape[0] or items.shape[1] < 1:
         raise CarcaHipError(f"{what}: items must be an int [B, N] tensor with N >= 1, one row per user")
     if items.shape[0] * items.shape[1] >= 2 ** 31:
         raise CarcaHipError(f"{what}: B * N = {items.shape[0] * items.shape[1]} does not fit an int")
     ops._need_cuda(items)
-    D = desc()
-    keep, p_ids = _fill(fill, what, D, allow_composed)
-    lst = _ids32_clamped(items, D.n_items)
-    return D, keep, p_ids, lst
+    side = model_side()
+    D = side.desc(desc)
+    return D, side, _ids32_clamped(items, D.n_items)
 
 
-def _lists_launch(what: str, D, keep: list, lst: Tensor, entry: str) -> None:
-    keep.append(lst)
+def _set_list(D, lst: Tensor) -> None:
     D.items, D.n_list, D.ld_items = lst.data_ptr(), lst.shape[1], lst.stride(0)
-    _lib.check(getattr(_lib.load(), entry)(C.byref(D), ops._stream()), what)
 
 
-def score_items(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool = False) -> Tensor:
+def score_items(what: str, model_side: Callable, profile, items: Tensor) -> Tensor:
     """The list-scoring call: scores [B, N] float32 of each user's own list, in caller order (carca_score_lists)."""
     with torch.no_grad():
-        D, keep, _, lst = _lists(what, fill, profile, items, allow_composed)
+        D, side, lst = _lists(what, model_side, profile, items)
         scores = torch.empty(D.B, lst.shape[1], dtype=torch.float32, device=profile[0].device)
         D.scores, D.ld_scores = scores.data_ptr(), lst.shape[1]
-        _lists_launch(what, D, keep, lst, "carca_score_lists")
+        _set_list(D, lst)
+        _lib.check(_lib.load().carca_score_lists(C.byref(D), ops._stream()), what)
         return scores
 
 
-def recommend_from(what: str, fill: Callable, profile, items: Tensor, k: int, exclude,
-                   allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+def recommend_from(what: str, model_side: Callable, profile, items: Tensor, k: int, exclude) -> Tuple[Tensor, Tensor]:
     """The top-k call over each user's own list (carca_recommend_lists): a list of up to LIST_FUSED_MAX entries goes to
     the one-launch kernel as it is; a longer one is sorted per row on the device first (no host sync), which is the form
     the split path asks for."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    k = _check_k(what, k)
     with torch.no_grad():
-        D, keep, p_ids, lst = _lists(what, fill, profile, items, allow_composed)
-        D.k = int(k)
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        D, side, lst = _lists(what, model_side, profile, items)
+        D.k = k
+        excl = _exclusion(what, exclude, side.p_ids, D, clamp=False)
         if lst.shape[1] > LIST_FUSED_MAX:
             lst = torch.sort(lst, dim=1).values
             D.sorted_rows = 1
-        outs = (torch.empty(D.B, int(k), dtype=torch.float32, device=profile[0].device),
-                torch.empty(D.B, int(k), dtype=torch.int64, device=profile[0].device))
-        D.scores, D.ld_scores, D.ids_out, D.ld_ids_out = outs[0].data_ptr(), int(k), outs[1].data_ptr(), int(k)
-        _lists_launch(what, D, keep, lst, "carca_recommend_lists")
+        outs = _outputs(D, "ids_out", (D.B, k), profile[0].device)
+        _set_list(D, lst)
+        _lib.check(_lib.load().carca_recommend_lists(C.byref(D), ops._stream()), what)
         return outs
 
 
@@ -595,14 +596,14 @@ def contexts_args(what: str, single: str, profile, contexts) -> Tuple[int, int]:
     return contexts.shape[1], contexts.shape[2]
 
 
-def carca_model_side_at(model, profile, contexts: Tensor, what: str, single: str, D,
-                        allow_composed: bool = False) -> Tuple[list, Tensor, "_lib.Contexts"]:
+def carca_model_side_at(model, profile, contexts: Tensor, what: str, single: str,
+                        allow_composed: bool = False) -> ModelSide:
     """carca_model_side for the C request contexts of each user, contexts [B, C, n_ctx] (contexts_args has checked it):
-    the share that reads no context runs ONCE, and the context rows of every (user, context) pair come back as a
-    CarcaContexts, row u * C + c (carca_model_side's `several`).  Two differences of envelope, both raised before anything
-    is launched and naming `single`, the single-context call: an embedding without a context matrix, and a cross-attention
-    decoder over more than CARCA_MAX_L slots.  Returns (the tensors kept alive, the profile ids as int32, the
-    CarcaContexts)."""
+    the share that reads no context runs ONCE (_carca_context_free), and the context rows of every (user, context) pair
+    (carca_context_rows_at) go to side.contexts, a filled CarcaContexts, as row u * C + c; the descriptors' own context
+    rows stay null.  side.dq, side.off or side.mc are then [B, C, ld].  Two differences of envelope, both raised before
+    anything is launched and naming `single`, the single-context call: an embedding without a context matrix, and a
+    cross-attention decoder over more than CARCA_MAX_L slots."""
     from .modules import CrossAttentionBlock
 
     ops._need_cuda(*profile, contexts)
@@ -613,32 +614,43 @@ def carca_model_side_at(model, profile, contexts: Tensor, what: str, single: str
     if isinstance(model.decoder, CrossAttentionBlock) and L > _lib.MAX_L:
         raise CarcaHipError(f"{what}: profile length L = {L} exceeds CARCA_MAX_L = {_lib.MAX_L}: the chunked scorer of "
                             f"longer profiles is not served under several contexts (call {single} per context)")
-    X = _lib.Contexts()
-    keep, p_ids = carca_model_side(model, profile, contexts, what, D, allow_composed, several=X)
-    return keep, p_ids, X
+    route = _carca_envelope(model, profile, what, allow_composed)
+    side, M = _carca_context_free(model, profile, contexts.shape[2], route)
+    by_context = ops._f32(contexts.transpose(0, 1))  # [C, B, n_ctx]: each context a dense [B, n_ctx] operand
+    mc, dq, off = carca_context_rows_at(model, M, by_context)
+
+    def by_user(t):  # [C, B, ld] -> [B, C, ld] dense: row u * C + c, row stride ld = shape[2] (C = 1: the same memory)
+        return t.transpose(0, 1).contiguous()
+    X = side.contexts = _lib.Contexts()
+    X.n_contexts = contexts.shape[1]
+    if dq is not None:  # (a cross-attention decoder)
+        side.dq = dq = by_user(dq)
+        X.user_q, X.ld_user_q = dq.data_ptr(), dq.shape[2]
+        if off is not None:
+            side.off = off = by_user(off)
+            X.user_off, X.ld_user_off = off.data_ptr(), off.shape[2]
+    else:
+        side.mc = mc = by_user(mc)
+        X.user_m, X.ld_user_m = mc.data_ptr(), mc.shape[2]
+    return side
 
 
-def _lists_at(what: str, single: str, model, profile, contexts: Tensor, items: Tensor, allow_composed: bool):
-    """_lists under several contexts: -> (D, keep, the lists as int32, the CarcaContexts)."""
-    n_c, _ = contexts_args(what, single, profile, contexts)
+def _lists_at(what: str, model_side: Callable, profile, contexts: Tensor, items: Tensor):
+    """_lists under several contexts, the list set: -> (D, the ModelSide, the lists as int32)."""
+    n_c, _ = contexts_args(what, "score_items", profile, contexts)
     if isinstance(items, Tensor) and items.dim() == 2 and n_c * items.shape[1] >= 2 ** 31:
         raise CarcaHipError(f"{what}: C * N = {n_c * items.shape[1]} does not fit an int")
-    box = []
-
-    def fill(what_, D, allow_composed=False):
-        keep, p_ids, X = carca_model_side_at(model, profile, contexts, what_, single, D, allow_composed)
-        box.append(X)
-        return keep, p_ids
-    D, keep, _, lst = _lists(what, fill, profile, items, allow_composed)
-    keep.append(lst)
-    D.items, D.n_list, D.ld_items = lst.data_ptr(), lst.shape[1], lst.stride(0)
-    return D, keep, lst, box[0]
+    D, side, lst = _lists(what, model_side, profile, items)
+    _set_list(D, lst)
+    return D, side, lst
 
 
-def score_items_at(what: str, model, profile, contexts: Tensor, items: Tensor, allow_composed: bool = False) -> Tensor:
-    """score_items under each of a user's C contexts (carca_score_lists_at): scores [B, C, N] float32."""
+def score_items_at(what: str, model_side: Callable, profile, contexts: Tensor, items: Tensor) -> Tensor:
+    """score_items under each of a user's C contexts (carca_score_lists_at): scores [B, C, N] float32.  model_side() ->
+    carca_model_side_at's ModelSide."""
     with torch.no_grad():
-        D, keep, lst, X = _lists_at(what, "score_items", model, profile, contexts, items, allow_composed)
+        D, side, lst = _lists_at(what, model_side, profile, contexts, items)
+        X = side.contexts
         n_c, N = X.n_contexts, lst.shape[1]
         scores = torch.empty(D.B, n_c, N, dtype=torch.float32, device=profile[0].device)
         D.scores, D.ld_scores = scores.data_ptr(), n_c * N
@@ -646,17 +658,15 @@ def score_items_at(what: str, model, profile, contexts: Tensor, items: Tensor, a
         return scores
 
 
-def best_context(what: str, model, profile, contexts: Tensor, items: Tensor,
-                 allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+def best_context(what: str, model_side: Callable, profile, contexts: Tensor, items: Tensor) -> Tuple[Tensor, Tensor]:
     """Per (user, list entry) the context of the largest logit (carca_score_lists_at with best_context): (scores [B, N]
     float32, which [B, N] int64); no [B, C, N] buffer is formed."""
     with torch.no_grad():
-        D, keep, lst, X = _lists_at(what, "score_items", model, profile, contexts, items, allow_composed)
-        N, dev = lst.shape[1], profile[0].device
-        scores = torch.empty(D.B, N, dtype=torch.float32, device=dev)
-        which = torch.empty(D.B, N, dtype=torch.int64, device=dev)
-        D.scores, D.ld_scores = scores.data_ptr(), N
-        _lib.check(_lib.load().carca_score_lists_at(C.byref(D), C.byref(X), which.data_ptr(), N, ops._stream()), what)
+        D, side, lst = _lists_at(what, model_side, profile, contexts, items)
+        N = lst.shape[1]
+        scores, which = _outputs(D, None, (D.B, N), profile[0].device)
+        _lib.check(_lib.load().carca_score_lists_at(C.byref(D), C.byref(side.contexts), which.data_ptr(), N,
+                                                    ops._stream()), what)
         return scores, which
 
 
@@ -679,33 +689,31 @@ def _user_rows(D, X, lo: int, hi: int):
     return Dc, Xc
 
 
-def recommend_at(what: str, model, profile, contexts: Tensor, k: int, exclude, candidates=None,
-                 allow_composed: bool = False, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
+def recommend_at(what: str, model_side: Callable, profile, contexts: Tensor, k: int, exclude, candidates=None,
+                 max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
     """recommend under each of a user's C contexts (carca_recommend_at / carca_recommend_among_at): (scores [B, C, k]
-    float32, ids [B, C, k] int64).  The users go in chunks whose [users, C, n_slots] fp32 logit scratch stays within
-    max_scratch_bytes, with no sync between them, each writing its rows of the outputs."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    float32, ids [B, C, k] int64).  model_side() -> carca_model_side_at's ModelSide.  The users go in chunks whose
+    [users, C, n_slots] fp32 logit scratch stays within max_scratch_bytes, with no sync between them, each writing its
+    rows of the outputs."""
+    k = _check_k(what, k)
     n_c, _ = contexts_args(what, "recommend", profile, contexts)
-    k, dev = int(k), profile[0].device
+    dev = profile[0].device
     with torch.no_grad():
-        D = _lib.RecommendDesc()
-        keep, p_ids, X = carca_model_side_at(model, profile, contexts, what, "recommend", D, allow_composed)
+        side = model_side()
+        D, X = side.desc(_lib.RecommendDesc), side.contexts
         D.k = k
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
-        if D.n_exclude and n_c > 1:  # user u's row for each of its contexts: row u * C + c of the launch's B * C users
-            excl = keep[-1][:, :D.n_exclude].repeat_interleave(n_c, dim=0).contiguous()
-            keep.append(excl)
+        excl = _exclusion(what, exclude, side.p_ids, D, clamp=False)
+        if excl is not None and n_c > 1:  # user u's row for each of its contexts: row u * C + c of the launch's B * C users
+            excl = excl.repeat_interleave(n_c, dim=0).contiguous()
             D.exclude, D.ld_exclude = excl.data_ptr(), excl.stride(0)
+        keep = [side, excl]
         cand = _candidates(what, candidates, D, keep, dev)
         n_slots = D.n_items if cand is None else cand.n
         users = int(max_scratch_bytes) // (4 * n_c * max(n_slots, 1))
         if users < 1:
             raise CarcaHipError(f"{what}: one user's [C, n_slots] = [{n_c}, {n_slots}] fp32 logits need "
                                 f"{4 * n_c * max(n_slots, 1)} bytes, max_scratch_bytes is {int(max_scratch_bytes)}")
-        scores = torch.empty(D.B, n_c, k, dtype=torch.float32, device=dev)
-        ids = torch.empty(D.B, n_c, k, dtype=torch.int64, device=dev)
-        D.scores, D.ids_out, D.ld_scores, D.ld_ids_out = scores.data_ptr(), ids.data_ptr(), n_c * k, n_c * k
+        outs = _outputs(D, "ids_out", (D.B, n_c, k), dev)
         lib, stream = _lib.load(), ops._stream()
         for lo in range(0, D.B, users):
             Dc, Xc = _user_rows(D, X, lo, min(D.B, lo + users))
@@ -714,7 +722,7 @@ def recommend_at(what: str, model, profile, contexts: Tensor, k: int, exclude, c
             else:
                 rc = lib.carca_recommend_among_at(C.byref(Dc), C.byref(Xc), C.byref(cand), stream)
             _lib.check(rc, what)
-        return scores, ids
+        return outs
 
 
 # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists) --------------
@@ -728,13 +736,12 @@ def _explain_m(what: str, m: int) -> int:
     return int(m)
 
 
-def _explain_launch(what: str, E, keep: list, lst: Tensor, m: Optional[int], device) -> tuple:
+def _explain_launch(what: str, E, lst: Tensor, m: Optional[int], device) -> tuple:
     """Points E at the list and at fresh outputs and queues carca_explain_lists: m None -> the dense form,
     (scores, base, contrib [B, N, L], weights [B, H, N, L]); else the top-m form, (scores, base, slots, slot_items,
     contrib), each [B, N, m]."""
     B, N = E.B, lst.shape[1]
-    keep.append(lst)
-    E.items, E.n_list, E.ld_items = lst.data_ptr(), N, lst.stride(0)
+    _set_list(E, lst)
     scores = torch.empty(B, N, dtype=torch.float32, device=device)
     base = torch.empty(B, N, dtype=torch.float32, device=device)
     E.scores, E.ld_scores, E.base, E.ld_base = scores.data_ptr(), N, base.data_ptr(), N
@@ -754,43 +761,36 @@ def _explain_launch(what: str, E, keep: list, lst: Tensor, m: Optional[int], dev
     return outs
 
 
-def explain_items(what: str, fill: Callable, profile, items: Tensor, allow_composed: bool = False) -> tuple:
+def explain_items(what: str, model_side: Callable, profile, items: Tensor) -> tuple:
     """The dense explanation of each user's own list: (scores [B, N], base [B, N], contrib [B, N, L],
     weights [B, H, N, L]), all float32."""
     with torch.no_grad():
-        E, keep, _, lst = _lists(what, fill, profile, items, allow_composed, desc=_lib.ExplainDesc)
-        return _explain_launch(what, E, keep, lst, None, profile[0].device)
+        E, side, lst = _lists(what, model_side, profile, items, desc=_lib.ExplainDesc)
+        return _explain_launch(what, E, lst, None, profile[0].device)
 
 
-def explain_top_slots(what: str, fill: Callable, profile, items: Tensor, m: int, allow_composed: bool = False) -> tuple:
+def explain_top_slots(what: str, model_side: Callable, profile, items: Tensor, m: int) -> tuple:
     """The m profile slots with the largest contribution per (user, list entry): (scores [B, N], base [B, N],
     slots [B, N, m] int64, slot_items [B, N, m] int64, contrib [B, N, m] float32); no [B, N, L] buffer."""
     m = _explain_m(what, m)
     with torch.no_grad():
-        E, keep, _, lst = _lists(what, fill, profile, items, allow_composed, desc=_lib.ExplainDesc)
-        return _explain_launch(what, E, keep, lst, m, profile[0].device)
+        E, side, lst = _lists(what, model_side, profile, items, desc=_lib.ExplainDesc)
+        return _explain_launch(what, E, lst, m, profile[0].device)
 
 
-def recommend_explained(what: str, fill: Callable, profile, k: int, m: int, exclude, candidates=None,
-                        allow_composed: bool = False) -> tuple:
-    """recommend, then explain_top_slots over its ids, with ONE run of the model side: the explain descriptor's
-    model-side fields are the recommend descriptor's, name for name, and are copied.  -> (scores [B, k], ids [B, k],
-    slot_items [B, k, m], contrib [B, k, m])."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+def recommend_explained(what: str, model_side: Callable, profile, k: int, m: int, exclude, candidates=None) -> tuple:
+    """recommend, then explain_top_slots over its ids, with ONE run of the model side: one ModelSide fills the recommend
+    descriptor and the explain descriptor.  -> (scores [B, k], ids [B, k], slot_items [B, k, m], contrib [B, k, m])."""
+    _check_k(what, k)
     m = _explain_m(what, m)
     with torch.no_grad():
-        D = _lib.RecommendDesc()
-        keep, p_ids = _fill(fill, what, D, allow_composed)
-        D.k = int(k)
-        _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+        side = model_side()
+        D, keep = _topk_desc(what, side, k, exclude)
         device = profile[0].device
         cand = _candidates(what, candidates, D, keep, device)
-        scores, ids = _launch(what, D, "carca_recommend", "ids_out", int(k), device, cand)
-        E = _lib.ExplainDesc()
-        for name in ("B", "L", "n_items", "d", "H", "k") + tuple(f[0] for f in _lib._CARCA_MODEL):
-            setattr(E, name, getattr(D, name))
-        _, _, _, slot_items, contrib = _explain_launch(what, E, keep, ops._ids32(ids), m, device)  # (id 0: no item)
+        scores, ids = _launch(what, D, "carca_recommend", "ids_out", D.k, device, cand)
+        E = side.desc(_lib.ExplainDesc)
+        _, _, _, slot_items, contrib = _explain_launch(what, E, ops._ids32(ids), m, device)  # (id 0: no item)
         return scores, ids, slot_items, contrib
 
 
@@ -813,8 +813,7 @@ class AudienceTopK:
 
     def __init__(self, items, k: int, n_items: int, device=None):
         what = "AudienceTopK"
-        if not 1 <= int(k) <= KMAX:
-            raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+        _check_k(what, k)
         if isinstance(items, CandidateSet):
             if items.n_items != int(n_items):
                 raise CarcaHipError(f"{what}: the item set was built for n_items = {items.n_items}, the model has "
@@ -843,12 +842,9 @@ class AudienceTopK:
         int32 / int64 [B] tensor of ids below 2^31, a negative entry dropping its row; None numbers the rows from
         rows_seen on."""
         what = _what
-        if not hasattr(model, "_check_built") or not hasattr(model, "_catalogue_size"):
+        if not hasattr(model, "_check_eval_built") or not hasattr(model, "_catalogue_size"):
             raise CarcaHipError(f"{what}: model must be a CARCA ({type(model).__name__} has no users-per-item call)")
-        if model.training:
-            raise CarcaHipError(f"{what}: the model is in training mode; recommendation scores with eval semantics "
-                                "(call model.eval() first)")
-        model._check_built()
+        model._check_eval_built(what)
         B, Q = profile[0].shape[0], len(self.items)
         n_known = model._catalogue_size()
         if n_known is not None and n_known != self.n_items:
@@ -862,15 +858,13 @@ class AudienceTopK:
         if B * Q >= 1 << 31:
             raise CarcaHipError(f"{what}: B * Q = {B * Q} does not fit an int (split the users)")
         with torch.no_grad():
-            D = _lib.RecommendDesc()
-            keep, p_ids = _fill(partial(carca_model_side, model, profile, context), what, D, allow_composed)
-            if D.n_items != self.n_items:
+            side = carca_model_side(model, profile, context, what, allow_composed)
+            if side.fields["n_items"] != self.n_items:
                 raise CarcaHipError(f"{what}: the item set was built for n_items = {self.n_items}, the model has "
-                                    f"{D.n_items}")
-            if self._decoder not in (None, D.decoder):
+                                    f"{side.fields['n_items']}")
+            if self._decoder not in (None, side.fields["decoder"]):
                 raise CarcaHipError(f"{what}: the state was fed by a model with another decoder (reset() it first)")
-            D.k = self.k
-            _exclusion(what, exclude, p_ids, D, keep, clamp=False)
+            D, keep = _topk_desc(what, side, self.k, exclude)
             ids = self.ids
             if ids.device != profile[0].device or self.keys.device != ids.device:
                 raise CarcaHipError(f"{what}: the state lives on {ids.device}, the batch on {profile[0].device}")
@@ -933,8 +927,7 @@ def similar_chunks(n_queries: int, chunk_rows: int) -> list:
 
 def similar_args(what: str, items: Optional[Tensor], k: int, metric: str) -> None:
     """The argument checks that need no table."""
-    if not 1 <= int(k) <= KMAX:
-        raise CarcaHipError(f"{what}: k = {k} outside 1..{KMAX} (the largest k the selection keeps is {KMAX})")
+    _check_k(what, k)
     if metric not in SIMILAR_METRICS:
         raise ValueError(f'{what}: metric must be "cosine" or "dot", got {metric!r}')
     if items is not None and (not isinstance(items, Tensor) or items.dim() != 1 or items.is_floating_point()

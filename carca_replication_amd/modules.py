@@ -1246,6 +1246,20 @@ class CARCA(_PackedModule, Model):
                                 "SelfAttentionBlock encoders and its decoders (CrossAttentionBlock/DotProduct/"
                                 "WeightedDotProduct); there is no ATen fallback for anything else")
 
+    def _check_eval_built(self, what: str) -> None:
+        """What every serving call asks first: eval mode (the scores are forward's eval scores) and a built model."""
+        if self.training:
+            raise CarcaHipError(f"{what}: the model is in training mode; the call scores with eval semantics "
+                                "(call model.eval() first)")
+        self._check_built()
+
+    def _model_side(self, what: str, profile, context, allow_composed: bool):
+        """The thunk a shared catalogue call runs once its own arguments have passed: () -> the ModelSide."""
+        return lambda: catalogue.carca_model_side(self, profile, context, what, allow_composed=allow_composed)
+
+    def _model_side_at(self, what: str, single: str, profile, contexts, allow_composed: bool):
+        return lambda: catalogue.carca_model_side_at(self, profile, contexts, what, single, allow_composed=allow_composed)
+
     def _attn_heads(self) -> List[int]:
         """H of every attention module (the fused kernels are built per (d, H) geometry)."""
         hs = [b.attn.H for b in self.encoder]
@@ -1355,13 +1369,10 @@ class CARCA(_PackedModule, Model):
         fused blocks); the dot decoders at every (d, H), a cross-attention decoder at its built (d, H) geometries (past
         64 slots the sweep stages a user's valid slots 64 at a time: DESIGN.md section 19).  Inside the fused envelope
         the keyword changes nothing."""
-        if self.training:
-            raise CarcaHipError("recommend: the model is in training mode; recommendation scores with eval semantics "
-                                "(call model.eval() first)")
-        self._check_built()
+        self._check_eval_built("recommend")
         return catalogue.recommend("recommend", _lib.RecommendDesc, "carca_recommend",
-                                   partial(catalogue.carca_model_side, self, profile, context), profile, k, exclude,
-                                   candidates, allow_composed)
+                                   self._model_side("recommend", profile, context, allow_composed), profile, k, exclude,
+                                   candidates)
 
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
@@ -1380,13 +1391,10 @@ class CARCA(_PackedModule, Model):
         rank 0.  scores keep their meaning and their bits.
 
         allow_composed: as recommend's."""
-        if self.training:
-            raise CarcaHipError("rank_items: the model is in training mode; ranks use eval semantics "
-                                "(call model.eval() first)")
-        self._check_built()
+        self._check_eval_built("rank_items")
         return catalogue.rank_items("rank_items", _lib.RankDesc, "carca_rank_items",
-                                    partial(catalogue.carca_model_side, self, profile, context), profile, items, exclude,
-                                    candidates, allow_composed)
+                                    self._model_side("rank_items", profile, context, allow_composed), profile, items,
+                                    exclude, candidates)
 
     # ---- a candidate list per user (include/carca_hip.h: carca_score_lists / carca_recommend_lists; DESIGN.md 21) ----
     def score_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
@@ -1399,12 +1407,9 @@ class CARCA(_PackedModule, Model):
         [1, n_items) scores 0 (no host check, no out-of-bounds read); duplicates are each scored, caller order is
         kept, nothing is excluded.  One launch with the user staged once per workgroup, no scratch, no host sync.
         profile, context and the envelope are recommend's; allow_composed: as recommend's."""
-        if self.training:
-            raise CarcaHipError("score_items: the model is in training mode; list scores use eval semantics "
-                                "(call model.eval() first)")
-        self._check_built()
-        return catalogue.score_items("score_items", partial(catalogue.carca_model_side, self, profile, context), profile,
-                                     items, allow_composed)
+        self._check_eval_built("score_items")
+        return catalogue.score_items("score_items", self._model_side("score_items", profile, context, allow_composed),
+                                     profile, items)
 
     def recommend_from(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                        k: int = 10, exclude="profile", allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
@@ -1419,20 +1424,12 @@ class CARCA(_PackedModule, Model):
         with one workgroup per user; a longer list is sorted per row on the device, scored into stream scratch [B, N]
         and selected per row -- the same result either way.  exclude: recommend's three forms; 1 <= k <= 128.
         profile, context and the envelope are recommend's; allow_composed: as recommend's."""
-        if self.training:
-            raise CarcaHipError("recommend_from: the model is in training mode; recommendation scores with eval "
-                                "semantics (call model.eval() first)")
-        self._check_built()
-        return catalogue.recommend_from("recommend_from", partial(catalogue.carca_model_side, self, profile, context),
-                                        profile, items, k, exclude, allow_composed)
+        self._check_eval_built("recommend_from")
+        return catalogue.recommend_from("recommend_from",
+                                        self._model_side("recommend_from", profile, context, allow_composed), profile,
+                                        items, k, exclude)
 
     # ---- several request contexts per user (include/carca_hip.h: CarcaContexts; DESIGN.md 25) -------------------------
-    def _check_contexts_call(self, what: str) -> None:
-        if self.training:
-            raise CarcaHipError(f"{what}: the model is in training mode; the scores under a request context use eval "
-                                "semantics (call model.eval() first)")
-        self._check_built()
-
     def score_items_at(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, items: Tensor,
                        allow_composed: bool = False) -> Tensor:
         """score_items under C request contexts per user in one call: [B, C, N] float32.
@@ -1445,8 +1442,9 @@ class CARCA(_PackedModule, Model):
         is recommend's with two differences: an embedding without a context matrix (AttrEmbedding, IdEmbedding,
         MLPIdEmbedding: the score does not depend on the candidate's context) raises -- call score_items -- and so does
         a cross-attention decoder over a profile of more than 64 slots -- call score_items per context."""
-        self._check_contexts_call("score_items_at")
-        return catalogue.score_items_at("score_items_at", self, profile, contexts, items, allow_composed)
+        self._check_eval_built("score_items_at")
+        side = self._model_side_at("score_items_at", "score_items", profile, contexts, allow_composed)
+        return catalogue.score_items_at("score_items_at", side, profile, contexts, items)
 
     def best_context(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, items: Tensor,
                      allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
@@ -1456,8 +1454,9 @@ class CARCA(_PackedModule, Model):
         index.  scores is that logit through the model's link, with score_items_at's bits (= its maximum over dim 1);
         which is its context index.  An id that is no item gives score 0 and index -1.  One launch; no [B, C, N] buffer
         is formed.  Arguments and envelope: score_items_at's."""
-        self._check_contexts_call("best_context")
-        return catalogue.best_context("best_context", self, profile, contexts, items, allow_composed)
+        self._check_eval_built("best_context")
+        side = self._model_side_at("best_context", "score_items", profile, contexts, allow_composed)
+        return catalogue.best_context("best_context", side, profile, contexts, items)
 
     def recommend_at(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], contexts: Tensor, k: int = 10,
                      exclude="profile", candidates=None, allow_composed: bool = False,
@@ -1472,9 +1471,9 @@ class CARCA(_PackedModule, Model):
         that keep it within max_scratch_bytes, with no host sync, and the result does not depend on the chunking; a
         budget that does not hold one user's [C, n_slots] raises.  k, exclude, candidates and allow_composed are
         recommend's; the envelope is score_items_at's."""
-        self._check_contexts_call("recommend_at")
-        return catalogue.recommend_at("recommend_at", self, profile, contexts, k, exclude, candidates, allow_composed,
-                                      max_scratch_bytes)
+        self._check_eval_built("recommend_at")
+        side = self._model_side_at("recommend_at", "recommend", profile, contexts, allow_composed)
+        return catalogue.recommend_at("recommend_at", side, profile, contexts, k, exclude, candidates, max_scratch_bytes)
 
     # ---- item groups (include/carca_hip.h: carca_recommend_groups / carca_recommend_capped; DESIGN.md 23) -------------
     def _catalogue_size(self) -> Optional[int]:
@@ -1497,12 +1496,9 @@ class CARCA(_PackedModule, Model):
         launch picks every (user, group) list.  No host sync.  There is no candidates= argument: restrict the call by
         leaving items ungrouped.  profile, context, exclude, 1 <= k <= 128, the envelope and allow_composed are
         recommend's."""
-        if self.training:
-            raise CarcaHipError("recommend_by_group: the model is in training mode; recommendation scores with eval "
-                                "semantics (call model.eval() first)")
-        self._check_built()
-        return catalogue.recommend_by_group("recommend_by_group", partial(catalogue.carca_model_side, self, profile, context),
-                                            profile, groups, k, exclude, allow_composed, self._catalogue_size())
+        self._check_eval_built("recommend_by_group")
+        side = self._model_side("recommend_by_group", profile, context, allow_composed)
+        return catalogue.recommend_by_group("recommend_by_group", side, profile, groups, k, exclude, self._catalogue_size())
 
     def recommend_capped(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], groups,
                          k: int = 10, max_per_group: int = 1, exclude="profile",
@@ -1517,12 +1513,10 @@ class CARCA(_PackedModule, Model):
         takes every group's best min(k, max_per_group) and then the k best of their union, through a
         [B, G, min(k, max_per_group)] buffer of 64-bit keys; a buffer beyond 1 GiB raises CarcaHipError (split the batch).
         No host sync.  groups, profile, context, exclude, k, the envelope and allow_composed: as recommend_by_group."""
-        if self.training:
-            raise CarcaHipError("recommend_capped: the model is in training mode; recommendation scores with eval "
-                                "semantics (call model.eval() first)")
-        self._check_built()
-        return catalogue.recommend_capped("recommend_capped", partial(catalogue.carca_model_side, self, profile, context),
-                                          profile, groups, k, max_per_group, exclude, allow_composed, self._catalogue_size())
+        self._check_eval_built("recommend_capped")
+        side = self._model_side("recommend_capped", profile, context, allow_composed)
+        return catalogue.recommend_capped("recommend_capped", side, profile, groups, k, max_per_group, exclude,
+                                          self._catalogue_size())
 
     # ---- the k best users per listed item (include/carca_hip.h: carca_recommend_users; DESIGN.md 24) ------------------
     def recommend_users(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items,
@@ -1542,22 +1536,16 @@ class CARCA(_PackedModule, Model):
         index.  The result does not depend on scheduling, and a larger audience over many batches comes from
         catalogue.AudienceTopK (train.audience walks a loader), whose result does not depend on the batching either.
         1 <= k <= 128; eval mode; profile, context, the envelope and allow_composed are recommend's."""
-        if self.training:
-            raise CarcaHipError("recommend_users: the model is in training mode; recommendation scores with eval "
-                                "semantics (call model.eval() first)")
-        self._check_built()
+        self._check_eval_built("recommend_users")
         return catalogue.recommend_users(self, profile, context, items, k, exclude, user_ids, allow_composed)
 
     # ---- which profile slots drive a score (include/carca_hip.h: carca_explain_lists; DESIGN.md 22) ------------------
     def _check_explainable(self, what: str) -> None:
-        if self.training:
-            raise CarcaHipError(f"{what}: the model is in training mode; explanations use eval semantics "
-                                "(call model.eval() first)")
+        self._check_eval_built(what)
         if not isinstance(self.decoder, CrossAttentionBlock):
             raise CarcaHipError(f"{what}: decoder {type(self.decoder).__name__} has no attention over the profile to "
                                 "decompose: its eval score reads the last profile slot only (a cross-attention decoder "
                                 "is needed)")
-        self._check_built()
 
     def explain_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                       allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -1575,8 +1563,8 @@ class CARCA(_PackedModule, Model):
         an empty profile.  items, profile, context, the envelope and allow_composed are score_items'; one launch, no
         host sync.  A dot decoder raises CarcaHipError."""
         self._check_explainable("explain_items")
-        return catalogue.explain_items("explain_items", partial(catalogue.carca_model_side, self, profile, context),
-                                       profile, items, allow_composed)
+        return catalogue.explain_items("explain_items", self._model_side("explain_items", profile, context, allow_composed),
+                                       profile, items)
 
     def explain_top_slots(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor],
                           items: Tensor, m: int = 3, allow_composed: bool = False
@@ -1590,8 +1578,8 @@ class CARCA(_PackedModule, Model):
         item, pad with slot -1, item 0 and contribution 0.  1 <= m <= catalogue.EXPLAIN_TOP_MAX = 8.  No [B, N, L]
         buffer exists on this path.  Everything else is explain_items'."""
         self._check_explainable("explain_top_slots")
-        return catalogue.explain_top_slots("explain_top_slots", partial(catalogue.carca_model_side, self, profile, context),
-                                           profile, items, m, allow_composed)
+        side = self._model_side("explain_top_slots", profile, context, allow_composed)
+        return catalogue.explain_top_slots("explain_top_slots", side, profile, items, m)
 
     def recommend_explained(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor],
                             k: int = 10, m: int = 3, exclude="profile", candidates=None, allow_composed: bool = False
@@ -1603,9 +1591,8 @@ class CARCA(_PackedModule, Model):
         those ids (the padding id 0 explains as an id that is no item: items 0, contributions 0).  The profile side
         runs once for both launches.  k, exclude, candidates and allow_composed are recommend's, m explain_top_slots'."""
         self._check_explainable("recommend_explained")
-        return catalogue.recommend_explained("recommend_explained",
-                                             partial(catalogue.carca_model_side, self, profile, context), profile, k, m,
-                                             exclude, candidates, allow_composed)
+        side = self._model_side("recommend_explained", profile, context, allow_composed)
+        return catalogue.recommend_explained("recommend_explained", side, profile, k, m, exclude, candidates)
 
     # ---- item-to-item top-k (include/carca_hip.h: carca_similar_items; DESIGN.md 17) ---------------------------------
     def similar_items(self, items: Optional[Tensor] = None, k: int = 10, metric: str = "cosine", exclude_self: bool = True,
@@ -1954,7 +1941,7 @@ class KNN(Model):
         entry) and padding are CARCA.recommend's: ties go to the smaller id, id 0 is never listed, fewer than k
         eligible items pad with id 0 and score 0.  1 <= k <= 128; any L; train and eval mode alike."""
         return catalogue.recommend("KNN.recommend", _lib.KnnRecommendDesc, "carca_knn_recommend",
-                                   partial(catalogue.knn_model_side, self, profile), profile, k, exclude)
+                                   lambda: catalogue.knn_model_side(self, profile, "KNN.recommend"), profile, k, exclude)
 
     def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
                           k: int = 10, pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile",
@@ -1983,7 +1970,8 @@ class KNN(Model):
         or an id outside [0, n_items) gives rank -1 and score 0.  Scores and the order are bit-identical to
         recommend's; profile, context and exclude are recommend's."""
         return catalogue.rank_items("KNN.rank_items", _lib.KnnRankDesc, "carca_knn_rank_items",
-                                    partial(catalogue.knn_model_side, self, profile), profile, items, exclude)
+                                    lambda: catalogue.knn_model_side(self, profile, "KNN.rank_items"), profile, items,
+                                    exclude)
 
     def forward(self, profile: Tuple[Tensor, Tensor, Tensor], targets: List[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
         p_x, p_a, p_c = profile

@@ -6,9 +6,11 @@ import os
 import re
 
 import pytest
+import torch
 
 from carca_replication_amd import CarcaHipError, _lib, catalogue, long_profile, ops, train
 from carca_replication_amd.modules import CARCA, KNN
+from tests.model_util import build_model
 
 # (d, H) with a fused attention geometry built (CARCA_ATT_GEOMETRIES), and without one
 BUILT = [(64, 4), (62, 2), (64, 1), (90, 3), (96, 2), (90, 1), (128, 4), (120, 2), (128, 1)]
@@ -80,7 +82,10 @@ def test_wider_than_128_stays_out(allow, L):
 
 
 def test_keyword_is_on_every_call_that_takes_it_and_off_by_default():
-    for fn in (CARCA.recommend, CARCA.rank_items, catalogue.recommend, catalogue.rank_items, catalogue.carca_model_side):
+    for fn in (CARCA.recommend, CARCA.rank_items, CARCA.score_items, CARCA.recommend_from, CARCA.score_items_at,
+               CARCA.best_context, CARCA.recommend_at, CARCA.recommend_by_group, CARCA.recommend_capped,
+               CARCA.recommend_users, CARCA.explain_items, CARCA.explain_top_slots, CARCA.recommend_explained,
+               CARCA.recommend_diverse, catalogue.carca_model_side):
         p = inspect.signature(fn).parameters
         assert "allow_composed" in p and p["allow_composed"].default is False, fn
     for fn in (KNN.recommend, KNN.rank_items, catalogue.knn_model_side):
@@ -107,16 +112,33 @@ def test_evaluate_full_passes_the_keyword_only_to_models_that_take_it():
     assert train._wide_envelope(CARCA.__new__(CARCA), "rank_items") == {"allow_composed": True}
 
 
-def test_shared_call_hands_the_keyword_to_the_model_side_only_when_set():
+def test_shared_call_hands_the_keyword_to_the_model_side_only_when_set(monkeypatch):
+    class Reached(Exception):
+        pass
+
     seen = []
 
-    def fill(what, D, **kw):
-        seen.append(kw)
-        return [], None
+    def recording(real):  # the arguments the model side was reached with, bound to its real signature; nothing launches
+        def stub(*a, **kw):
+            seen.append(dict(inspect.signature(real).bind(*a, **kw).arguments))
+            raise Reached
+        return stub
 
-    assert catalogue._fill(fill, "x", None, False) == ([], None) and seen == [{}]
-    catalogue._fill(fill, "x", None, True)
-    assert seen[1] == {"allow_composed": True}
+    monkeypatch.setattr(catalogue, "carca_model_side", recording(catalogue.carca_model_side))
+    monkeypatch.setattr(catalogue, "knn_model_side", recording(catalogue.knn_model_side))
+    prof = (torch.ones(2, 8, dtype=torch.int64), None, torch.zeros(2, 8, 6))
+    ctx = torch.zeros(2, 6)
+    model = build_model(dict(d=64, H=4, n_blocks=1, embedding="all", decoder="ca"), 50, 24, 6, 12, 8).eval()
+    with pytest.raises(Reached):
+        model.recommend(prof, ctx, allow_composed=True)
+    assert seen[0]["allow_composed"] is True and seen[0]["model"] is model and seen[0]["what"] == "recommend"
+    with pytest.raises(Reached):
+        model.recommend(prof, ctx)
+    assert seen[1].get("allow_composed", False) is False
+    knn = KNN()
+    with pytest.raises(Reached):  # (a keyword the baseline's model side does not take would fail the bind)
+        knn.recommend(prof)
+    assert "allow_composed" not in seen[2] and seen[2]["model"] is knn and len(seen) == 3
 
 
 def test_constants_match_the_header():
@@ -130,5 +152,5 @@ def test_constants_match_the_header():
 
 def test_forward_and_the_catalogue_calls_share_one_encoder():
     assert "encode(model" in inspect.getsource(long_profile.forward)
-    assert "long_profile.encode(model" in inspect.getsource(catalogue.carca_model_side)
+    assert "long_profile.encode(model" in inspect.getsource(catalogue._carca_context_free)
     assert "sa_block(" not in inspect.getsource(long_profile.forward)  # (the block loop lives in encode alone)

@@ -23,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_recommend import _batch, _model, _time  # noqa: E402
-from carca_replication_amd import _lib, catalogue  # noqa: E402
+from carca_replication_amd import catalogue  # noqa: E402
 from carca_replication_amd.catalogue import AudienceTopK, CandidateSet  # noqa: E402
 
 C2 = dict(n_items=12102, n_attrs=4096, d=90, g=450, H=3)
@@ -59,7 +59,7 @@ def run(users, items, reps, passes):
                 calls = dict(users=lambda: model.recommend_users(prof, ctx, S, k=k),
                              scoring=lambda: model.recommend(prof, ctx, k=1, candidates=S),
                              aten=aten,
-                             side=lambda: catalogue.carca_model_side(model, prof, ctx, "bench", _lib.RecommendDesc()))
+                             side=lambda: catalogue.carca_model_side(model, prof, ctx, "bench"))
                 r = max(2, reps // 8) if B * Q > 1 << 22 else reps
                 best = {key: float("inf") for key in calls}
                 for _ in range(passes):  # interleaved: a drift of the machine hits them alike

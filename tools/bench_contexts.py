@@ -17,7 +17,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from carca_replication_amd import _lib, catalogue  # noqa: E402
+from carca_replication_amd import catalogue  # noqa: E402
 from carca_replication_amd import modules as M  # noqa: E402
 
 N_ITEMS, N_ATTRS, N_CTX, D, G, H, B, L, K = 12102, 4096, 6, 90, 450, 3, 128, 50, 10
@@ -79,7 +79,7 @@ def run(model, prof, gen, n_c, passes, inner):
     lists = {N: torch.randint(1, N_ITEMS, (B, N), generator=gen).cuda() for N in LIST_SIZES}
 
     def model_side():
-        return catalogue.carca_model_side(model, prof, xs[0], "bench", _lib.ListsDesc())
+        return catalogue.carca_model_side(model, prof, xs[0], "bench")
 
     fns = {"model_side": model_side}
     for N, items in lists.items():

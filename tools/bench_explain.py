@@ -76,9 +76,8 @@ def _summary(ts):
 def aten_top_slots(pkg, model, prof, ctx, items, m):
     """explain_top_slots' outputs composed in ATen from the tensors the call itself stages (catalogue.carca_model_side):
     -> (slots [B, N, m], slot_items [B, N, m], contrib [B, N, m])."""
-    desc = pkg._lib.ListsDesc()
-    keep, _ = pkg.catalogue.carca_model_side(model, prof, ctx, "bench_explain", desc)
-    qt, kk, uu, dq = keep[4], keep[6], keep[7], keep[8]  # T, p_ids, p_n, mc | qt, wt, kk, uu | dq | off
+    side = pkg.catalogue.carca_model_side(model, prof, ctx, "bench_explain")
+    qt, kk, uu, dq = side.qt, side.kk, side.uu, side.dq
     dh = D // H
     p_x = prof[0]
     valid = p_x != 0

@@ -49,8 +49,7 @@ def run(lengths, reps):
             rec = _time(lambda: model.recommend(prof, ctx, k=k, allow_composed=True), n)
             rnk = _time(lambda: model.rank_items(prof, ctx, items, allow_composed=True), n)
             rec2 = _time(lambda: model.recommend(prof, ctx, k=k, allow_composed=True), n)  # (alternated)
-            side = _time(lambda: catalogue.carca_model_side(model, prof, ctx, "bench", _lib.RecommendDesc(),
-                                                            allow_composed=True), n)
+            side = _time(lambda: catalogue.carca_model_side(model, prof, ctx, "bench", allow_composed=True), n)
             rec = min(rec, rec2)
             route = catalogue.carca_route("bench", d, [H, H], L, H, True)
             rows.append(dict(config="C2", L=L, B=B, n_items=n_items, d=d, H=H, k=k, valid_slots=int((p_x != 0).sum()),
