@@ -20,9 +20,9 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip", "recommend_contexts.hip"]
+           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h"]
+           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -441,6 +441,9 @@ SIGNATURES = {
     "carca_rank_items": (_i, [C.POINTER(RankDesc), _fp]),
     "carca_recommend_among": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), _fp]),
     "carca_rank_items_among": (_i, [C.POINTER(RankDesc), C.POINTER(Candidates), _fp]),
+    "carca_retrieve": (_i, [C.POINTER(RecommendDesc), _fp]),
+    "carca_retrieve_among": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), _fp]),
+    "carca_knn_retrieve": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
     "carca_recommend_groups": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _fp]),
     "carca_recommend_capped": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _i, _fp]),
     "carca_recommend_users": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Audience), _fp]),

@@ -12,7 +12,9 @@ items with a group; recommend_by_group / recommend_capped are the top-k of every
 (CARCA.recommend_by_group / recommend_capped).  AudienceTopK / recommend_users turn the question
 round: the k best users of each listed item, kept across batches (CARCA.recommend_users, train.audience; DESIGN.md
 section 24).  score_items_at / best_context / recommend_at serve several request contexts per user from one run of the
-profile side (CARCA.score_items_at / best_context / recommend_at)."""
+profile side (CARCA.score_items_at / best_context / recommend_at).  retrieve is recommend in
+depth, k up to RETRIEVE_KMAX: the first stage those second-stage calls sit behind (CARCA.retrieve, KNN.retrieve; DESIGN.md
+section 26)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -505,10 +507,28 @@ def recommend(what: str, desc, entry: str, model_side: Callable, profile, k: int
     """The top-k call: desc the descriptor class, entry its C entry point, model_side() -> the ModelSide, run after the
     argument checks; candidates: None, or the set the call is restricted to (entry + "_among")."""
     _check_k(what, k)
+    return _topk(what, desc, entry, model_side, profile, k, exclude, candidates)
+
+
+def _topk(what: str, desc, entry: str, model_side: Callable, profile, k: int, exclude, candidates) -> Tuple[Tensor, Tensor]:
+    """What recommend and retrieve do once k has passed: the descriptor, the candidate list, the outputs, the launch."""
     with torch.no_grad():
         D, keep = _topk_desc(what, model_side(), k, exclude, desc)
         cand = _candidates(what, candidates, D, keep, profile[0].device)
         return _launch(what, D, entry, "ids_out", D.k, profile[0].device, cand)
+
+
+RETRIEVE_KMAX = 4096  # largest k of retrieve (csrc: rc::DS_KMAX, the deep selection's LDS key block)
+
+
+def retrieve(what: str, desc, entry: str, model_side: Callable, profile, k: int, exclude,
+             candidates=None) -> Tuple[Tensor, Tensor]:
+    """The deep top-k call: recommend's arguments, contract and launches but the selection, with
+    1 <= k <= RETRIEVE_KMAX; entry: carca_retrieve or carca_knn_retrieve.  k is checked before model_side() runs."""
+    if not 1 <= int(k) <= RETRIEVE_KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{RETRIEVE_KMAX} (the largest k the deep selection keeps is "
+                            f"{RETRIEVE_KMAX})")
+    return _topk(what, desc, entry, model_side, profile, int(k), exclude, candidates)
 
 
 def rank_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, exclude,

@@ -236,7 +236,8 @@ enum { CARCA_TUNE_GEMM_VARIANT = 0, CARCA_TUNE_ATTN_VARIANT = 1, CARCA_TUNE_WGRA
        CARCA_TUNE_FEAT_CACHE = 21,         // 1: the evaluation dedup never uses a per-item cache of P rows (A/B, tests)
        CARCA_TUNE_DEDUP_SOLO = 22,         // 1: every row issues its own compare with its cache entry (ranks taken, unused)
        CARCA_TUNE_SA_LEND = 23,            // 1: the eval SelfAttentionBlock never lends idle workgroups to four-tile users (A/B, tests)
-       CARCA_TUNE_COUNT = 24 };
+       CARCA_TUNE_RETRIEVE_PARTS = 24,     // deep top-k: parts a user's row is split into (0 = the shipped choice; A/B, tests)
+       CARCA_TUNE_COUNT = 25 };
 // Values of key 0 (CARCA_TUNE_GEMM_VARIANT): A/B switches of the row GEMMs, the weight-gradient GEMMs and the gather, one
 // at a time -- which is why 158 exists.  A value with two meanings switches both.
 enum {
@@ -285,7 +286,7 @@ void* carca_stream_scratch(hipStream_t stream, int tag, size_t bytes, size_t zer
 enum { CARCA_SCRATCH_SK = 1, CARCA_SCRATCH_WPART = 2, CARCA_SCRATCH_WTAB = 3, CARCA_SCRATCH_SPLITW = 4, CARCA_SCRATCH_SKC = 5,
        CARCA_SCRATCH_SKC_PART = 6, CARCA_SCRATCH_RECOMMEND = 7, CARCA_SCRATCH_RANK = 8,
        CARCA_SCRATCH_KNN = 9, CARCA_SCRATCH_DEDUP_HASH = 10, CARCA_SCRATCH_DEDUP = 11, CARCA_SCRATCH_SIMILAR = 12,
-       CARCA_SCRATCH_LISTS = 13, CARCA_SCRATCH_GROUPS = 14 };
+       CARCA_SCRATCH_LISTS = 13, CARCA_SCRATCH_GROUPS = 14, CARCA_SCRATCH_RETRIEVE = 15 };
 void* carca_capture_alloc(hipStream_t stream, size_t bytes, bool host_mapped, void** device_view, size_t zero_bytes = 0);
 // Timing events for this thread's NEXT row-GEMM launch (the roofline hooks of carca_forward): the launch binds them to
 // its own dispatch packet (hipExtLaunchKernel), so elapsed(start, stop) is the kernel's duration and no barrier packet

@@ -24,6 +24,7 @@
 // and the same score bits.  Integer atomics only: results do not depend on scheduling.
 #include "catalogue_select.h"
 #include "catalogue_sweep.h"
+#include "deep_select.h"
 #include "row_stream.h"
 
 namespace {
@@ -181,6 +182,31 @@ extern "C" int carca_knn_recommend(const CarcaKnnRecommendDesc* desc, void* stre
                      (int)ld_s, rc::AllItems{});
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
+}
+
+// carca_knn_recommend in depth: the same query, scoring and exclusion launches, so the same logit
+// bits, then the deep selection of deep_select.h in place of rc_select_kernel
+extern "C" int carca_knn_retrieve(const CarcaKnnRecommendDesc* desc, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  CARCA_CHECK_ARG(desc, "knn_retrieve: null descriptor");
+  const CarcaKnnRecommendDesc& D = *desc;
+  int rc = kc_check(D, "knn_retrieve");
+  if (rc != CARCA_OK) return rc;
+  CARCA_CHECK_SUPPORTED(D.k >= 1 && D.k <= rc::DS_KMAX, "knn_retrieve: k = %d outside 1..4096", D.k);
+  CARCA_CHECK_ARG(D.scores && D.ids_out && D.ld_scores >= D.k && D.ld_ids_out >= D.k,
+                  "knn_retrieve: null output or row stride shorter than k");
+  float* logits = nullptr;
+  int64_t ld_s = 0;
+  void* unused = nullptr;
+  rc = kc_score(D, "knn_retrieve", 0, stream, &logits, &ld_s, &unused);
+  if (rc != CARCA_OK) return rc;
+  rc::SelectView S;
+  S.n_items = D.n_items, S.k = D.k, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;
+  S.scores = D.scores, S.ld_scores = D.ld_scores, S.ids_out = D.ids_out, S.ld_ids_out = D.ld_ids_out;
+  hipLaunchKernelGGL(rc::rc_exclude_kernel<rc::SelectView>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s,
+                     rc::AllItems{});
+  CARCA_LAUNCH_CHECK();
+  return rc::ds_select(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, "knn_retrieve", stream);
 }
 
 extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_) {

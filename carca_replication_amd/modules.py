@@ -1374,6 +1374,26 @@ class CARCA(_PackedModule, Model):
                                    self._model_side("recommend", profile, context, allow_composed), profile, k, exclude,
                                    candidates)
 
+    def retrieve(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 1000,
+                 exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
+        """recommend in depth, the first stage in front of a re-ranker, a filter or recommend_from: the k best items per
+        user for 1 <= k <= catalogue.RETRIEVE_KMAX = 4096, (scores [B, k] float32, ids [B, k] int64), best first
+        (DESIGN.md section 26).
+
+        Every argument and the whole contract are recommend's: the order is the raw logit descending with ties to the
+        smaller id (the link is applied to the selected logits only), id 0 and the excluded ids are never returned, fewer
+        than k eligible items pad with id 0 and score 0, `candidates` restricts the call to a set (an empty one gives all
+        zeros; scratch [B, |S|]), allow_composed widens the envelope, and the errors are recommend's under this call's
+        name.  retrieve(k)[:, :j] equals retrieve(j) bit for bit in both outputs for every j <= k, and retrieve(k)
+        equals recommend(k) bit for bit for every k <= 128: scoring and exclusion are recommend's launches, so a
+        returned pair's score has recommend's / score_items' bits.  The result is bit-reproducible and does not depend on
+        how many parts the selection split a user's row into (ops.TUNE_RETRIEVE_PARTS).  ids can go unchanged to
+        recommend_from / score_items / score_items_at as `items` (id 0 scores 0 there)."""
+        self._check_eval_built("retrieve")
+        return catalogue.retrieve("retrieve", _lib.RecommendDesc, "carca_retrieve",
+                                  self._model_side("retrieve", profile, context, allow_composed), profile, k, exclude,
+                                  candidates)
+
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
         """Exact full-catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64).
@@ -1942,6 +1962,15 @@ class KNN(Model):
         eligible items pad with id 0 and score 0.  1 <= k <= 128; any L; train and eval mode alike."""
         return catalogue.recommend("KNN.recommend", _lib.KnnRecommendDesc, "carca_knn_recommend",
                                    lambda: catalogue.knn_model_side(self, profile, "KNN.recommend"), profile, k, exclude)
+
+    def retrieve(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None, k: int = 1000,
+                 exclude="profile") -> Tuple[Tensor, Tensor]:
+        """recommend in depth: the k best items per user for 1 <= k <= catalogue.RETRIEVE_KMAX = 4096, with recommend's
+        arguments, order, exclusion and padding; any L; train and eval mode alike.  retrieve(k)[:, :j] equals retrieve(j)
+        bit for bit, retrieve(k) equals recommend(k) for k <= 128, and the scores are forward's / rank_items' for the
+        returned pairs (CARCA.retrieve)."""
+        return catalogue.retrieve("KNN.retrieve", _lib.KnnRecommendDesc, "carca_knn_retrieve",
+                                  lambda: catalogue.knn_model_side(self, profile, "KNN.retrieve"), profile, k, exclude)
 
     def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
                           k: int = 10, pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile",

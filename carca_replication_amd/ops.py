@@ -1319,6 +1319,7 @@ def feat_dedup_rows_grouped() -> int:
 TUNE_FEAT_CACHE = 21  # 1: the evaluation dedup never uses the per-item cache of P rows (A/B, tests)
 TUNE_DEDUP_SOLO = 22  # 1: under that cache every row compares with its entry itself (A/B, tests); the cache stays on
 TUNE_SA_LEND = 23  # 1: the eval SelfAttentionBlock never lends idle workgroups to four-tile users (A/B, tests)
+TUNE_RETRIEVE_PARTS = 24  # retrieve: parts a user's logit row is split into, 0 = the shipped choice (the same bits; A/B, tests)
 
 
 def sa_eval_lent() -> int:

@@ -109,7 +109,11 @@ int carca_abi_version(void);
  *   key 22 1 = under that cache every row compares its bytes with its entry itself; 0 = one row of up to four of an item
  *          compares for all of them with one read of the entry (the same results; A/B, tests).  Does not switch the cache off
  *   key 23 eval SelfAttentionBlock with two workgroups per user and pads_uniform: 0 = the idle second workgroups of one-tile
- *          users take query tiles of four-tile users, 1 = never (the same bits; A/B, tests) */
+ *          users take query tiles of four-tile users, 1 = never (the same bits; A/B, tests)
+ *   key 24 deep top-k (carca_retrieve / carca_retrieve_among / carca_knn_retrieve): parts S a user's logit row is split
+ *          into for the selection.  0 = the shipped choice; v > 0 forces S = v, clamped to [1, 64] and
+ *          to the row length, and lowered like the shipped choice where the key scratch would pass 1 GiB (the same bits for
+ *          every S; A/B, tests) */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
@@ -961,6 +965,31 @@ typedef struct CarcaCandidates {
 int carca_recommend_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
 int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* candidates, void* stream);
 
+/* ---- deep top-k: the first stage in front of a re-ranker, a business-rule filter or carca_recommend_lists (DESIGN.md
+ * section 26) ----------------------------------------------------------------------------------------------------------
+ * carca_recommend / carca_recommend_among in depth: the descriptor and the candidate list are theirs, every field means
+ * what it means there, and 1 <= k <= 4096.  The contract is carca_recommend's:
+ *   order      best first by RAW LOGIT descending, ties to the smaller id; the link (sigmoid, or (logit + 1) / 2 for
+ *              decoder 2) is applied to the k selected logits only;
+ *   exclusion  id 0 and the nonzero entries of exclude [B, n_exclude] are never returned;
+ *   padding    fewer than k eligible items pad with id 0 and score 0; an empty candidate list gives all zeros;
+ *   prefix     the first j columns of a call with k are the call with j, bit for bit in both outputs, for every j <= k;
+ *              for k <= 128 both outputs are carca_recommend's (carca_recommend_among's) bit for bit;
+ *   scores     a returned pair's score has carca_recommend's / carca_score_lists' bits: scoring and exclusion ARE
+ *              carca_recommend's launches into its [B, n_items] ([B, n] under a list) stream scratch;
+ *   keys       selection orders by the 64-bit key (order-preserving logit bits, then the complemented column); under a
+ *              candidate list the column is the position in the ascending list and ids_out holds ids[position];
+ *   ids_out    int64, usable unchanged as the lists of carca_recommend_lists / carca_score_lists (id 0 scores 0 there).
+ * Selection splits a user's row into S contiguous parts: a launch on grid (B, S) writes each part's min(k, part length)
+ * best keys to [B, S, kp] uint64 of stream scratch (or the capture's memory), a launch on grid (B) takes the k largest of
+ * them, links and writes; S = 1 skips the first launch and selects from the row.  S is chosen from B, the row length and
+ * the CU count (tuning key 24 forces it) and lowered, down to 1, while that scratch would pass 1 GiB -- never an error.
+ * Keys are distinct, so the result is bit-identical run to run and for every S.  Integer LDS atomics only.
+ * Limits and errors as carca_recommend / carca_recommend_among with "retrieve" in the message, and CARCA_ERR_UNSUPPORTED
+ * for k > 4096; CARCA_ERR_BADARG for k < 1 or ld_scores / ld_ids_out < k. */
+int carca_retrieve(const CarcaRecommendDesc* desc, void* stream);
+int carca_retrieve_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
+
 /* ---- item groups: the k best of EVERY group in one call, and the k best overall with at most m per group (a page of
  * carousels; "at most two per brand") ----------------------------------------------------------
  * CarcaItemGroups labels items with one of n_groups groups (category, brand, shelf); an item may carry no label and is
@@ -1239,6 +1268,14 @@ typedef struct CarcaKnnRecommendDesc {
   int ld_ids_out;
 } CarcaKnnRecommendDesc;
 int carca_knn_recommend(const CarcaKnnRecommendDesc* desc, void* stream);
+/* carca_knn_retrieve: carca_knn_recommend in depth, 1 <= k <= 4096, with carca_retrieve's contract (above): the order is
+ * logit descending with ties to the smaller id, id 0 and the excluded ids are never returned, fewer than k eligible items
+ * pad with id 0 and score 0; the first j columns of a call with k are the call with j bit for bit, and for k <= 128 both
+ * outputs are carca_knn_recommend's; scores = the logits, with carca_knn_recommend's / carca_knn_rank_items' bits (the
+ * query, scoring and exclusion launches are carca_knn_recommend's); keys are (order bits, complemented id); ids_out is
+ * int64.  Selection is carca_retrieve's two launches (one where S = 1), bit-identical for every S and run to run.
+ * Errors as carca_knn_recommend, with CARCA_ERR_UNSUPPORTED for k outside 1..4096. */
+int carca_knn_retrieve(const CarcaKnnRecommendDesc* desc, void* stream);
 
 /* carca_knn_rank_items: for user u and list entry j, with id = items[u][j]:
  *   ranks[u][j]  = number of ELIGIBLE items (id != 0, not excluded) that order strictly before id in
