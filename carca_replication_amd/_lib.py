@@ -20,9 +20,10 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip"]
+           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
-           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h"]
+           "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h",
+           "sampled_select.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -274,6 +275,12 @@ class Candidates(C.Structure):
     _fields_ = [("ids", _fp), ("n", C.c_int32)]
 
 
+class Sampling(C.Structure):
+    """CarcaSampling (carca_recommend_sampled / carca_knn_recommend_sampled)."""
+    _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64), ("user_keys", _fp), ("log_probs", _fp),
+                ("ld_log_probs", C.c_int32)]
+
+
 class Contexts(C.Structure):
     """CarcaContexts (carca_score_lists_at / carca_recommend_at / carca_recommend_among_at)."""
     _fields_ = [("n_contexts", C.c_int32), ("user_q", _fp), ("ld_user_q", C.c_int32), ("user_off", _fp),
@@ -444,6 +451,9 @@ SIGNATURES = {
     "carca_retrieve": (_i, [C.POINTER(RecommendDesc), _fp]),
     "carca_retrieve_among": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), _fp]),
     "carca_knn_retrieve": (_i, [C.POINTER(KnnRecommendDesc), _fp]),
+    "carca_recommend_sampled": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Sampling), _fp]),
+    "carca_sampled_perturb": (_i, [_fp, _fp, _fp, _i, _i, C.POINTER(Sampling), _fp]),
+    "carca_knn_recommend_sampled": (_i, [C.POINTER(KnnRecommendDesc), C.POINTER(Candidates), C.POINTER(Sampling), _fp]),
     "carca_recommend_groups": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _fp]),
     "carca_recommend_capped": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _i, _fp]),
     "carca_recommend_users": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Audience), _fp]),

@@ -14,7 +14,9 @@ round: the k best users of each listed item, kept across batches (CARCA.recommen
 section 24).  score_items_at / best_context / recommend_at serve several request contexts per user from one run of the
 profile side (CARCA.score_items_at / best_context / recommend_at).  retrieve is recommend in
 depth, k up to RETRIEVE_KMAX: the first stage those second-stage calls sit behind (CARCA.retrieve, KNN.retrieve; DESIGN.md
-section 26)."""
+section 26).  recommend_sampled draws the list instead of sorting it -- Gumbel top-k over softmax(logit / temperature),
+with each drawn item's log-probability -- and plackett_luce_log_prob turns those into the list's conditional
+log-probabilities (CARCA.recommend_sampled, KNN.recommend_sampled)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -529,6 +531,81 @@ def retrieve(what: str, desc, entry: str, model_side: Callable, profile, k: int,
         raise CarcaHipError(f"{what}: k = {k} outside 1..{RETRIEVE_KMAX} (the largest k the deep selection keeps is "
                             f"{RETRIEVE_KMAX})")
     return _topk(what, desc, entry, model_side, profile, int(k), exclude, candidates)
+
+
+# ---- Gumbel top-k sampling with logged propensities (include/carca_hip.h: CarcaSampling) ---------
+FLT_MIN = 2.0 ** -126  # the smallest normal fp32 number: the smallest temperature (csrc: sp_check)
+
+
+def sampled_args(what: str, profile, k: int, temperature, seed, user_keys) -> Tuple[int, float, int]:
+    """The checks of recommend_sampled's own arguments, before any device work: -> (k, temperature, seed mod 2^64).
+    temperature must be a finite float that is a normal positive number as fp32 (FLT_MIN <= t < inf); seed an int, or None: drawn from torch's CPU generator
+    as the dropout seed is (ops.new_dropout_seed), so torch.manual_seed makes a call sequence reproducible; user_keys None
+    or an int [B] tensor."""
+    if not 1 <= int(k) <= RETRIEVE_KMAX:
+        raise CarcaHipError(f"{what}: k = {k} outside 1..{RETRIEVE_KMAX} (the largest k the deep selection keeps is "
+                            f"{RETRIEVE_KMAX})")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+        raise CarcaHipError(f"{what}: temperature must be a finite float > 0, got {temperature!r}")
+    t32 = C.c_float(float(temperature)).value  # (what the kernels divide by)
+    if not (math.isfinite(t32) and t32 >= FLT_MIN):  # (a denormal would take logit / temperature to +-inf)
+        raise CarcaHipError(f"{what}: temperature must be a finite float > 0, a normal fp32 number (>= {FLT_MIN:.3e}), "
+                            f"got {temperature!r}")
+    if seed is None:
+        seed = ops.new_dropout_seed()
+    elif isinstance(seed, bool) or not isinstance(seed, int):
+        raise CarcaHipError(f"{what}: seed must be an int or None, got {seed!r}")
+    if user_keys is not None:
+        B = profile[0].shape[0]
+        if not isinstance(user_keys, Tensor) or user_keys.is_floating_point() or user_keys.is_complex() or \
+                user_keys.dtype == torch.bool or tuple(user_keys.shape) != (B,):
+            raise CarcaHipError(f"{what}: user_keys must be None or an int [B] tensor with B = {B}")
+    return int(k), t32, int(seed) % (1 << 64)
+
+
+def recommend_sampled(what: str, desc, entry: str, model_side: Callable, profile, k: int, temperature, seed, user_keys,
+                      exclude, candidates=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The sampling call: recommend's arguments and eligibility, the list drawn without replacement
+    from softmax(logit / temperature) by Gumbel top-k: -> (scores [B, k] float32, ids [B, k] int64, log_probs [B, k]
+    float32).  entry: carca_recommend_sampled or carca_knn_recommend_sampled (both take a nullable candidate list).  Every
+    argument of its own is checked (sampled_args) before model_side() runs."""
+    k, t32, seed = sampled_args(what, profile, k, temperature, seed, user_keys)
+    with torch.no_grad():
+        D, keep = _topk_desc(what, model_side(), k, exclude, desc)
+        device = profile[0].device
+        cand = _candidates(what, candidates, D, keep, device)
+        X = _lib.Sampling(temperature=t32, seed=seed)
+        if user_keys is not None:
+            ops._need_cuda(user_keys)
+            keys = user_keys.to(torch.int64).contiguous()
+            keep.append(keys)
+            X.user_keys = keys.data_ptr()
+        scores, ids = _outputs(D, "ids_out", (D.B, k), device)
+        log_probs = torch.empty(D.B, k, dtype=torch.float32, device=device)
+        X.log_probs, X.ld_log_probs = log_probs.data_ptr(), k
+        rc = getattr(_lib.load(), entry)(C.byref(D), C.byref(cand) if cand is not None else None, C.byref(X), ops._stream())
+        _lib.check(rc, what)
+        return scores, ids, log_probs
+
+
+def plackett_luce_log_prob(log_probs: Tensor) -> Tensor:
+    """recommend_sampled's log_probs [B, k] -> the conditional log-probabilities [B, k] (float64) of the ordered list drawn
+    without replacement: out[:, j] = lp_j - log1p(-sum_{m<j} exp(lp_m)), the log-probability of item j among the items
+    that the first j draws left; out.sum(1) is the Plackett-Luce log-probability of the list.  Padding (-inf) stays -inf.
+    Torch ops in float64 on the input's device; not a kernel.
+
+    Cancellation: 1 - sum_{m<j} exp(lp_m) is the mass that is left, computed from fp32 log_probs whose absolute error is
+    about 1e-6 at best.  When the drawn head holds nearly all the mass -- a cold temperature, or k close to the eligible
+    count -- that difference loses its leading digits: with a remaining mass r the result's error grows like 1e-6 / r,
+    and once the rounded head sums to 1 or more the remainder clamps at 0 and the entry is +inf (-inf where lp_j is
+    itself -inf).  Trust column j only while the head's mass stays well below 1."""
+    if not isinstance(log_probs, Tensor) or log_probs.dim() != 2 or not log_probs.is_floating_point():
+        raise CarcaHipError("plackett_luce_log_prob: log_probs must be a float [B, k] tensor")
+    lp = log_probs.to(torch.float64)
+    p = torch.exp(lp)
+    head = torch.cumsum(p, dim=1) - p  # sum_{m<j} exp(lp_m)
+    out = lp - torch.log1p(-head.clamp(max=1.0))
+    return torch.where(torch.isneginf(lp), lp, out)
 
 
 def rank_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, exclude,

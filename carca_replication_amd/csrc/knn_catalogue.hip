@@ -26,6 +26,7 @@
 #include "catalogue_sweep.h"
 #include "deep_select.h"
 #include "row_stream.h"
+#include "sampled_select.h"
 
 namespace {
 
@@ -207,6 +208,38 @@ extern "C" int carca_knn_retrieve(const CarcaKnnRecommendDesc* desc, void* strea
                      rc::AllItems{});
   CARCA_LAUNCH_CHECK();
   return rc::ds_select(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, "knn_retrieve", stream);
+}
+
+// carca_knn_recommend drawn instead of sorted: the same query, scoring and exclusion launches, so
+// the same logit bits, then sampled_select.h's perturb pass, deep selection and finishing launch with no link.  The
+// buffer's columns are item ids; a candidate list strikes the items outside it out in the perturb pass.
+extern "C" int carca_knn_recommend_sampled(const CarcaKnnRecommendDesc* desc, const CarcaCandidates* cand,
+                                           const CarcaSampling* sampling, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  CARCA_CHECK_ARG(desc, "knn_recommend_sampled: null descriptor");
+  const CarcaKnnRecommendDesc& D = *desc;
+  int rc = kc_check(D, "knn_recommend_sampled");
+  if (rc != CARCA_OK) return rc;
+  CARCA_CHECK_SUPPORTED(D.k >= 1 && D.k <= rc::DS_KMAX, "knn_recommend_sampled: k = %d outside 1..4096", D.k);
+  CARCA_CHECK_ARG(D.scores && D.ids_out && D.ld_scores >= D.k && D.ld_ids_out >= D.k,
+                  "knn_recommend_sampled: null output or row stride shorter than k");
+  if ((rc = rc::sp_check(sampling, D.k, "knn_recommend_sampled")) != CARCA_OK) return rc;
+  if (cand && (rc = rc::check_candidates(cand, "knn_recommend_sampled")) != CARCA_OK) return rc;
+  float* logits = nullptr;
+  int64_t ld_s = 0;
+  void* unused = nullptr;
+  rc = kc_score(D, "knn_recommend_sampled", 0, stream, &logits, &ld_s, &unused);
+  if (rc != CARCA_OK) return rc;
+  rc::SelectView S;
+  S.n_items = D.n_items, S.k = D.k, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;
+  S.scores = D.scores, S.ld_scores = D.ld_scores, S.ids_out = D.ids_out, S.ld_ids_out = D.ld_ids_out;
+  hipLaunchKernelGGL(rc::rc_exclude_kernel<rc::SelectView>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s,
+                     rc::AllItems{});
+  CARCA_LAUNCH_CHECK();
+  if (cand)
+    return rc::sp_run(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, rc::SpKeepListed{rc::ListedItems{cand->ids, cand->n}},
+                      *sampling, "knn_recommend_sampled", stream);
+  return rc::sp_run(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, rc::SpKeepAll{}, *sampling, "knn_recommend_sampled", stream);
 }
 
 extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_) {

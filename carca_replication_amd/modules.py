@@ -1394,6 +1394,34 @@ class CARCA(_PackedModule, Model):
                                   self._model_side("retrieve", profile, context, allow_composed), profile, k, exclude,
                                   candidates)
 
+    def recommend_sampled(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], k: int = 10,
+                          temperature: float = 1.0, seed: Optional[int] = None, user_keys: Optional[Tensor] = None,
+                          exclude="profile", candidates=None,
+                          allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """recommend with exploration and logged propensities: per user, k items drawn WITHOUT
+        replacement from softmax(logit / temperature) over the eligible items -- a Plackett-Luce list, in draw order --
+        as (scores [B, k] float32, ids [B, k] int64, log_probs [B, k] float32), 1 <= k <= catalogue.RETRIEVE_KMAX.
+
+        Eligibility, exclude, candidates, allow_composed and the envelope are recommend's.  scores[u, j] is
+        link(raw logit), bit for bit what score_items / recommend return for that pair.  log_probs[u, j] =
+        logit / temperature - logsumexp over user u's eligible items: the item's first-draw log-probability, the
+        pi(a | x) of an IPS or doubly-robust estimator; catalogue.plackett_luce_log_prob(log_probs) gives the conditional
+        log-probabilities of the ordered list.  Rows with fewer than k eligible items pad with (0, 0, -inf).
+
+        The draw is Gumbel top-k: the k largest of logit / temperature + g, g iid standard Gumbel hashed from (seed, the
+        user's key, the item id) -- include/carca_hip.h states the hash.  seed: an int (mod 2^64), or None: one from
+        torch's CPU generator (torch.manual_seed makes the sequence reproducible).  user_keys: None (row u's key is u) or
+        an int [B] tensor, e.g. user or request ids.  So: the same arguments and seed give the same bits;
+        recommend_sampled(k)[:, :j] equals recommend_sampled(j); a row depends on (seed, its key, its profile, context
+        and exclusion) only, not on the batch around it; under candidates=S the result is the unrestricted perturbed
+        order with the items outside S struck out.  temperature must be a finite float > 0 and a normal fp32 number (>= 1.18e-38); as
+        it falls the list approaches recommend's.  The noise has 23 bits: an item more than 19.4 in logit / temperature below the user's
+        best is never drawn ahead of it.  Scratch: a second [B, n_items] fp32 buffer beside recommend's."""
+        self._check_eval_built("recommend_sampled")
+        return catalogue.recommend_sampled("recommend_sampled", _lib.RecommendDesc, "carca_recommend_sampled",
+                                           self._model_side("recommend_sampled", profile, context, allow_composed),
+                                           profile, k, temperature, seed, user_keys, exclude, candidates)
+
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
         """Exact full-catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64).
@@ -1971,6 +1999,20 @@ class KNN(Model):
         returned pairs (CARCA.retrieve)."""
         return catalogue.retrieve("KNN.retrieve", _lib.KnnRecommendDesc, "carca_knn_retrieve",
                                   lambda: catalogue.knn_model_side(self, profile, "KNN.retrieve"), profile, k, exclude)
+
+    def recommend_sampled(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
+                          k: int = 10, temperature: float = 1.0, seed: Optional[int] = None,
+                          user_keys: Optional[Tensor] = None, exclude="profile",
+                          candidates=None) -> Tuple[Tensor, Tensor, Tensor]:
+        """CARCA.recommend_sampled for the baseline: k items per user drawn without replacement from
+        softmax(score / temperature) over the eligible rows of the registered table, (scores [B, k], ids [B, k],
+        log_probs [B, k]), 1 <= k <= catalogue.RETRIEVE_KMAX, with its noise contract, seed, user_keys, padding and
+        properties.  scores are KNN.recommend's raw dot products for the returned pairs, bit for
+        bit; exclude is KNN.recommend's; candidates (None, a catalogue.CandidateSet or a 1-D id tensor / bool mask)
+        strikes out every other item -- the whole catalogue is still scored.  Any L; train and eval mode alike."""
+        return catalogue.recommend_sampled("KNN.recommend_sampled", _lib.KnnRecommendDesc, "carca_knn_recommend_sampled",
+                                           lambda: catalogue.knn_model_side(self, profile, "KNN.recommend_sampled"),
+                                           profile, k, temperature, seed, user_keys, exclude, candidates)
 
     def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
                           k: int = 10, pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile",

@@ -113,7 +113,8 @@ int carca_abi_version(void);
  *   key 24 deep top-k (carca_retrieve / carca_retrieve_among / carca_knn_retrieve): parts S a user's logit row is split
  *          into for the selection.  0 = the shipped choice; v > 0 forces S = v, clamped to [1, 64] and
  *          to the row length, and lowered like the shipped choice where the key scratch would pass 1 GiB (the same bits for
- *          every S; A/B, tests) */
+ *          every S; A/B, tests).  carca_recommend_sampled / carca_knn_recommend_sampled run that selection, and a forced
+ *          value also forces the parts of their perturb pass (clamped to [1, 1024] and to a chunk per wave): the same bits */
 int carca_set_tuning(int key, int value);
 /* Deterministic mode, per backward pass: register the pass's flat fp32 gradient buffer `flat` (n floats) and its shadow
  * (n uint64, ZERO on entry); kernels launched on `stream` afterwards accumulate gradients that land inside `flat` into
@@ -990,6 +991,63 @@ int carca_rank_items_among(const CarcaRankDesc* desc, const CarcaCandidates* can
 int carca_retrieve(const CarcaRecommendDesc* desc, void* stream);
 int carca_retrieve_among(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates, void* stream);
 
+/* ---- Gumbel top-k sampling with logged propensities: exploration, and the pi(a | x) of an off-policy estimator
+ *  -----------------------------------------------------------------------------------------------
+ * carca_recommend_sampled draws, per user, k items WITHOUT replacement from softmax(logit / temperature) over the user's
+ * eligible items -- a Plackett-Luce list -- and returns each drawn item's log-probability under that softmax.  The
+ * descriptor and the (nullable) candidate list are carca_retrieve's, 1 <= k <= 4096; eligibility is carca_recommend's
+ * (id != 0, not in exclude, inside the candidate list when one is given).  With z = logit / temperature (one fp32
+ * division) and g the noise below:
+ *   ids_out    the k eligible items with the largest z + g, largest first, ties in z + g to the smaller id (the keys of
+ *              carca_retrieve's selection over the perturbed values); fewer than k eligible items pad with id 0;
+ *   scores     link(raw logit) of the pair, bit for bit carca_recommend's / carca_score_lists': scoring and exclusion ARE
+ *              carca_recommend's launches, and the perturb pass only reads their buffer; padding scores 0;
+ *   log_probs  z - logsumexp(z over the user's eligible items): the item's first-draw log-probability; padding is -inf.
+ *              The conditional log-probabilities of the ordered list follow on the host: lp_j - log1p(-sum_{m<j} exp(lp_m)).
+ * NOISE CONTRACT.  g is a function of (seed, user key, item id) alone -- never of the column (under a candidate list the
+ * id is ids[position]), the batch row, the batch size or any launch shape.  User u's key is user_keys[u], or u when
+ * user_keys is NULL.  Every variable below is a 32-bit unsigned, arithmetic mod 2^32; seed and key are 64 bits (the key
+ * an int64 reinterpreted), _lo = bits 0..31, _hi = bits 32..63:
+ *   mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   hu = mix32( seed_lo ^ (key_lo * 0x9E3779B1) )
+ *   hu = mix32( hu ^ seed_hi ^ (key_hi * 0x85EBCA77) )
+ *   h  = mix32( hu ^ (item * 0xC2B2AE3D) )
+ *   U  = ((h >> 9) + 0.5) * 2^-23          exact in fp32; 23 hash bits reach U
+ *   g  = -log(-log(U))                      fp32
+ * U lies in [2^-24, 1 - 2^-24], strictly inside (0, 1) for every h, so g is finite for every element: g ranges over
+ * [g_min, g_max] = [-log(24 log 2), -log(-log(1 - 2^-24))] = [-2.8116, 16.6355].  The resolution bounds what can be drawn:
+ * an item whose z lies more than g_max - g_min = 19.447 below the user's best z (softmax odds against the best item
+ * below exp(-19.447) = 3.6e-9) is never drawn ahead of it.  A perturbed value is clamped to the finite fp32 range, so it
+ * never carries the exclusion sentinel's bits.
+ * Consequences: the same arguments and seed give the same bits; the first j columns of a call with k are the call with
+ * j; a user's row depends on (seed, its key, its model-side rows and exclusion) only, not on the batch it sits in; under
+ * a candidate list S the result is the unrestricted perturbed order with the items outside S struck out; no split of
+ * the selection or of the perturb pass changes a bit (logsumexp is summed per fixed 1024-column chunk in 64-bit fixed
+ * point and merged in a fixed shape).  No atomics.
+ * Launches behind carca_recommend's scoring and exclusion: the perturb pass on grid (B, S), carca_retrieve's selection,
+ * a finishing launch on grid (B).  Stream scratch (or the capture's memory): a SECOND [B, n_items] ([B, n] under a list)
+ * fp32 buffer beside carca_recommend's, plus 8 bytes per user and 1024 columns -- 512 MB more at 1 M items x 128 users.
+ * Errors as carca_retrieve with "recommend_sampled" in the message; CARCA_ERR_BADARG also for a null sampling block, a
+ * temperature that is not a finite, positive, normal fp32 number (below FLT_MIN = 1.18e-38 the division would overflow),
+ * null log_probs or ld_log_probs < k. */
+typedef struct CarcaSampling {
+  float temperature;         /* finite, >= FLT_MIN */
+  uint64_t seed;
+  const int64_t* user_keys;  /* [B] on the device, or NULL: user u's key is u */
+  float* log_probs;          /* [B, ld_log_probs], first k columns written */
+  int ld_log_probs;
+} CarcaSampling;
+int carca_recommend_sampled(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates /* nullable */,
+                            const CarcaSampling* sampling, void* stream);
+/* The perturb pass of carca_recommend_sampled alone, over buffers the caller holds (a measurement hook: tools/
+ * bench_sampled.py times it against its bytes): perturbed[u][i] = logits[u][i] / temperature + g(seed, key of u, item i), the
+ * exclusion sentinel (bits 0xFFFFFFFF) copied through, and per user and 1024-column chunk (max z, sum exp(z - max)) over the
+ * other columns into partials.  logits, perturbed: [B, n_slots] fp32 with row stride n_slots, 16-byte aligned; partials:
+ * [B, ceil(n_slots / 1024), 2] fp32.  Of the sampling block temperature, seed and user_keys are read.  CARCA_ERR_BADARG for
+ * null pointers, B or n_slots < 1, a bad temperature or a misaligned buffer. */
+int carca_sampled_perturb(const float* logits, float* perturbed, float* partials, int B, int n_slots,
+                          const CarcaSampling* sampling, void* stream);
+
 /* ---- item groups: the k best of EVERY group in one call, and the k best overall with at most m per group (a page of
  * carousels; "at most two per brand") ----------------------------------------------------------
  * CarcaItemGroups labels items with one of n_groups groups (category, brand, shelf); an item may carry no label and is
@@ -1276,6 +1334,12 @@ int carca_knn_recommend(const CarcaKnnRecommendDesc* desc, void* stream);
  * int64.  Selection is carca_retrieve's two launches (one where S = 1), bit-identical for every S and run to run.
  * Errors as carca_knn_recommend, with CARCA_ERR_UNSUPPORTED for k outside 1..4096. */
 int carca_knn_retrieve(const CarcaKnnRecommendDesc* desc, void* stream);
+/* carca_knn_recommend_sampled: carca_recommend_sampled (above) over the KNN descriptor, 1 <= k <= 4096: the query, scoring
+ * and exclusion launches are carca_knn_recommend's, scores = the raw logits with its bits (no link), and the noise
+ * contract, log_probs, padding and consequences are carca_recommend_sampled's.  The logit buffer's columns are item ids;
+ * a (nullable) candidate list strikes the items outside it out in the perturb pass, so time and scratch follow n_items. */
+int carca_knn_recommend_sampled(const CarcaKnnRecommendDesc* desc, const CarcaCandidates* candidates /* nullable */,
+                                const CarcaSampling* sampling, void* stream);
 
 /* carca_knn_rank_items: for user u and list entry j, with id = items[u][j]:
  *   ranks[u][j]  = number of ELIGIBLE items (id != 0, not excluded) that order strictly before id in
