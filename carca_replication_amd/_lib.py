@@ -20,10 +20,10 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip"]
+           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip", "policy_items.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h",
-           "sampled_select.h"]
+           "sampled_select.h", "policy_items.h"]
 
 MAX_SEGS = 4
 MAX_GROUPS = 3
@@ -319,6 +319,12 @@ class CatalogueXentDesc(C.Structure):
                 ("row_loss", _fp), ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dT", _fp)]
 
 
+class PolicyItems(C.Structure):
+    """CarcaPolicyItems (carca_log_prob_items / carca_knn_log_prob_items)."""
+    _fields_ = [("temperature", C.c_float), ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32),
+                ("log_probs", _fp), ("ld_log_probs", C.c_int32), ("lse", _fp), ("entropy", _fp)]
+
+
 class SampledXentDesc(C.Structure):
     """CarcaSampledXentDesc (carca_sampled_xent_fwd / _bwd)."""
     _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp),
@@ -454,6 +460,9 @@ SIGNATURES = {
     "carca_recommend_sampled": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Sampling), _fp]),
     "carca_sampled_perturb": (_i, [_fp, _fp, _fp, _i, _i, C.POINTER(Sampling), _fp]),
     "carca_knn_recommend_sampled": (_i, [C.POINTER(KnnRecommendDesc), C.POINTER(Candidates), C.POINTER(Sampling), _fp]),
+    "carca_log_prob_items": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(PolicyItems), _fp]),
+    "carca_policy_reduce": (_i, [_fp, _fp, _i, _i, _f, _fp]),
+    "carca_knn_log_prob_items": (_i, [C.POINTER(KnnRecommendDesc), C.POINTER(Candidates), C.POINTER(PolicyItems), _fp]),
     "carca_recommend_groups": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _fp]),
     "carca_recommend_capped": (_i, [C.POINTER(RecommendDesc), C.POINTER(ItemGroups), _i, _fp]),
     "carca_recommend_users": (_i, [C.POINTER(RecommendDesc), C.POINTER(Candidates), C.POINTER(Audience), _fp]),

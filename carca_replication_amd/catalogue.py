@@ -608,6 +608,133 @@ def plackett_luce_log_prob(log_probs: Tensor) -> Tensor:
     return torch.where(torch.isneginf(lp), lp, out)
 
 
+# ---- a policy's log-probabilities for logged items (include/carca_hip.h: CarcaPolicyItems) -------
+def policy_args(what: str, profile, items, temperature) -> float:
+    """The checks of log_prob_items' own arguments, before any device work: -> the temperature as the fp32 value the
+    kernels divide by.  temperature as sampled_args asks: a finite float that is a normal positive number as fp32; items
+    an int [B, N] tensor, N >= 0."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+        raise CarcaHipError(f"{what}: temperature must be a finite float > 0, got {temperature!r}")
+    t32 = C.c_float(float(temperature)).value
+    if not (math.isfinite(t32) and t32 >= FLT_MIN):  # (a denormal would take logit / temperature to +-inf)
+        raise CarcaHipError(f"{what}: temperature must be a finite float > 0, a normal fp32 number (>= {FLT_MIN:.3e}), "
+                            f"got {temperature!r}")
+    B = profile[0].shape[0]
+    if not isinstance(items, Tensor) or items.dim() != 2 or items.is_floating_point() or items.is_complex() or \
+            items.dtype == torch.bool or items.shape[0] != B:
+        raise CarcaHipError(f"{what}: items must be an int [B, N] tensor, one row per user, with B = {B}")
+    return t32
+
+
+def log_prob_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, temperature, exclude,
+                   candidates=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The policy call: recommend_sampled's arguments and eligibility with a list per user in place
+    of the draw: -> (log_probs [B, N] float32, lse [B] float32, entropy [B] float32).  entry: carca_log_prob_items or
+    carca_knn_log_prob_items (both take a nullable candidate list).  The ids go to the kernel as int64, so no id wraps
+    into range.  Every argument of its own is checked (policy_args) before model_side() runs."""
+    t32 = policy_args(what, profile, items, temperature)
+    with torch.no_grad():
+        D, keep = _topk_desc(what, model_side(), 0, exclude, desc)
+        device = profile[0].device
+        cand = _candidates(what, candidates, D, keep, device)
+        ops._need_cuda(items)
+        N = items.shape[1]
+        lst = items.to(torch.int64).contiguous()
+        log_probs = torch.empty(D.B, N, dtype=torch.float32, device=device)
+        lse = torch.empty(D.B, dtype=torch.float32, device=device)
+        entropy = torch.empty(D.B, dtype=torch.float32, device=device)
+        X = _lib.PolicyItems(temperature=t32, items=lst.data_ptr() if N else None, n_list=N, ld_items=N,
+                             log_probs=log_probs.data_ptr() if N else None, ld_log_probs=N, lse=lse.data_ptr(),
+                             entropy=entropy.data_ptr())
+        rc = getattr(_lib.load(), entry)(C.byref(D), C.byref(cand) if cand is not None else None, C.byref(X), ops._stream())
+        _lib.check(rc, what)
+        return log_probs, lse, entropy
+
+
+def policy_log_ratio(target_log_probs: Tensor, logged_log_probs: Tensor, mode: str = "first") -> Tensor:
+    """log(pi_target / pi_logged) per logged row, [B] float64: the log of an importance weight.  target_log_probs: what
+    log_prob_items returned for the logged ids under the policy being evaluated; logged_log_probs: what
+    recommend_sampled logged; both [B, k].
+
+    mode "first" takes column 0, the first draw -- the only position whose logged value is a true marginal (a later
+    item's first-draw probability is not the probability that it was drawn there).  mode "list" takes the Plackett-Luce
+    log-probability of the ordered list, plackett_luce_log_prob(.) summed over the columns that are not padding (-inf) in
+    the LOGGED row, on either side; its cancellation caveat applies.
+
+    A -inf target where the log is finite gives -inf: the target policy never takes that action, weight 0.  A finite
+    target where the log says -inf raises: the logging policy cannot have drawn it (the log and the target disagree on
+    eligibility -- another exclude or candidates).  The check is the function's one host sync.  Torch ops in float64 on
+    the input's device; not a kernel."""
+    ratio, bad = _policy_log_ratio(target_log_probs, logged_log_probs, mode)
+    if bool(bad):
+        raise CarcaHipError(_RATIO_UNDRAWN)
+    return ratio
+
+
+_RATIO_UNDRAWN = ("policy_log_ratio: a logged log-probability is -inf where the target's is finite: the logging policy "
+                  "cannot have drawn that item (the log and the target disagree on eligibility)")
+
+
+def _policy_log_ratio(target_log_probs: Tensor, logged_log_probs: Tensor, mode: str) -> Tuple[Tensor, Tensor]:
+    """policy_log_ratio without its host sync: -> (the ratio [B] float64; a 0-d bool tensor, true where the raising case
+    occurred, for the caller to test when it syncs)."""
+    for name, t in (("target_log_probs", target_log_probs), ("logged_log_probs", logged_log_probs)):
+        if not isinstance(t, Tensor) or t.dim() != 2 or not t.is_floating_point():
+            raise CarcaHipError(f"policy_log_ratio: {name} must be a float [B, k] tensor")
+    if target_log_probs.shape != logged_log_probs.shape:
+        raise CarcaHipError(f"policy_log_ratio: shapes differ: target {tuple(target_log_probs.shape)}, logged "
+                            f"{tuple(logged_log_probs.shape)}")
+    if mode not in ("first", "list"):
+        raise CarcaHipError(f'policy_log_ratio: mode must be "first" or "list", got {mode!r}')
+    if target_log_probs.shape[1] < 1:
+        raise CarcaHipError("policy_log_ratio: k = 0: no logged action")
+    tgt, log = target_log_probs.to(torch.float64), logged_log_probs.to(torch.float64)
+    if mode == "first":
+        tgt, log = tgt[:, :1], log[:, :1]
+    pad = torch.isneginf(log)
+    bad = (pad & ~torch.isneginf(tgt)).any()
+    if mode == "list":
+        tgt, log = plackett_luce_log_prob(tgt), plackett_luce_log_prob(log)
+    zero = torch.zeros((), dtype=torch.float64, device=log.device)
+    return (torch.where(pad, zero, tgt) - torch.where(pad, zero, log)).sum(1), bad
+
+
+def _off_policy_sums(log_ratio: Tensor, rewards: Tensor, clip) -> Tensor:
+    """[sum w r, sum w, sum w^2, max w, n] float64 on the input's device, w = min(exp(log_ratio), clip)."""
+    if not isinstance(log_ratio, Tensor) or log_ratio.dim() != 1 or not isinstance(rewards, Tensor) or \
+            rewards.shape != log_ratio.shape:
+        raise CarcaHipError("off_policy_estimate: log_ratio and rewards must be [B] tensors of one shape")
+    if clip is not None and not (isinstance(clip, (int, float)) and not isinstance(clip, bool) and clip > 0):
+        raise CarcaHipError(f"off_policy_estimate: clip must be None or a number > 0, got {clip!r}")
+    w = torch.exp(log_ratio.to(torch.float64))
+    if clip is not None:
+        w = w.clamp(max=float(clip))
+    r = rewards.to(device=w.device, dtype=torch.float64)
+    n = torch.full((), float(w.shape[0]), dtype=torch.float64, device=w.device)
+    peak = w.max() if w.shape[0] else torch.zeros((), dtype=torch.float64, device=w.device)
+    return torch.stack([(w * r).sum(), w.sum(), (w * w).sum(), peak, n])
+
+
+def _off_policy_result(sums: Tensor, clip) -> dict:
+    wr, w1, w2, peak, n = sums.unbind(0)
+    return dict(ips=wr / n, snips=wr / w1, ess=w1 * w1 / w2, max_weight=peak, n=n, clip=clip)
+
+
+def off_policy_estimate(log_ratio: Tensor, rewards: Tensor, clip: Optional[float] = None) -> dict:
+    """Inverse-propensity estimates of a target policy's value from logged rewards.  log_ratio [B]: policy_log_ratio's
+    log weights; rewards [B]: the reward each logged row earned; w = exp(log_ratio), capped from above at clip when one is
+    given (bias for variance).  -> dict of 0-d float64 tensors on log_ratio's device -- nothing is synced; the caller
+    decides when -- and the clip:
+      ips         mean of w r: unbiased when the logging policy covers the target's support and clip is None;
+      snips       sum w r / sum w, the self-normalised estimate: biased, consistent, bounded by the rewards' range;
+      ess         (sum w)^2 / sum w^2, the effective sample size: n when every weight is 1;
+      max_weight  the largest (clipped) weight;
+      n           the number of rows;
+      clip        as given.
+    No rows, or weights that are all 0, give nan where the formula divides by zero."""
+    return _off_policy_result(_off_policy_sums(log_ratio, rewards, clip), clip)
+
+
 def rank_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, exclude,
                candidates=None) -> Tuple[Tensor, Tensor]:
     """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""

@@ -287,7 +287,7 @@ enum { CARCA_SCRATCH_SK = 1, CARCA_SCRATCH_WPART = 2, CARCA_SCRATCH_WTAB = 3, CA
        CARCA_SCRATCH_SKC_PART = 6, CARCA_SCRATCH_RECOMMEND = 7, CARCA_SCRATCH_RANK = 8,
        CARCA_SCRATCH_KNN = 9, CARCA_SCRATCH_DEDUP_HASH = 10, CARCA_SCRATCH_DEDUP = 11, CARCA_SCRATCH_SIMILAR = 12,
        CARCA_SCRATCH_LISTS = 13, CARCA_SCRATCH_GROUPS = 14, CARCA_SCRATCH_RETRIEVE = 15,
-       CARCA_SCRATCH_SAMPLED = 16 };
+       CARCA_SCRATCH_SAMPLED = 16, CARCA_SCRATCH_POLICY = 17 };
 void* carca_capture_alloc(hipStream_t stream, size_t bytes, bool host_mapped, void** device_view, size_t zero_bytes = 0);
 // Timing events for this thread's NEXT row-GEMM launch (the roofline hooks of carca_forward): the launch binds them to
 // its own dispatch packet (hipExtLaunchKernel), so elapsed(start, stop) is the kernel's duration and no barrier packet

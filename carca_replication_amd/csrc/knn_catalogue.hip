@@ -25,6 +25,7 @@
 #include "catalogue_select.h"
 #include "catalogue_sweep.h"
 #include "deep_select.h"
+#include "policy_items.h"
 #include "row_stream.h"
 #include "sampled_select.h"
 
@@ -240,6 +241,35 @@ extern "C" int carca_knn_recommend_sampled(const CarcaKnnRecommendDesc* desc, co
     return rc::sp_run(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, rc::SpKeepListed{rc::ListedItems{cand->ids, cand->n}},
                       *sampling, "knn_recommend_sampled", stream);
   return rc::sp_run(S, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, rc::SpKeepAll{}, *sampling, "knn_recommend_sampled", stream);
+}
+
+// carca_log_prob_items over the KNN descriptor: carca_knn_recommend_sampled's query, scoring and
+// exclusion launches, so the same logit bits and eligibility, then policy_items.h's reduce pass and finishing launch.  The
+// buffer's columns are item ids; a candidate list strikes the items outside it out in both launches.
+extern "C" int carca_knn_log_prob_items(const CarcaKnnRecommendDesc* desc, const CarcaCandidates* cand,
+                                        const CarcaPolicyItems* policy, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  CARCA_CHECK_ARG(desc, "knn_log_prob_items: null descriptor");
+  const CarcaKnnRecommendDesc& D = *desc;
+  int rc = kc_check(D, "knn_log_prob_items");
+  if (rc != CARCA_OK) return rc;
+  if ((rc = rc::pl_check(policy, "knn_log_prob_items")) != CARCA_OK) return rc;
+  if (cand && (rc = rc::check_candidates(cand, "knn_log_prob_items")) != CARCA_OK) return rc;
+  float* logits = nullptr;
+  int64_t ld_s = 0;
+  void* unused = nullptr;
+  rc = kc_score(D, "knn_log_prob_items", 0, stream, &logits, &ld_s, &unused);
+  if (rc != CARCA_OK) return rc;
+  rc::SelectView S = {};
+  S.n_items = D.n_items, S.exclude = D.exclude, S.n_exclude = D.n_exclude, S.ld_exclude = D.ld_exclude;
+  hipLaunchKernelGGL(rc::rc_exclude_kernel<rc::SelectView>, dim3(D.B), dim3(64), 0, stream, S, logits, (int)ld_s,
+                     rc::AllItems{});
+  CARCA_LAUNCH_CHECK();
+  if (cand)
+    return rc::pl_run(D.n_items, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{},
+                      rc::SpKeepListed{rc::ListedItems{cand->ids, cand->n}}, *policy, "knn_log_prob_items", stream);
+  return rc::pl_run(D.n_items, D.B, logits, (int)ld_s, D.n_items, rc::AllItems{}, rc::SpKeepAll{}, *policy,
+                    "knn_log_prob_items", stream);
 }
 
 extern "C" int carca_knn_rank_items(const CarcaKnnRankDesc* desc, void* stream_) {

@@ -81,11 +81,44 @@ __device__ __forceinline__ unsigned long long sp_wave_sum(unsigned long long v) 
   return v;
 }
 
+// ---- one chunk of a user's row: what the perturb pass and the reduce pass of policy_items.h share ---------------------
+// A chunk is read as 16-byte vectors aligned in MEMORY (row starts are u * ld_s floats: any residue mod 4), so a chunk that
+// does not start on a 16-byte boundary has a partial vector at either end, handled by dword accesses.  The two passes
+// share z's definition (sp_z) and the whole reduction (sp_chunk_sums), so their (max z, sum exp(z - max)) partials are
+// the same code over the same values -- z is one correctly rounded division, a maximum is exact in any order -- and
+// carry the same bits by construction.  The load loop with its two eligibility tests stands twice, here with the
+// perturbed store in it and in pl_reduce_kernel without: one template over both took sp_perturb_kernel<AllItems,
+// SpKeepAll> from 49 to 84 VGPRs, a shared per-column eligibility function still to 71 (DESIGN.md
+// section 28).
+
+// z of a column whose bits are `raw`: one fp32 division
+__device__ __forceinline__ float sp_z(unsigned raw, float tau) { return __uint_as_float(raw) / tau; }
+
+// The chunk's sums over the wave, in units of 2^-32 and 64-bit integers (integer addition is associative: no sum depends
+// on which lane read which column).  acc: sum exp(z - mx), each term exp2((z - mx) log2(e) + 32), at most 2^32 (saturated
+// one unit below).  ENTROPY: also ent = sum exp(z - mx) (mx - z), each term that same exp2 value times (mx - z) -- at
+// most 2^32 / e, since x exp(-x) <= 1 / e -- truncated to an integer.
+template <bool ENTROPY>
+__device__ __forceinline__ void sp_chunk_sums(const float (&z)[SP_VECS + 1][4], float mx, unsigned long long& acc,
+                                              unsigned long long& ent) {
+  acc = 0ull, ent = 0ull;
+  if (mx > -INFINITY) {
+#pragma unroll
+    for (int r = 0; r <= SP_VECS; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float t = fminf(exp2f(fmaf(z[r][e] - mx, 1.4426950408889634f, 32.f)), 4294967040.f);  // (z = -inf: 0)
+        acc += (unsigned long long)(unsigned)t;
+        if constexpr (ENTROPY) ent += (unsigned long long)(unsigned)(t > 0.f ? t * (mx - z[r][e]) : 0.f);
+      }
+  }
+  acc = sp_wave_sum(acc);
+  if constexpr (ENTROPY) ent = sp_wave_sum(ent);
+}
+
 // ---- 1. the perturb pass --------------------------------------------------------------------------------------------
 // grid (B, S): part p of user u owns chunks [p nc / S, (p + 1) nc / S) of the row, wave w of the workgroup every
-// SP_WAVES-th of them.  A chunk is read as 16-byte vectors aligned in MEMORY (row starts are u * ld_s floats: any residue
-// mod 4), so a chunk that does not start on a 16-byte boundary has a partial vector at either end, handled by dword
-// accesses; logits and pert are 16-byte aligned and share ld_s (the host side checks).  Offsets are size_t.
+// SP_WAVES-th of them; logits and pert are 16-byte aligned and share ld_s (the host side checks).  Offsets are size_t.
 template <class Map, class Keep>
 __global__ __launch_bounds__(SP_THREADS) void sp_perturb_kernel(const float* __restrict__ logits, float* __restrict__ pert,
                                                                 int ld_s, int n_items, Map map, Keep keep, SpNoise N,
@@ -128,7 +161,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_perturb_kernel(const float* __r
         if (raw[e] == RC_SENTINEL) continue;  // excluded, or outside the chunk
         const int item = m.item(col);
         if (!keep(item)) continue;
-        const float zz = __uint_as_float(raw[e]) / N.tau;
+        const float zz = sp_z(raw[e], N.tau);
         z[r][e] = zz;
         const float key = fminf(fmaxf(zz + sp_gumbel(sp_item_hash(hu, (unsigned)item)), -3.402823466e38f), 3.402823466e38f);
         out[e] = __float_as_uint(key);
@@ -145,18 +178,8 @@ __global__ __launch_bounds__(SP_THREADS) void sp_perturb_kernel(const float* __r
       }
     }
     mx = wave_max(mx);
-    // sum exp(z - mx) in units of 2^-32: exp2((z - mx) log2(e) + 32), at most 2^32 (saturated one unit below)
-    unsigned long long acc = 0ull;
-    if (mx > -INFINITY) {
-#pragma unroll
-      for (int r = 0; r <= SP_VECS; ++r)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float t = exp2f(fmaf(z[r][e] - mx, 1.4426950408889634f, 32.f));  // (z = -inf: 0)
-          acc += (unsigned long long)(unsigned)fminf(t, 4294967040.f);
-        }
-    }
-    acc = sp_wave_sum(acc);
+    unsigned long long acc, ent;
+    sp_chunk_sums<false>(z, mx, acc, ent);
     if (lane == 0) part[(size_t)u * (size_t)n_chunks + c] = make_float2(mx, (float)acc * 0x1p-32f);
   }
 }

@@ -1422,6 +1422,32 @@ class CARCA(_PackedModule, Model):
                                            self._model_side("recommend_sampled", profile, context, allow_composed),
                                            profile, k, temperature, seed, user_keys, exclude, candidates)
 
+    def log_prob_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
+                       temperature: float = 1.0, exclude="profile", candidates=None,
+                       allow_composed: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """log pi(item | user) of listed items under recommend_sampled's policy: the numerator of
+        an IPS / SNIPS estimator whose denominator recommend_sampled logged.  -> (log_probs [B, N] float32, lse [B]
+        float32, entropy [B] float32).
+
+        items: an int [B, N] tensor, a list per user -- any length (N = 0 too), any order, duplicates allowed.
+        Eligibility, exclude, candidates, allow_composed, the envelope and the temperature check are recommend_sampled's.
+        With z = logit / temperature: lse[u] is the logsumexp of z over user u's eligible items (-inf when there is none);
+        log_probs[u, j] = z - lse[u] where items[u, j] is eligible and exactly -inf otherwise (id 0, an excluded id, an id
+        outside candidates, a negative id, an id >= n_items -- 2^40 does not wrap into range); entropy[u] =
+        -sum p log p over the eligible items in nats (0 when there is none), so exp(entropy) is the effective number of
+        items the policy chooses among -- how exploratory a temperature is, before it ships.
+
+        For the ids recommend_sampled(temperature=t, exclude=e, candidates=S) returned, log_prob_items(items=ids,
+        temperature=t, exclude=e, candidates=S)[0] equals that call's log_probs bit for bit (padding gives -inf on both
+        sides); under another checkpoint or temperature it is the target policy's side of the ratio
+        (catalogue.policy_log_ratio, off_policy_estimate; train.off_policy_value runs a whole log).  A user's row, lse and
+        entropy do not depend on the batch around it, on the order of the list or on any launch shape.  Scratch:
+        recommend's buffer plus 12 bytes per user and 1024 items -- no second buffer."""
+        self._check_eval_built("log_prob_items")
+        return catalogue.log_prob_items("log_prob_items", _lib.RecommendDesc, "carca_log_prob_items",
+                                        self._model_side("log_prob_items", profile, context, allow_composed),
+                                        profile, items, temperature, exclude, candidates)
+
     def rank_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor], items: Tensor,
                    exclude="profile", candidates=None, allow_composed: bool = False) -> Tuple[Tensor, Tensor]:
         """Exact full-catalogue ranks of listed items: (scores [B, N] float32, ranks [B, N] int64).
@@ -2013,6 +2039,21 @@ class KNN(Model):
         return catalogue.recommend_sampled("KNN.recommend_sampled", _lib.KnnRecommendDesc, "carca_knn_recommend_sampled",
                                            lambda: catalogue.knn_model_side(self, profile, "KNN.recommend_sampled"),
                                            profile, k, temperature, seed, user_keys, exclude, candidates)
+
+    def log_prob_items(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
+                       items: Tensor = ..., temperature: float = 1.0, exclude="profile",
+                       candidates=None) -> Tuple[Tensor, Tensor, Tensor]:
+        """CARCA.log_prob_items for the baseline: (log_probs [B, N], lse [B], entropy [B]) of the listed items under
+        softmax(score / temperature) over the eligible rows of the registered table, with its definitions, -inf for an
+        ineligible entry, and independence of batch, list order and launch shape.  For the ids
+        KNN.recommend_sampled returned under the same temperature, exclude and candidates, log_probs equals that call's
+        bit for bit.  items (required; the default only keeps context optional) is an int [B, N] tensor.  Any L; train and
+        eval mode alike."""
+        if items is ...:
+            raise CarcaHipError("KNN.log_prob_items: items is required: an int [B, N] tensor, one list per user")
+        return catalogue.log_prob_items("KNN.log_prob_items", _lib.KnnRecommendDesc, "carca_knn_log_prob_items",
+                                        lambda: catalogue.knn_model_side(self, profile, "KNN.log_prob_items"),
+                                        profile, items, temperature, exclude, candidates)
 
     def recommend_diverse(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], context: Optional[Tensor] = None,
                           k: int = 10, pool: int = 128, lam: float = 0.7, metric: str = "cosine", exclude="profile",

@@ -332,6 +332,47 @@ def evaluate_full_ranks(model: Model, loader: DataLoader, device: str, ks=(1, 5,
     return out
 
 
+def off_policy_value(model: Model, logs, device: str, temperature: float = 1.0, mode: str = "first", clip=None,
+                     exclude="profile", candidates=None, allow_composed: bool = False) -> dict:
+    """What logged traffic would have earned under `model` at `temperature`: IPS / SNIPS estimates over a log that
+    recommend_sampled wrote.  logs: an iterable of (profile, context, ids, logged_log_probs,
+    rewards) batches -- profile and context as recommend_sampled took them, ids and logged_log_probs [B, k] as it
+    returned them, rewards [B], or [B, k]: summed over the list for mode "list", column 0 read for mode "first".  Per
+    batch: model.log_prob_items(profile, context, ids, temperature, exclude, candidates) for the target's side,
+    catalogue.policy_log_ratio's ratio (mode as there) and off_policy_estimate's sums.  exclude and candidates must be
+    what the log was drawn under.  The sums stay on the device in float64; one host sync at the end, where a logged
+    -inf under a finite target raises as policy_log_ratio does.  -> off_policy_estimate's dict, as Python floats (n an
+    int)."""
+    from . import catalogue
+
+    if mode not in ("first", "list"):
+        raise CarcaHipError(f'off_policy_value: mode must be "first" or "list", got {mode!r}')
+    model = model.eval().to(device)
+    wide = {"allow_composed": True} if allow_composed and _wide_envelope(model, "log_prob_items") else {}
+    sums = torch.zeros(5, dtype=torch.float64, device=device)
+    bad = torch.zeros((), dtype=torch.bool, device=device)
+    with torch.no_grad():
+        for profile, context, ids, logged, rewards in logs:
+            profile = to(*profile, device=device)
+            context, ids, logged, rewards = to(context, ids, logged, rewards, device=device)
+            target, _, _ = model.log_prob_items(profile, context, ids, temperature=temperature, exclude=exclude,
+                                                candidates=candidates, **wide)
+            ratio, b = catalogue._policy_log_ratio(target, logged, mode)
+            if rewards.dim() == 2:
+                rewards = rewards.to(torch.float64).sum(1) if mode == "list" else rewards[:, 0]
+            part = catalogue._off_policy_sums(ratio, rewards, clip)
+            sums = torch.cat([sums[:3] + part[:3], torch.maximum(sums[3], part[3]).reshape(1), (sums[4] + part[4]).reshape(1)])
+            bad |= b
+    host = torch.cat([sums, bad.to(torch.float64).reshape(1)]).cpu()  # (the host sync)
+    vals = {k: float(v) for k, v in catalogue._off_policy_result(host[:5], clip).items() if k != "clip"}
+    if torch.device(device).type == "cuda":
+        ops.poll_errors()
+    if bool(host[5]):
+        raise CarcaHipError(catalogue._RATIO_UNDRAWN.replace("policy_log_ratio", "off_policy_value", 1))
+    vals["n"], vals["clip"] = int(vals["n"]), clip
+    return vals
+
+
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,

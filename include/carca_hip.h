@@ -1048,6 +1048,56 @@ int carca_recommend_sampled(const CarcaRecommendDesc* desc, const CarcaCandidate
 int carca_sampled_perturb(const float* logits, float* perturbed, float* partials, int B, int n_slots,
                           const CarcaSampling* sampling, void* stream);
 
+/* ---- a sampling policy's log-probabilities for listed items: the numerator of an off-policy estimator (DESIGN.md
+ * section 28) --------------------------------------------------------------------------------------------------------
+ * carca_log_prob_items returns, for a list of n_list item ids per user, each item's log-probability under
+ * softmax(logit / temperature) over the user's eligible items -- the distribution carca_recommend_sampled draws from --
+ * and that softmax's logsumexp and entropy per user.  The descriptor and the (nullable) candidate list are
+ * carca_recommend_sampled's; its k, scores and ids_out are NOT read.  Eligibility is carca_recommend's (id != 0, not in
+ * exclude, inside the candidate list when one is given).  With z = logit / temperature (one fp32 division):
+ *   lse[u]          logsumexp of z over user u's eligible items; -inf when there is none;
+ *   log_probs[u][j] z - lse[u] when items[u][j] is eligible for u; exactly -inf otherwise: id 0, an excluded id, an id
+ *                   outside the candidate list, a negative id, an id >= n_items.  The id is compared as an int64, so
+ *                   2^40 does not wrap into range.  The list may be in any order and repeat ids; n_list = 0 is allowed
+ *                   (lse and entropy are still written);
+ *   entropy[u]      -sum_i p_i log p_i over the eligible items, in nats; 0 when there is none.  exp(entropy) is the
+ *                   effective number of items the policy chooses among.
+ * BITS.  For the ids carca_recommend_sampled returned under the same descriptor, candidate list and temperature,
+ * log_probs equals that call's log_probs bit for bit (padding, id 0, is -inf on both sides): scoring and exclusion are
+ * the same launches, the chunk partials come from the SAME device code as the perturb pass's (csrc/sampled_select.h:
+ * sp_z, sp_chunk_sums), and they merge in the same shape.  A user's row, lse and entropy depend on that user's
+ * model-side rows, exclusion and list entry only: not on the batch, on the order of the list, or on the row split S
+ * (tuning key 24).  Per fixed 1024-column chunk: an exact maximum, sum exp(z - max) and the entropy partial
+ * sum exp(z - max) (max - z) in 64-bit fixed point, units of 2^-32 (each entropy term is at most 2^32 / e); thread t of
+ * the finishing launch folds chunks t, t + 256, ..., then a fixed tree over 256 threads; with (m, s, w) the running
+ * maximum, sum and entropy partial, w' = (w + s (M - m)) e^(m - M) + (pw + ps (M - pm)) e^(pm - M) and
+ * entropy = max(log s + w / s, 0).  No atomics.
+ * Launches behind carca_recommend's scoring and exclusion: the reduce pass on grid (B, S), S as the perturb pass's, and a
+ * finishing launch on grid (B).  Stream scratch (or the capture's memory): carca_recommend's [B, n_items] ([B, n] under a
+ * list) fp32 buffer plus 12 bytes per user and 1024 columns -- no second buffer, half of carca_recommend_sampled's.
+ * Errors as carca_recommend_sampled with "log_prob_items" in the message; CARCA_ERR_BADARG for a null policy block, a
+ * temperature that is not a finite, positive, normal fp32 number, n_list < 0, null items or log_probs with n_list > 0,
+ * ld_items or ld_log_probs < n_list.  z must stay finite: |logit| / temperature below FLT_MAX. */
+typedef struct CarcaPolicyItems {
+  float temperature;     /* finite, >= FLT_MIN */
+  const int64_t* items;  /* [B, ld_items] on the device, the first n_list columns read */
+  int n_list;
+  int ld_items;
+  float* log_probs;      /* [B, ld_log_probs], the first n_list columns written */
+  int ld_log_probs;
+  float* lse;            /* [B], or NULL: not written */
+  float* entropy;        /* [B], or NULL: not written */
+} CarcaPolicyItems;
+int carca_log_prob_items(const CarcaRecommendDesc* desc, const CarcaCandidates* candidates /* nullable */,
+                         const CarcaPolicyItems* policy, void* stream);
+/* The reduce pass of carca_log_prob_items alone, over a buffer the caller holds (a measurement hook: tools/bench_policy.py
+ * times it against its bytes, beside carca_sampled_perturb on the same buffer): per user and 1024-column chunk (max z,
+ * sum exp(z - max), sum exp(z - max) (max - z)) over the columns that do not hold the exclusion sentinel (bits
+ * 0xFFFFFFFF), z = logits / temperature.  logits: [B, n_slots] fp32 with row stride n_slots, 16-byte aligned, only read;
+ * partials: [B, ceil(n_slots / 1024), 3] fp32.  The first two of a chunk's three values are carca_sampled_perturb's pair,
+ * bit for bit.  CARCA_ERR_BADARG for null pointers, B or n_slots < 1, a bad temperature or a misaligned buffer. */
+int carca_policy_reduce(const float* logits, float* partials, int B, int n_slots, float temperature, void* stream);
+
 /* ---- item groups: the k best of EVERY group in one call, and the k best overall with at most m per group (a page of
  * carousels; "at most two per brand") ----------------------------------------------------------
  * CarcaItemGroups labels items with one of n_groups groups (category, brand, shelf); an item may carry no label and is
@@ -1340,6 +1390,12 @@ int carca_knn_retrieve(const CarcaKnnRecommendDesc* desc, void* stream);
  * a (nullable) candidate list strikes the items outside it out in the perturb pass, so time and scratch follow n_items. */
 int carca_knn_recommend_sampled(const CarcaKnnRecommendDesc* desc, const CarcaCandidates* candidates /* nullable */,
                                 const CarcaSampling* sampling, void* stream);
+/* carca_knn_log_prob_items: carca_log_prob_items (above) over the KNN descriptor, whose k, scores and ids_out are not
+ * read: the query, scoring and exclusion launches are carca_knn_recommend_sampled's, so for the ids that call returned
+ * log_probs equals its log_probs bit for bit.  The logit buffer's columns are item ids; a (nullable) candidate list
+ * strikes the items outside it out in the reduce pass and in the lookup, so time and scratch follow n_items. */
+int carca_knn_log_prob_items(const CarcaKnnRecommendDesc* desc, const CarcaCandidates* candidates /* nullable */,
+                             const CarcaPolicyItems* policy, void* stream);
 
 /* carca_knn_rank_items: for user u and list entry j, with id = items[u][j]:
  *   ranks[u][j]  = number of ELIGIBLE items (id != 0, not excluded) that order strictly before id in
