@@ -518,7 +518,8 @@ EVAL_METRICS_MAX = 16384  # elements of one batch that carca_eval_metrics takes
 
 def eval_metrics(y: Tensor, y_true: Tensor, ids: Tensor, k: int, sums: Tensor, eps: float = 1e-8) -> None:
     """sums [5] += [HR@k, NDCG@k, ties, masked-mean BCE loss, users] of one evaluation batch y [B, N] (positive in column
-    0), one launch (train.py:45-51)."""
+    0), one launch (train.py:45-51).  Ranks and ties follow rank_metrics' order: a NaN score ranks above every number and
+    ties with NaN."""
     _need_cuda(y, y_true, ids, sums)
     y = _f32(y)
     B, N = y.shape
@@ -533,11 +534,16 @@ def eval_metrics(y: Tensor, y_true: Tensor, ids: Tensor, k: int, sums: Tensor, e
 def rank_metrics(y: Tensor, k: int, sums: Optional[Tensor] = None, want_rank: bool = False,
                  pos: Optional[Tensor] = None):
     """Accumulates [HR@k sum, NDCG@k sum, ties] into `sums` (device float[3]) for y [B, N]; the positive sits in
-    column pos[u] (default: column 0)."""
+    column pos[u] (default: column 0; pos holds B columns).  rank[u] counts the other columns that rank above the
+    positive, ties those that equal it.  A NaN score ranks above every number and ties with NaN, the order of the
+    reference's torch.sort(descending=True): a finite positive ranks below every NaN candidate, a NaN positive has rank
+    0 and the other NaNs of its row are counted as ties."""
     lib = _lib.load()
-    _need_cuda(y)
+    _need_cuda(y, pos)
     y = _f32(y)
     B, N = y.shape
+    if pos is not None and pos.numel() != B:  # (the kernels read pos[u] for every user u < B)
+        raise CarcaHipError(f"rank_metrics: pos holds {pos.numel()} columns for {B} users")
     if sums is None:
         sums = torch.zeros(3, dtype=torch.float32, device=y.device)
     rank = torch.empty(B, dtype=torch.int32, device=y.device) if want_rank else None
