@@ -9,8 +9,9 @@
 // with no [R, K] buffer.  The structure is sampled_xent.hip's, with a sigmoid in place of the softmax:
 //   1. compact (cx_compact_kernel, xent_tile.h): the valid rows (pos in [1, n_items)) in row order;
 //   2. row pre-pass (forward): zpos[r] = z(r, +) and br[r] per original row, both kept for the backward;
-//   3. tile (xent_tile.h's skeleton, xent_stage.h's staging: the next stream tile in registers).  br travels where the
-//      softmax backward carries lse (XentTile::lse): the own row's value in FWD and DP, the stream rows' metadata in DS:
+//   3. tile: xent_stage.h's xs_tile_kernel (the next stream tile in registers, the mask tests, xent_tile.h's products and
+//      epilogue), the kernel sampled_xent.hip runs, under this file's rule (SbRule).  br travels where the softmax
+//      backward carries lse (XentTile::lse): the own row's value in FWD and DP, the stream rows' metadata in DS:
 //        FWD  own = valid rows, stream = the samples of one split: (sum sp(z), sum sigmoid(z)) per (split, row);
 //        DP   own = valid rows, stream = samples: partial dP[split][v] = sum over the split's samples of G S;
 //        DS   (xent_tile.h: XT_DT) own = samples, stream = the valid rows of one split: dS[k] (or its partial) = G^T P;
@@ -68,159 +69,67 @@ __global__ __launch_bounds__(256) void sb_rows_kernel(CarcaSampledBceDesc D) {
   }
 }
 
-// ---- 3. logit tiles ------------------------------------------------------------------------------------------------
-// the per-entry values of a stream tile (threads 0..63), masked when stored: FWD / DP: id of the samples; DS: br and pos
-// of the valid rows, read through mrow = ridx[entry] (loaded one tile ahead)
-template <int MODE>
-__device__ __forceinline__ void sb_meta(const XentTile& A, int s0, int s_end, int mrow, int tid, float& f, int& id) {
-  if (tid < XT_TILE) {
-    if constexpr (MODE == XT_DT) {
-      f = A.lse[mrow];
-      id = A.pos[mrow];
-    } else {
-      id = A.ids[min(s0 + tid, s_end - 1)];
-    }
-  }
-}
+// ---- 3. logit tiles: the sigmoid's rule for xs_tile_kernel --------------------------------------------------------------
+struct SbRule {
+  // (FWD / DP: the samples carry no float, and s_f is not written)
+  static constexpr bool keep_f(int mode) { return mode == XT_DT; }
 
-// NCB: 16-column blocks the kernel is built for (d <= 16 NCB)
-template <int MODE, int NCB>
-__global__ __launch_bounds__(XT_THREADS) void sb_tile_kernel(XentTile A) {
-  extern __shared__ float sb_lds[];
-  float* own = sb_lds;
-  float* str = sb_lds + XT_TILE * A.pitch;
-  float* s_f = str + XT_TILE * A.pitch;                // DS: br of the stream rows (FWD / DP: unused)
-  int* s_id = reinterpret_cast<int*>(s_f + XT_TILE);   // FWD / DP: ids of the stream samples; DS: pos of the stream rows
-  const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, q = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nv = A.nv[0];
-  const int kpad = round_up(A.d, 16), nc4 = kpad / 4;
-  const int own0 = blockIdx.x * XT_TILE, split = blockIdx.y;
-  int s_begin, s_end;
-  if (MODE != XT_DT && own0 >= nv) return;  // (grid sized for R; rows past n_valid have nothing to do)
-  xt_split_range<MODE>(A, nv, split, s_begin, s_end);
-  constexpr bool OWN_ROWS = MODE != XT_DT;
-  const int d4 = (A.d + 3) / 4 * 4;
-  const float* sbase = OWN_ROWS ? A.T : A.P;  // the streamed operand
-  const int sld = OWN_ROWS ? A.ld_t : A.ld_p;
-  f32x4 pre[NCB];  // the stream tile in flight
-  int src[NCB];    // its pieces' operand rows
-  {
-    const int own_end = OWN_ROWS ? nv : A.n;
-    sx_rows<NCB>(A, src, own0, own_end, OWN_ROWS, nc4, tid);
-    __builtin_amdgcn_s_waitcnt(SX_WAIT_VM0);  // (the row indices, once: then the pieces' loads go out back to back)
-    sx_issue<NCB>(OWN_ROWS ? A.P : A.T, OWN_ROWS ? A.ld_p : A.ld_t, src, pre, nc4, d4, tid);
-    sx_store<NCB>(A, pre, own, own0, own_end, nc4, tid);
-  }
-  float pre_f = 0.f;
-  int pre_id = 0, mrow = 0;
-  if (s_begin < s_end) {
-    sx_rows<NCB>(A, src, s_begin, s_end, !OWN_ROWS, nc4, tid);
-    if constexpr (MODE == XT_DT) mrow = tid < XT_TILE ? A.ridx[min(s_begin + tid, s_end - 1)] : 0;
-    __builtin_amdgcn_s_waitcnt(SX_WAIT_VM0);
-    sx_issue<NCB>(sbase, sld, src, pre, nc4, d4, tid);
-    sb_meta<MODE>(A, s_begin, s_end, mrow, tid, pre_f, pre_id);
-    if constexpr (MODE == XT_DT) {  // the row indices one tile ahead
-      if (s_begin + XT_TILE < s_end) {
-        sx_rows<NCB>(A, src, s_begin + XT_TILE, s_end, true, nc4, tid);
-        mrow = tid < XT_TILE ? A.ridx[min(s_begin + XT_TILE + tid, s_end - 1)] : 0;
-      }
-    }
-  }
-
-  // this lane's own entry (column r16 of the wave's Z^T tiles)
-  const int o_idx = own0 + 16 * w + r16;
-  float o_f = 0.f;  // FWD / DP: br of the own row
-  int o_id = -1;    // FWD / DP: pos of the own row; DS: id of the own sample
-  bool o_ok = false;
-  if constexpr (MODE != XT_DT) {
-    if (o_idx < nv) {
-      const int r = A.ridx[o_idx];
-      o_id = A.pos[r];
-      o_f = A.lse[r];
-      o_ok = true;
-    }
-  } else {
-    if (o_idx < A.n) {
-      o_id = A.ids[o_idx];
-      o_ok = o_id >= 1 && o_id < A.n_items;
-    }
-  }
-  float run_sp = 0.f, run_sg = 0.f;  // FWD: sum of softplus(z), sum of sigmoid(z) over the lane's unmasked logits
-  f32x4 acc[NCB];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float* own_row = own + (16 * w + r16) * A.pitch + 4 * q;
-
-  for (int s0 = s_begin; s0 < s_end; s0 += XT_TILE) {
-    __syncthreads();  // (the previous step's readers of `str` are done)
-    // Every load in flight lands here, on every path (see sampled_xent.hip: the compiler would wait again otherwise).
-    __builtin_amdgcn_s_waitcnt(SX_WAIT_VM0);
-    sx_store<NCB>(A, pre, str, s0, s_end, nc4, tid);
+  // the per-entry values of a stream tile (threads 0..63), masked when stored: FWD / DP: id of the samples; DS: br and pos
+  // of the valid rows, read through mrow = ridx[entry] (loaded one tile ahead)
+  template <int MODE>
+  static __device__ __forceinline__ void meta(const XentTile& A, int s0, int s_end, int mrow, int tid, float& f, int& id) {
     if (tid < XT_TILE) {
-      const bool live = s0 + tid < s_end;
-      if constexpr (MODE == XT_DT) s_f[tid] = live ? pre_f : 0.f;
-      s_id[tid] = live ? pre_id : (MODE == XT_DT ? -1 : 0);  // (id 0: never a class)
-    }
-    __syncthreads();
-    if (s0 + XT_TILE < s_end) {  // the next tile's loads: in flight while this tile multiplies
-      if constexpr (MODE != XT_DT) sx_rows<NCB>(A, src, s0 + XT_TILE, s_end, false, nc4, tid);
-      sx_issue<NCB>(sbase, sld, src, pre, nc4, d4, tid);
-      sb_meta<MODE>(A, s0 + XT_TILE, s_end, mrow, tid, pre_f, pre_id);
-      if constexpr (MODE == XT_DT) {  // the row indices of the tile after it
-        if (s0 + 2 * XT_TILE < s_end) {
-          sx_rows<NCB>(A, src, s0 + 2 * XT_TILE, s_end, true, nc4, tid);
-          mrow = tid < XT_TILE ? A.ridx[min(s0 + 2 * XT_TILE + tid, s_end - 1)] : 0;
-        }
+      if constexpr (MODE == XT_DT) {
+        f = A.lse[mrow];
+        id = A.pos[mrow];
+      } else {
+        id = A.ids[min(s0 + tid, s_end - 1)];
       }
     }
-    f32x4 z[4];
-    xt_logits<NCB>(A, own_row, str, r16, q, z);
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sl = 16 * n + 4 * q + j;
-        if constexpr (MODE == XT_FWD) {
-          // own row r16 against samples s0 + 16n + 4q + j: the unmasked logits' softplus and sigmoid
-          const int sid = s_id[sl];
-          if (sid >= 1 && sid < A.n_items && sid != o_id) {
-            float sp, sg;
-            sb_softplus_sigmoid(z[n][j] + o_f, sp, sg);
-            run_sp += sp;
-            run_sg += sg;
-          }
-        } else {
-          // G[own r16][stream 16n + 4q + j] = sigmoid(z), 0 where masked
-          float g = 0.f;
-          if constexpr (MODE == XT_DP) {
-            const int sid = s_id[sl];
-            if (o_ok && sid >= 1 && sid < A.n_items && sid != o_id) g = sb_sigmoid(z[n][j] + o_f);
-          } else {
-            if (o_ok && s0 + sl < s_end && s_id[sl] != o_id) g = sb_sigmoid(z[n][j] + s_f[sl]);
-          }
-          z[n][j] = g;
-        }
-      }
-    if constexpr (MODE != XT_FWD) xt_accumulate<NCB>(A, z, str, r16, q, acc);
   }
 
-  if constexpr (MODE == XT_FWD) {
-    // merge the four lanes of own row r16 (lanes r16 + 16q; + is commutative, so every lane gets the same bits) and
-    // store the (sum softplus, sum sigmoid) partial of (split, valid row o_idx) in the part_m / part_s slots
+  // the lane's own entry: FWD / DP: br of the own row (in the lse slot)
+  template <int MODE>
+  static __device__ __forceinline__ float own_f(const XentTile& A, int e) {
+    if constexpr (MODE != XT_DT) return A.lse[e];
+    else return 0.f;
+  }
+
+  // FWD: sum of softplus(z), sum of sigmoid(z) over the lane's unmasked logits
+  struct Fwd {
+    float sp = 0.f, sg = 0.f;
+  };
+  static __device__ __forceinline__ float fwd_logit(bool ok, float z, const float*, int, float o_f, Fwd& run) {
+    if (ok) {
+      float sp, sg;
+      sb_softplus_sigmoid(z + o_f, sp, sg);
+      run.sp += sp;
+      run.sg += sg;
+    }
+    return z;
+  }
+  static __device__ __forceinline__ void fwd_tile(const f32x4 (&)[4], Fwd&) {}
+  // merge the four lanes of own row r16 (lanes r16 + 16q; + is commutative, so every lane gets the same bits) and store
+  // the (sum softplus, sum sigmoid) partial of (split, valid row o_idx) in the part_m / part_s slots
+  static __device__ __forceinline__ void fwd_store(const XentTile& A, Fwd run, int split, int o_idx, int q, int nv) {
 #pragma unroll
     for (int x = 16; x <= 32; x *= 2) {
-      run_sp += __shfl_xor(run_sp, x);
-      run_sg += __shfl_xor(run_sg, x);
+      run.sp += __shfl_xor(run.sp, x);
+      run.sg += __shfl_xor(run.sg, x);
     }
     if (q == 0 && o_idx < nv) {
-      A.part_m[(size_t)split * A.R + o_idx] = run_sp;
-      A.part_s[(size_t)split * A.R + o_idx] = run_sg;
+      A.part_m[(size_t)split * A.R + o_idx] = run.sp;
+      A.part_s[(size_t)split * A.R + o_idx] = run.sg;
     }
-  } else {
-    xt_epilogue<MODE, NCB>(A, acc, nv, own0, split, w, lane);
   }
-}
+
+  // G = sigmoid(z): DP: z = P[r] . S[k] + br of the own row; DS: + br of the stream row
+  template <int MODE>
+  static __device__ __forceinline__ float g(float z, const float* s_f, int sl, float o_f) {
+    if constexpr (MODE == XT_DP) return sb_sigmoid(z + o_f);
+    else return sb_sigmoid(z + s_f[sl]);
+  }
+};
 
 // ---- 4. merges -----------------------------------------------------------------------------------------------------
 // per row: the split partials in split order, then the positive term beta sp(-zpos)
@@ -317,7 +226,7 @@ extern "C" int carca_sampled_bce_fwd(const CarcaSampledBceDesc* desc, void* stre
   if ((rc = xt_check(C, "fwd", false)) != CARCA_OK) return rc;  // (before the pre-pass reads the operands)
   hipLaunchKernelGGL(sb_rows_kernel, dim3((D.R + 31) / 32), dim3(256), 0, stream, D);
   CARCA_LAUNCH_CHECK();
-  return xt_forward(C, XT_KERNELS(sb_tile_kernel, XT_FWD), stream,
+  return xt_forward(C, XS_KERNELS(SbRule, XT_FWD), stream,
                     [&](const int32_t* rpos, const float* part_sp, const float* part_sg) {
                       hipLaunchKernelGGL(sb_merge_kernel, dim3((D.R + 255) / 256), dim3(256), 0, stream, D, rpos, part_sp,
                                          part_sg);
@@ -333,7 +242,7 @@ extern "C" int carca_sampled_bce_bwd(const CarcaSampledBceDesc* desc, void* stre
   if (rc != CARCA_OK) return rc;
   CARCA_CHECK_ARG(D.dTp && (!D.C || D.dC), "sampled_bce_bwd: null dTp, or C without dC");
   // the row terms: dP's last partial, after the sample splits'; dTp and dC
-  return xt_backward(C, XT_KERNELS(sb_tile_kernel, XT_DP), XT_KERNELS(sb_tile_kernel, XT_DT), stream,
+  return xt_backward(C, XS_KERNELS(SbRule, XT_DP), XS_KERNELS(SbRule, XT_DT), stream,
                      [&](const int32_t* rpos, const int32_t* nv, float* part, int ldo) {
                        const int ldm = D.C && D.ld_c > D.ld_tp ? D.ld_c : D.ld_tp;
                        const int64_t n = (int64_t)D.R * ldm;

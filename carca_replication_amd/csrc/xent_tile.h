@@ -1,6 +1,8 @@
 // The tile skeleton of the softmax cross-entropy kernels: catalogue_xent.hip (the classes are the whole catalogue,
 // DESIGN.md section 13) and sampled_xent.hip (the classes are K shared samples with the logQ correction, section 14).
-// sampled_bce.hip (a sigmoid loss over K shared samples, section 16) runs on it too, with its own per-logit rule.
+// sampled_bce.hip (a sigmoid loss over K shared samples, section 16) runs on it too.  Two tile kernels are built from it:
+// cx_tile_kernel (catalogue_xent.hip) and xs_tile_kernel (xent_stage.h), which both sampled losses instantiate, each with
+// its own rule struct.
 //
 // A workgroup of four waves owns 64 rows of one operand (the "own" tile, staged once in LDS) and streams 64-row tiles of
 // the other through LDS.  Wave w owns own rows 16w .. 16w+15; lane l holds column r16 = l & 15 and the stream rows
@@ -12,8 +14,9 @@
 //           row losses) and cx_reduce_kernel (split partials summed in split order, scaled by grad / n_valid);
 //   host:   the scratch layout, the checks both descriptors share, the LDS-size / NCB dispatch, and the launch sequences
 //           of the forward (compact, tile, merge, mean) and the backward (compact, dP tile, reduce, dT tile, reduce).
-// What each kernel keeps: how it stages a tile (catalogue: straight into LDS; sampled: one tile ahead in registers), its
-// mask / G rule with the lane's own-entry metadata, and its merge kernels.
+// What each tile kernel keeps: how it stages a tile (cx_tile_kernel: straight into LDS; xs_tile_kernel: one tile ahead in
+// registers) and its mask tests with the lane's own-entry metadata.  What each loss keeps: the values around those tests
+// (catalogue: in its kernel; sampled: SxRule, SbRule) and its merge kernels.
 #pragma once
 #include "carca_common.h"
 #include "../../include/carca_hip.h"

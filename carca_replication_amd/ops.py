@@ -1523,15 +1523,59 @@ def catalogue_xent(P: Tensor, T: Tensor, pos: Tensor) -> Tensor:
 # --------------------------------------------------------------------------------------------------
 # sampled softmax cross-entropy with the logQ correction (carca_sampled_xent_fwd / _bwd)
 # --------------------------------------------------------------------------------------------------
+def _sampled_plan(op: str, R: int, K: int, d: int, n_cus: int, share_partials: bool) -> dict:
+    """The plan of either loss over K shared samples: _xent_plan with the samples as the classes and one more dP partial."""
+    if R < 1 or K < 1 or d < 1:
+        raise CarcaHipError(f"{op}_plan: R, K and d must be positive")
+    s_s, per, s_r, fwd, bwd = _xent_plan(R, K, d, n_cus, 1, share_partials=share_partials)
+    return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+
+
+def _sampled_check(op: str, floats: str, P: Tensor, Tp: Tensor, S: Tensor, pos: Tensor, s_ids: Tensor,
+                   C: Optional[Tensor] = None) -> None:  # noqa: N803
+    """The operand checks of sampled_xent / sampled_bce: P [R, d], Tp [R, d], S [K, d] and C [R, d] or None, float32 (floats:
+    what the dtype message calls them); pos [R] and s_ids [K] integer."""
+    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
+        raise CarcaHipError(f"{op}: expected P [R, d], Tp [R, d], S [K, d]; got {tuple(P.shape)}, "
+                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
+    if C is not None and tuple(C.shape) != tuple(P.shape):
+        raise CarcaHipError(f"{op}: C must have the shape of P {tuple(P.shape)}, got {tuple(C.shape)}")
+    if pos.numel() != P.shape[0] or s_ids.numel() != S.shape[0]:
+        raise CarcaHipError(f"{op}: pos must have R = {P.shape[0]} entries and s_ids K = {S.shape[0]}; got "
+                            f"{pos.numel()} and {s_ids.numel()}")
+    if S.shape[0] < 1:
+        raise CarcaHipError(f"{op}: at least one sample is needed")
+    if pos.is_floating_point() or s_ids.is_floating_point():
+        raise CarcaHipError(f"{op}: pos and s_ids must be integer tensors")
+    dtypes = [x.dtype for x in (P, Tp, S, C) if x is not None]
+    if any(t != torch.float32 for t in dtypes):
+        raise CarcaHipError(f"{op}: {floats} must be float32, got {', '.join(str(t) for t in dtypes)}")
+
+
+def _sampled_desc(D, plan_of, P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int, d: int,
+                  scratch_key: str, keep: list):
+    """The fields both sampled descriptors share (pos [R], s_ids [K]: int32, contiguous), with plan_of's splits and scratch."""
+    keep += [pos, s_ids]
+    D.R, D.K, D.n_items, D.d = P.shape[0], S.shape[0], int(n_items), d
+    plan = plan_of(D.R, D.K, d, num_cus())
+    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
+    D.pos, D.s_ids = pos.data_ptr(), s_ids.data_ptr()
+    return _xent_splits(D, plan, ("splits_samples", "samples_per_split", "splits_rows"), scratch_key, P.device, keep)
+
+
+def _sampled_grads(D, P: Tensor, Tp: Tensor, S: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dP [R, ld_p], dTp [R, ld_tp], dS [K, ld_s]), uninitialised, set as D's gradient outputs."""
+    dP, dTp, dS = (torch.empty(x.shape[0], x.stride(0), dtype=torch.float32, device=P.device) for x in (P, Tp, S))
+    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
+    return dP, dTp, dS
+
+
 def sampled_xent_plan(R: int, K: int, d: int, n_cus: int = 256) -> dict:
     """Host-side sizing of carca_sampled_xent_fwd / _bwd (pure: no device): _xent_plan with the K samples as the classes
     and one more dP partial.  Returns the split counts and the scratch each call needs, in 4-byte words: the row lists,
     then the forward's (max, sum-exp) partials, or the backward's dP partials [splits_samples + 1, R, ld] (the last: the
     positive term) and, with more than one row split, dS partials [splits_rows, K, ld], ld = round_up(d, 4)."""
-    if R < 1 or K < 1 or d < 1:
-        raise CarcaHipError("sampled_xent_plan: R, K and d must be positive")
-    s_s, per, s_r, fwd, bwd = _xent_plan(R, K, d, n_cus, 1)
-    return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+    return _sampled_plan("sampled_xent", R, K, d, n_cus, share_partials=False)
 
 
 def _sx_vec(t: Tensor, n: int, name: str, ids: bool) -> Tensor:
@@ -1546,13 +1590,10 @@ def _sx_desc(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: T
     R, K = P.shape[0], S.shape[0]
     bp, bs = _sx_vec(bp, R, "bp", False), _sx_vec(bs, K, "bs", False)
     pos, s_ids = _sx_vec(pos, R, "pos", True), _sx_vec(s_ids, K, "s_ids", True)
-    keep += [bp, bs, pos, s_ids]
+    keep += [bp, bs]
     D = _lib.SampledXentDesc()
-    D.R, D.K, D.n_items, D.d = R, K, int(n_items), d
-    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
-    D.bp, D.pos, D.s_ids, D.bs = bp.data_ptr(), pos.data_ptr(), s_ids.data_ptr(), bs.data_ptr()
-    plan = sampled_xent_plan(R, K, d, num_cus())
-    return _xent_splits(D, plan, ("splits_samples", "samples_per_split", "splits_rows"), scratch_key, P.device, keep)
+    D.bp, D.bs = bp.data_ptr(), bs.data_ptr()
+    return _sampled_desc(D, sampled_xent_plan, P, Tp, pos, S, s_ids, n_items, d, scratch_key, keep)
 
 
 def sampled_xent_fwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, bs: Tensor, n_items: int,
@@ -1578,11 +1619,8 @@ def sampled_xent_bwd(P: Tensor, Tp: Tensor, bp: Tensor, pos: Tensor, S: Tensor, 
     keep: list = []
     D = _sx_desc(P, Tp, bp, pos, S, s_ids, bs, n_items, d, "scratch_bwd", keep)
     g = _f32(grad.reshape(1))
-    dP = torch.empty(P.shape[0], P.stride(0), dtype=torch.float32, device=P.device)
-    dTp = torch.empty(P.shape[0], Tp.stride(0), dtype=torch.float32, device=P.device)
-    dS = torch.empty(S.shape[0], S.stride(0), dtype=torch.float32, device=P.device)
+    dP, dTp, dS = _sampled_grads(D, P, Tp, S)
     D.lse, D.row_loss, D.grad = lse.data_ptr(), row_loss.data_ptr(), g.data_ptr()
-    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
     _lib.check(_lib.load().carca_sampled_xent_bwd(C.byref(D), _stream()), "sampled_xent_bwd")
     return dP, dTp, dS
 
@@ -1634,18 +1672,7 @@ def sampled_xent(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, l
     log_q [n_items] = log Q(i) of the proposal the samples were drawn from (n_items = log_q.numel()).  Row r is valid iff
     pos[r] lies in [1, n_items); a sample id outside [1, n_items) contributes nothing; a batch without a valid row gives 0.
     With s_ids = arange(1, n_items) and uniform Q this is catalogue_xent.  Fused HIP kernels: no [R, K] buffer."""
-    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
-        raise CarcaHipError(f"sampled_xent: expected P [R, d], Tp [R, d], S [K, d]; got {tuple(P.shape)}, "
-                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
-    if pos.numel() != P.shape[0] or s_ids.numel() != S.shape[0]:
-        raise CarcaHipError(f"sampled_xent: pos must have R = {P.shape[0]} entries and s_ids K = {S.shape[0]}; got "
-                            f"{pos.numel()} and {s_ids.numel()}")
-    if S.shape[0] < 1:
-        raise CarcaHipError("sampled_xent: at least one sample is needed")
-    if pos.is_floating_point() or s_ids.is_floating_point():
-        raise CarcaHipError("sampled_xent: pos and s_ids must be integer tensors")
-    if any(x.dtype != torch.float32 for x in (P, Tp, S)):
-        raise CarcaHipError(f"sampled_xent: P, Tp and S must be float32, got {P.dtype}, {Tp.dtype}, {S.dtype}")
+    _sampled_check("sampled_xent", "P, Tp and S", P, Tp, S, pos, s_ids)
     if log_q.dim() != 1 or log_q.numel() < 1 or not log_q.is_floating_point():
         raise CarcaHipError(f"sampled_xent: log_q must be a 1-d float tensor [n_items], got {tuple(log_q.shape)} "
                             f"{log_q.dtype}")
@@ -1658,16 +1685,11 @@ def sampled_xent(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, l
 # binary cross-entropy against K shared negatives, gBCE (carca_sampled_bce_fwd / _bwd)
 # --------------------------------------------------------------------------------------------------
 def sampled_bce_plan(R: int, K: int, d: int, n_cus: int = 256) -> dict:
-    """Host-side sizing of carca_sampled_bce_fwd / _bwd (pure: no device): _xent_plan with the K samples as the classes
-    and one more dP partial, as sampled_xent_plan.  Returns the split counts and the scratch each call needs, in 4-byte
-    words: the row lists, then the forward's (sum softplus, sum sigmoid) partials, or the backward's dP partials
-    [splits_samples + 1, R, ld] (the last: the positive's and the context's terms) or, where larger, the dS partials
-    [splits_rows, K, ld] of more than one row split, in the same words (dP is complete before dS starts),
-    ld = round_up(d, 4)."""
-    if R < 1 or K < 1 or d < 1:
-        raise CarcaHipError("sampled_bce_plan: R, K and d must be positive")
-    s_s, per, s_r, fwd, bwd = _xent_plan(R, K, d, n_cus, 1, share_partials=True)
-    return dict(splits_samples=s_s, samples_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
+    """Host-side sizing of carca_sampled_bce_fwd / _bwd (pure: no device), as sampled_xent_plan, but: the forward's partials
+    are (sum softplus, sum sigmoid); the backward's scratch after the row lists is the dP partials [splits_samples + 1, R,
+    ld] (the last: the positive's and the context's terms) or, where larger, the dS partials [splits_rows, K, ld] of more
+    than one row split, in the same words (dP is complete before dS starts)."""
+    return _sampled_plan("sampled_bce", R, K, d, n_cus, share_partials=True)
 
 
 def sampled_bce_beta(K: int, n_items: int, t: float) -> float:
@@ -1687,15 +1709,11 @@ def _sb_desc(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S: Tensor
     if pos.numel() != R or s_ids.numel() != K:
         raise CarcaHipError(f"sampled_bce: pos must have {R} entries and s_ids {K}, got {pos.numel()} and {s_ids.numel()}")
     pos, s_ids = _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1))
-    keep += [pos, s_ids]
     D = _lib.SampledBceDesc()
-    D.R, D.K, D.n_items, D.d, D.beta = R, K, int(n_items), d, float(beta)
-    D.P, D.ld_p, D.Tp, D.ld_tp, D.S, D.ld_s = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0), S.data_ptr(), S.stride(0)
+    D.beta = float(beta)
     if Cr is not None:
         D.C, D.ld_c = Cr.data_ptr(), Cr.stride(0)
-    D.pos, D.s_ids = pos.data_ptr(), s_ids.data_ptr()
-    plan = sampled_bce_plan(R, K, d, num_cus())
-    return _xent_splits(D, plan, ("splits_samples", "samples_per_split", "splits_rows"), scratch_key, P.device, keep)
+    return _sampled_desc(D, sampled_bce_plan, P, Tp, pos, S, s_ids, n_items, d, scratch_key, keep)
 
 
 def sampled_bce_fwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S: Tensor, s_ids: Tensor, n_items: int,
@@ -1704,7 +1722,7 @@ def sampled_bce_fwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S:
     Tp [R, ld_tp], the shared samples S [K, ld_s] and the rows' context share Cr [R, ld_c] or None (first d columns, unit
     column stride; ld_p, ld_tp, ld_s multiples of 4): pos [R] and s_ids [K] int32, beta the positive's weight.  Returns
     (loss [1], saved [3, R] = (zpos, br, gsum) for the backward, row_loss [R]); no host wait."""
-    _need_cuda(P, Tp, pos, S, s_ids, *(() if Cr is None else (Cr,)))
+    _need_cuda(P, Tp, pos, S, s_ids, Cr)
     keep: list = []
     D = _sb_desc(P, Tp, Cr, pos, S, s_ids, n_items, beta, d, "scratch_fwd", keep)
     saved = torch.empty(3, P.shape[0], dtype=torch.float32, device=P.device)
@@ -1720,7 +1738,7 @@ def sampled_bce_bwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S:
                     beta: float, saved: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
     """(dP [R, ld_p], dTp [R, ld_tp], dS [K, ld_s], dC [R, ld_c] or None) of sampled_bce_fwd's loss scaled by grad [1]
     (device), from the forward's saved [3, R]; zeros past d."""
-    _need_cuda(P, Tp, pos, S, s_ids, saved, grad, *(() if Cr is None else (Cr,)))
+    _need_cuda(P, Tp, pos, S, s_ids, saved, grad, Cr)
     keep: list = []
     D = _sb_desc(P, Tp, Cr, pos, S, s_ids, n_items, beta, d, "scratch_bwd", keep)
     g = _f32(grad.reshape(1))
@@ -1728,15 +1746,10 @@ def sampled_bce_bwd(P: Tensor, Tp: Tensor, Cr: Optional[Tensor], pos: Tensor, S:
     if saved.shape != (3, R) or saved.dtype != torch.float32 or not saved.is_contiguous():
         raise CarcaHipError(f"sampled_bce_bwd: saved must be the forward's contiguous fp32 [3, {R}], got {tuple(saved.shape)}")
     row_loss = torch.empty(R, dtype=torch.float32, device=P.device)  # (the descriptor's forward output: not read here)
-    dP = torch.empty(R, P.stride(0), dtype=torch.float32, device=P.device)
-    dTp = torch.empty(R, Tp.stride(0), dtype=torch.float32, device=P.device)
-    dS = torch.empty(S.shape[0], S.stride(0), dtype=torch.float32, device=P.device)
+    dP, dTp, dS = _sampled_grads(D, P, Tp, S)
     dC = torch.empty(R, Cr.stride(0), dtype=torch.float32, device=P.device) if Cr is not None else None
     D.zpos, D.br, D.gsum = saved[0].data_ptr(), saved[1].data_ptr(), saved[2].data_ptr()
-    D.row_loss, D.grad = row_loss.data_ptr(), g.data_ptr()
-    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr()
-    if dC is not None:
-        D.dC = dC.data_ptr()
+    D.row_loss, D.grad, D.dC = row_loss.data_ptr(), g.data_ptr(), _ptr(dC)
     _lib.check(_lib.load().carca_sampled_bce_bwd(C.byref(D), _stream()), "sampled_bce_bwd")
     return dP, dTp, dS, dC
 
@@ -1773,26 +1786,12 @@ def sampled_bce(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, n_
     context) and C [R, d] (the rows' context share M c_r; None: no context term) fp32; pos [R], s_ids [K] integer; beta in
     [0, 1] the positive's weight (sampled_bce_beta).  Row r is valid iff pos[r] lies in [1, n_items); a sample id outside
     [1, n_items) contributes nothing; a batch without a valid row gives 0.  Fused HIP kernels: no [R, K] buffer."""
-    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
-        raise CarcaHipError(f"sampled_bce: expected P [R, d], Tp [R, d], S [K, d]; got {tuple(P.shape)}, "
-                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
-    if C is not None and tuple(C.shape) != tuple(P.shape):
-        raise CarcaHipError(f"sampled_bce: C must have the shape of P {tuple(P.shape)}, got {tuple(C.shape)}")
-    if pos.numel() != P.shape[0] or s_ids.numel() != S.shape[0]:
-        raise CarcaHipError(f"sampled_bce: pos must have R = {P.shape[0]} entries and s_ids K = {S.shape[0]}; got "
-                            f"{pos.numel()} and {s_ids.numel()}")
-    if S.shape[0] < 1:
-        raise CarcaHipError("sampled_bce: at least one sample is needed")
-    if pos.is_floating_point() or s_ids.is_floating_point():
-        raise CarcaHipError("sampled_bce: pos and s_ids must be integer tensors")
-    ops_f = (P, Tp, S) + (() if C is None else (C,))
-    if any(x.dtype != torch.float32 for x in ops_f):
-        raise CarcaHipError(f"sampled_bce: P, Tp, S and C must be float32, got {', '.join(str(x.dtype) for x in ops_f)}")
+    _sampled_check("sampled_bce", "P, Tp, S and C", P, Tp, S, pos, s_ids, C)
     if int(n_items) < 2:
         raise CarcaHipError(f"sampled_bce: n_items must be at least 2, got {n_items}")
     if not 0.0 <= float(beta) <= 1.0:
         raise CarcaHipError(f"sampled_bce: beta must lie in [0, 1], got {beta}")
-    _need_cuda(*ops_f, pos, s_ids)
+    _need_cuda(P, Tp, S, C, pos, s_ids)
     return _SampledBceFn.apply(P, Tp, S, C, _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1)), int(n_items), float(beta))
 
 

@@ -23,12 +23,12 @@ _root = argparse.ArgumentParser(add_help=False)
 _root.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.abspath(_root.parse_known_args()[0].package_root))  # (the tree whose package is imported)
-from bench_catalogue_xent import PEAK_TFLOPS, _batch, _peak  # noqa: E402
-from bench_recommend import _time  # noqa: E402
-from carca_replication_amd import engine, ops  # noqa: E402
+from carca_replication_amd import engine, ops  # noqa: E402  (before the helper tools: they put their own tree in front)
 from carca_replication_amd import modules as M  # noqa: E402
 from carca_replication_amd.optim import Adam  # noqa: E402
 from carca_replication_amd.sampling import ItemSampler  # noqa: E402
+from bench_catalogue_xent import PEAK_TFLOPS, _batch, _peak  # noqa: E402
+from bench_recommend import _time  # noqa: E402
 
 B, L = 128, 50
 KS = (256, 1024, 8192)

@@ -1,12 +1,13 @@
-"""Bit fingerprints of the softmax cross-entropy kernels (csrc/catalogue_xent.hip, csrc/sampled_xent.hip over
-csrc/xent_tile.h; DESIGN.md sections 13 and 14): for a fixed list of seeded cases, one sha256 per output tensor of
-ops.catalogue_xent_fwd / _bwd and ops.sampled_xent_fwd / _bwd, over the bytes of the whole strided buffer (so the zero
-columns past d count).  Every sum in these kernels has one fixed order, so a change that only moves code must leave every
-line as it was: run the script once per build (a fresh process each, --package-root naming the tree whose package is
-imported) on the same machine and compare the listings line for line.  The hashes depend on the CU count through the
-split plan (first line).  The cases: d in {64, 90, 128, 192, 256} with row strides past d; padding rows (pos 0, pos >=
+"""Bit fingerprints of the tile-kernel losses (csrc/catalogue_xent.hip, csrc/sampled_xent.hip, csrc/sampled_bce.hip over
+csrc/xent_tile.h and csrc/xent_stage.h; DESIGN.md sections 13, 14 and 16): for a fixed list of seeded cases, one sha256
+per output tensor of ops.catalogue_xent_fwd / _bwd, ops.sampled_xent_fwd / _bwd and ops.sampled_bce_fwd / _bwd, over the
+bytes of the whole strided buffer (so the zero columns past d count).  Every sum in these kernels has one fixed order,
+so a change that only moves code must leave every line as it was: run the script once per build (a fresh process each,
+--package-root naming the tree whose package is imported) on the same machine and compare the listings line for line.
+The hashes depend on the CU count through the split plan (first line).  The cases: d in {64, 90, 128, 192, 256} with row strides past d; padding rows (pos 0, pos >=
 n_items, negative); R = 1; one and several row splits, several class splits with a short last one; sample ids that are
-invalid, repeated, or equal to a row's positive; a batch without a valid row; the two benchmark shapes.
+invalid, repeated, or equal to a row's positive; a batch without a valid row; the two benchmark shapes.  gBCE runs the
+sampled shapes twice, with the context rows C and without, after the softmax losses' lines (which keep their seeds).
 usage: python tools/xent_bits.py [--package-root DIR] [--out listing.txt]"""
 import argparse
 import hashlib
@@ -62,6 +63,18 @@ def _sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
+def _sample_ids(g, K, n_items, pos):
+    """K sample ids with invalid ones, duplicates and accidental hits of a row's positive (and of padding rows' ids)."""
+    s_ids = torch.randint(1, n_items, (K,), generator=g, dtype=torch.int32)
+    s_ids[3::17] = 0
+    s_ids[5::29] = n_items
+    s_ids[7::31] = -3
+    s_ids[11::13] = s_ids[10::13][: s_ids[11::13].numel()]
+    hits = torch.arange(2, K, 19)
+    s_ids[hits] = pos[hits % pos.numel()]
+    return s_ids
+
+
 def catalogue_case(seed, name, R, n_items, d, ld, valid):
     g = torch.Generator().manual_seed(seed)
     P, T = _operand(g, R, d, ld), _operand(g, n_items, d, ld)
@@ -77,13 +90,7 @@ def sampled_case(seed, name, R, K, d, ld, valid):
     n_items = 5000
     P, Tp, S = _operand(g, R, d, ld), _operand(g, R, d, ld), _operand(g, K, d, ld)
     pos = _pos(g, R, n_items, valid)
-    s_ids = torch.randint(1, n_items, (K,), generator=g, dtype=torch.int32)
-    s_ids[3::17] = 0                      # invalid ids
-    s_ids[5::29] = n_items
-    s_ids[7::31] = -3
-    s_ids[11::13] = s_ids[10::13][: s_ids[11::13].numel()]  # duplicates
-    hits = torch.arange(2, K, 19)
-    s_ids[hits] = pos[hits % R]           # accidental hits of a row's positive (and of padding rows' ids)
+    s_ids = _sample_ids(g, K, n_items, pos)
     bp = -torch.rand(R, generator=g) * 3 - 1
     bs = -torch.rand(K, generator=g) * 3 - 1
     grad = torch.tensor([0.37], device="cuda")
@@ -94,6 +101,22 @@ def sampled_case(seed, name, R, K, d, ld, valid):
     return [(f"sampled/{name}/{k}", _sha(v)) for k, v in outs]
 
 
+def bce_case(seed, with_c, name, R, K, d, ld, valid):
+    g = torch.Generator().manual_seed(seed)
+    n_items, beta = 5000, 0.8125  # (beta strictly inside (0, 1))
+    P, Tp, S = _operand(g, R, d, ld), _operand(g, R, d, ld), _operand(g, K, d, ld)
+    Cr = _operand(g, R, d, ld) if with_c else None
+    pos = _pos(g, R, n_items, valid)
+    s_ids = _sample_ids(g, K, n_items, pos).cuda()
+    pos = pos.cuda()
+    grad = torch.tensor([0.37], device="cuda")
+    loss, saved, row_loss = ops.sampled_bce_fwd(P, Tp, Cr, pos, S, s_ids, n_items, beta, d)
+    dP, dTp, dS, dC = ops.sampled_bce_bwd(P, Tp, Cr, pos, S, s_ids, n_items, beta, saved, grad, d)
+    outs = (("loss", loss), ("saved", saved), ("row_loss", row_loss), ("dP", dP), ("dTp", dTp), ("dS", dS), ("dC", dC))
+    tag = "bce_c" if with_c else "bce"
+    return [(f"{tag}/{name}/{k}", _sha(v)) for k, v in outs if v is not None]
+
+
 def main():
     assert torch.cuda.is_available(), "xent_bits.py needs a GPU"
     lines = [f"# cus={ops.num_cus()}"]
@@ -101,6 +124,9 @@ def main():
         lines += [f"{k} {h}" for k, h in catalogue_case(100 + i, *shape)]
     for i, shape in enumerate(SHAPES + [BENCH_SAMPLED]):
         lines += [f"{k} {h}" for k, h in sampled_case(200 + i, *shape)]
+    for with_c in (True, False):
+        for i, shape in enumerate(SHAPES + [BENCH_SAMPLED]):
+            lines += [f"{k} {h}" for k, h in bce_case(300 + i, with_c, *shape)]
     torch.cuda.synchronize()
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
