@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip", "policy_items.hip"]
+           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip", "policy_items.hip", "policy_xent.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h",
            "sampled_select.h", "policy_items.h"]
@@ -319,6 +319,15 @@ class CatalogueXentDesc(C.Structure):
                 ("row_loss", _fp), ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dT", _fp)]
 
 
+class PolicyXentDesc(C.Structure):
+    """CarcaPolicyXentDesc (carca_policy_xent_fwd / _bwd)."""
+    _fields_ = [("R", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp), ("ld_p", C.c_int32), ("T", _fp),
+                ("ld_t", C.c_int32), ("items", _fp), ("temperature", C.c_float), ("excl", _fp), ("n_excl", C.c_int32),
+                ("t_off", _fp), ("t_rows", _fp), ("splits_items", C.c_int32), ("items_per_split", C.c_int32),
+                ("splits_rows", C.c_int32), ("scratch", _fp), ("scratch_floats", C.c_int64), ("lse", _fp),
+                ("log_prob", _fp), ("entropy", _fp), ("valid", _fp), ("c", _fp), ("h", _fp), ("dP", _fp), ("dT", _fp)]
+
+
 class PolicyItems(C.Structure):
     """CarcaPolicyItems (carca_log_prob_items / carca_knn_log_prob_items)."""
     _fields_ = [("temperature", C.c_float), ("items", _fp), ("n_list", C.c_int32), ("ld_items", C.c_int32),
@@ -480,6 +489,8 @@ SIGNATURES = {
     "carca_mmr_rerank": (_i, [C.POINTER(MmrDesc), _fp]),
     "carca_catalogue_xent_fwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
     "carca_catalogue_xent_bwd": (_i, [C.POINTER(CatalogueXentDesc), _fp]),
+    "carca_policy_xent_fwd": (_i, [C.POINTER(PolicyXentDesc), _fp]),
+    "carca_policy_xent_bwd": (_i, [C.POINTER(PolicyXentDesc), _fp]),
     "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
     "carca_sampled_xent_bwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
     "carca_sampled_bce_fwd": (_i, [C.POINTER(SampledBceDesc), _fp]),

@@ -735,6 +735,107 @@ def off_policy_estimate(log_ratio: Tensor, rewards: Tensor, clip: Optional[float
     return _off_policy_result(_off_policy_sums(log_ratio, rewards, clip), clip)
 
 
+# ---- objectives over a policy's differentiable log-probabilities -------------------------------
+POLICY_OBJECTIVES = ("ips", "clipped_ips", "snips", "weighted_nll")
+_OBJECTIVE_UNDRAWN = ("policy_objective: a logged log-probability is -inf on a valid row: the logging policy cannot have "
+                      "drawn that item (the log and the policy disagree on eligibility)")
+
+
+def _policy_objective(log_probs: Tensor, valid: Tensor, logged_log_probs: Optional[Tensor], rewards: Tensor, kind: str,
+                      clip=None, entropy: Optional[Tensor] = None, entropy_coef: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """policy_objective without its host sync: -> (the loss, 0-d float64; a 0-d bool tensor, true where the raising case
+    occurred, for the caller to test when it syncs)."""
+    if kind not in POLICY_OBJECTIVES:
+        raise CarcaHipError(f"policy_objective: kind must be one of {POLICY_OBJECTIVES}, got {kind!r}")
+    if not isinstance(log_probs, Tensor) or not log_probs.is_floating_point():
+        raise CarcaHipError("policy_objective: log_probs must be a float tensor")
+    if not isinstance(valid, Tensor) or valid.shape != log_probs.shape:
+        raise CarcaHipError("policy_objective: valid must have log_probs' shape")
+    if not isinstance(rewards, Tensor) or rewards.shape != log_probs.shape:
+        raise CarcaHipError("policy_objective: rewards must have log_probs' shape")
+    if logged_log_probs is None:
+        if kind != "weighted_nll":
+            raise CarcaHipError(f'policy_objective: kind "{kind}" needs logged_log_probs')
+    elif not isinstance(logged_log_probs, Tensor) or logged_log_probs.shape != log_probs.shape:
+        raise CarcaHipError("policy_objective: logged_log_probs must have log_probs' shape")
+    if kind == "clipped_ips":
+        if not (isinstance(clip, (int, float)) and not isinstance(clip, bool) and clip > 0):
+            raise CarcaHipError(f'policy_objective: kind "clipped_ips" needs a clip > 0, got {clip!r}')
+    elif clip is not None:
+        raise CarcaHipError('policy_objective: clip belongs to kind "clipped_ips"')
+    if entropy_coef != 0.0 and (not isinstance(entropy, Tensor) or entropy.shape != log_probs.shape):
+        raise CarcaHipError("policy_objective: a non-zero entropy_coef needs entropy with log_probs' shape")
+    dev = log_probs.device
+    ok = valid.to(device=dev) != 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    m = ok.to(torch.float64)
+    n = m.sum().clamp(min=1.0)  # (no valid row: every sum below is 0, and so is the loss)
+    lp = torch.where(ok, log_probs.to(torch.float64), zero)
+    r = torch.where(ok, rewards.to(device=dev, dtype=torch.float64), zero)
+    bad = torch.zeros((), dtype=torch.bool, device=dev)
+    if logged_log_probs is not None:
+        lg = logged_log_probs.to(device=dev, dtype=torch.float64)
+        bad = (ok & torch.isneginf(lg)).any()
+        lg = torch.where(ok, lg, zero)
+    if kind == "weighted_nll":
+        w0 = m if logged_log_probs is None else torch.exp(lp.detach() - lg) * m
+        loss = -(r * w0 * lp).sum() / n
+    else:
+        w = torch.exp(lp - lg) * m
+        if kind == "ips":
+            loss = -(r * w).sum() / n
+        elif kind == "clipped_ips":
+            cap = torch.full((), float(clip), dtype=torch.float64, device=dev)
+            loss = -(r * torch.where(w < cap, w, cap) * m).sum() / n  # (rows at the cap are constants: no gradient)
+        else:
+            ws = w.sum()
+            loss = -(r * w).sum() / torch.where(ws > 0, ws, torch.ones_like(ws))
+    if entropy_coef != 0.0:
+        loss = loss - float(entropy_coef) * torch.where(ok, entropy.to(torch.float64), zero).sum() / n
+    return loss, bad
+
+
+def policy_objective(log_probs: Tensor, valid: Tensor, logged_log_probs: Optional[Tensor], rewards: Tensor, kind: str,
+                     clip: Optional[float] = None, entropy: Optional[Tensor] = None, entropy_coef: float = 0.0) -> Tensor:
+    """A loss to minimise over the valid rows of CARCA.log_prob_rows' output, 0-d float64, differentiable through
+    log_probs and entropy.  log_probs, valid, logged_log_probs, rewards (and entropy) share one shape; logged_log_probs is
+    what the logging policy reported for the same actions (recommend_sampled's column 0).  With w = exp(log_probs -
+    logged) and means over the valid rows, kind is one of
+      "ips"           -mean(r w): minus the inverse-propensity estimate of the policy's value;
+      "clipped_ips"   -mean(r min(w, clip)): rows at the cap get no gradient;
+      "snips"         -(sum r w) / (sum w): the self-normalised estimate;
+      "weighted_nll"  -mean(r w_0 log_probs) with w_0 = 1 when logged_log_probs is None, else the detached weight
+                      exp(log_probs.detach() - logged): reward-weighted likelihood.
+    Every kind subtracts entropy_coef * mean(entropy).  No valid row gives 0 with zero gradients.  Rows that are not
+    valid are read nowhere (their logged value and reward may be anything).  A valid row whose logged value is -inf
+    raises: the logging policy cannot have drawn it; that check is the function's one host sync, as policy_log_ratio's
+    (_policy_objective returns the flag instead, for a caller that syncs later).  Torch ops in float64 on log_probs'
+    device; not a kernel."""
+    loss, bad = _policy_objective(log_probs, valid, logged_log_probs, rewards, kind, clip, entropy, entropy_coef)
+    if bool(bad):
+        raise CarcaHipError(_OBJECTIVE_UNDRAWN)
+    return loss
+
+
+def off_policy_rows(shape, ids: Tensor, logged_log_probs: Tensor, rewards: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """A logged batch as log_prob_rows' rows: (items, logged, rewards), each [B, L] = shape, with the first logged column
+    (ids[:, 0], its log-probability, its reward) at column L - 1 -- the policy after the whole profile -- and 0 elsewhere.
+    Only that column's logged value is a true softmax marginal (section 28)."""
+    B, L = shape
+    if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1 or logged_log_probs.shape != ids.shape:
+        raise CarcaHipError(f"off_policy_step: ids and logged_log_probs must be [B = {B}, k >= 1] tensors of one shape")
+    if rewards.shape[0] != B or rewards.dim() not in (1, 2):
+        raise CarcaHipError(f"off_policy_step: rewards must be [B = {B}] or [B, k]")
+    r = rewards[:, 0] if rewards.dim() == 2 else rewards
+    items = torch.zeros(B, L, dtype=ids.dtype, device=ids.device)
+    logged = torch.zeros(B, L, dtype=torch.float64, device=ids.device)
+    rew = torch.zeros(B, L, dtype=torch.float64, device=ids.device)
+    items[:, L - 1] = ids[:, 0]
+    logged[:, L - 1] = logged_log_probs[:, 0].to(torch.float64)
+    rew[:, L - 1] = r.to(device=ids.device, dtype=torch.float64)
+    return items, logged, rew
+
+
 def rank_items(what: str, desc, entry: str, model_side: Callable, profile, items: Tensor, exclude,
                candidates=None) -> Tuple[Tensor, Tensor]:
     """The rank call; the arguments are recommend's, with the [B, N] list in place of k."""

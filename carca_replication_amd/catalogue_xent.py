@@ -216,6 +216,121 @@ def catalogue_softmax_loss(model, profile, pos: Tensor) -> Tensor:
     return _CatalogueFn.apply(model, tuple(profile), pos, *cached_parameters(model))
 
 
+# ---- the policy's log-probabilities, differentiable ----------------------------------------------
+def profile_exclusion(p_x: Tensor) -> Tensor:
+    """exclude="profile" for every slot: [B, L, L] with row (b, t) holding p_x[b, :t + 1] and 0 (padding) after it -- at
+    t = L - 1 recommend(exclude="profile")'s rule.  Torch ops on p_x's device, no host wait."""
+    L = p_x.shape[1]
+    keep = torch.ones(L, L, dtype=torch.bool, device=p_x.device).tril()
+    return torch.where(keep.unsqueeze(0), p_x.unsqueeze(1), torch.zeros((), dtype=p_x.dtype, device=p_x.device))
+
+
+def _policy_args(model, profile, items, temperature, exclude, what: str, last_only: bool = False):
+    """The checks of log_prob_rows' own arguments -> (items [B L] int32 with the rows of padding slots set to 0, the
+    temperature as fp32, the sorted exclusion lists [B L, E] int32 or None); with last_only the rows of slot L - 1 alone
+    ([B] and [B, E]; "profile" is then p_x itself, one list per user)."""
+    p_x = profile[0]
+    if not isinstance(items, Tensor) or tuple(items.shape) != tuple(p_x.shape) or items.is_floating_point() or \
+            items.dtype == torch.bool:
+        raise CarcaHipError(f"{what}: items must be an int tensor of p_x's shape {tuple(p_x.shape)}, got "
+                            f"{tuple(items.shape) if isinstance(items, Tensor) else type(items).__name__}")
+    t32 = ops.policy_temperature(what, temperature)
+    _check(model, profile, items, what)
+    emb = model.embeds
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    B, L = p_x.shape
+    if exclude is None:
+        excl = None
+    elif isinstance(exclude, str):
+        if exclude != "profile":
+            raise CarcaHipError(f'{what}: exclude must be None, "profile" or an int [B, L, E] tensor, got {exclude!r}')
+        excl = p_x.reshape(B, 1, L) if last_only else profile_exclusion(p_x)
+    else:
+        if not isinstance(exclude, Tensor) or exclude.dim() != 3 or tuple(exclude.shape[:2]) != (B, L) or \
+                exclude.is_floating_point() or exclude.dtype == torch.bool:
+            raise CarcaHipError(f'{what}: exclude must be None, "profile" or an int [B, L, E] tensor with B, L = {B}, {L}')
+        ops._need_cuda(exclude)
+        excl = exclude[:, L - 1:] if last_only else exclude
+    live = torch.where(p_x != 0, items, torch.zeros_like(items))
+    if last_only:
+        live = live[:, L - 1]
+    R = live.numel()
+    excl_sorted = ops.policy_exclusion(excl.reshape(R, -1), R, n_items) if excl is not None else None
+    return ops._ids32_clamped(live.reshape(-1), n_items), t32, excl_sorted
+
+
+def _last_slot(full_shape, last: Tensor) -> Tensor:
+    """[B] values of slot L - 1 -> [B, L] with zeros (False) elsewhere."""
+    out = torch.zeros(full_shape, dtype=last.dtype, device=last.device)
+    out[:, -1] = last
+    return out
+
+
+class _PolicyRowsFn(torch.autograd.Function):
+    """_CatalogueFn with ops.policy_xent_fwd / _bwd: per-row outputs, per-row upstream gradients.  last_only: the op runs
+    over the B rows of slot L - 1 alone (a contiguous copy of them), the other rows are not valid by construction."""
+
+    @staticmethod
+    def forward(ctx, model, profile, items32, t32, excl_sorted, with_entropy, last_only, *params):
+        segs, n_items = _segments(model, profile)
+        rows, (cat,), st = _profile_forward(model, segs)
+        B, L, dpi = st["B"], st["L"], st["dpi"]
+        T = cat.view(n_items, dpi)
+        P = rows.view(B, L, dpi)[:, L - 1].contiguous() if last_only else rows
+        log_prob, valid, entropy, lse = ops.policy_xent_fwd(P, T, items32, model.embeds.d, t32, excl_sorted, with_entropy)
+        ctx.model, ctx.params = model, params
+        ctx.st = dict(st, T=T, px=(P, items32, t32, excl_sorted, lse, valid, entropy, last_only))
+        full = (lambda t: _last_slot((B, L), t)) if last_only else (lambda t: t.view(B, L))
+        out = (full(log_prob), full(valid))
+        ctx.mark_non_differentiable(out[1])
+        return out + (full(entropy),) if with_entropy else out
+
+    @staticmethod
+    def backward(ctx, g_lp, g_valid, g_ent=None):
+        st, d = ctx.st, ctx.model.embeds.d
+        P, items32, t32, excl_sorted, lse, valid, entropy, last_only = st["px"]
+        B, L, dpi = st["B"], st["L"], st["dpi"]
+        rows_of = (lambda g: g.detach()[:, L - 1].contiguous()) if last_only else (lambda g: g.detach().reshape(-1))
+
+        def loss_bwd():
+            c = rows_of(g_lp) if g_lp is not None else torch.zeros_like(lse)
+            h = None
+            if entropy is not None:
+                h = rows_of(g_ent) if g_ent is not None else torch.zeros_like(lse)
+            dP, dT = ops.policy_xent_bwd(P, st["T"], items32, d, t32, excl_sorted, lse, c, h, entropy, valid)
+            if last_only:
+                dP_last, dP = dP, torch.zeros(B, L, dpi, dtype=torch.float32, device=dP.device)
+                dP[:, L - 1] = dP_last
+                dP = dP.view(B * L, dpi)
+            return dP, [dT]
+
+        grads = _profile_backward(ctx.model, ctx.params, st, loss_bwd)
+        ctx.st = None
+        return (None,) * 7 + grads
+
+
+def log_prob_rows(model, profile, items: Tensor, temperature: float = 1.0, exclude=None, with_entropy: bool = False,
+                  last_slot_only: bool = False):
+    from .modules import cached_parameters, note_training_forward
+
+    what = "log_prob_rows"
+    last = bool(last_slot_only)
+    items32, t32, excl_sorted = _policy_args(model, profile, items, temperature, exclude, what, last)
+    note_training_forward()  # packed-weight caches: see modules._WEIGHT_EPOCH
+    B, L = profile[0].shape
+    if model._composed(profile, [profile]):
+        segs, n_items = _segments(model, profile)
+        p_n, (T,) = _composed_rows(model, profile, segs, what)
+        d = model.embeds.d
+        P = p_n[:, L - 1] if last else p_n.reshape(-1, d)
+        out = ops._PolicyXentFn.apply(P, T.reshape(n_items, d), items32, t32, excl_sorted, bool(with_entropy))
+        out = tuple(_last_slot((B, L), o) if last else o.view(B, L) for o in out)
+    else:
+        out = _PolicyRowsFn.apply(model, tuple(profile), items32, t32, excl_sorted, bool(with_entropy), last,
+                                  *cached_parameters(model))
+    return (out[0], out[1], out[2]) if with_entropy else (out[0], out[1], None)
+
+
 # ---- sampled softmax with the logQ correction (DESIGN.md section 14) ------------------------------------------------
 def _sampled_segments(model, profile, pos, samples):
     """[(profile segment), (samples [1, K], zero context), (positives [B, L], zero context)]; sample and positive ids

@@ -204,6 +204,35 @@ def _softmax_step(model, optim, batch) -> torch.Tensor:
     return loss.detach()
 
 
+def off_policy_step(model, optim, log_batch, temperature: float = 1.0, kind: str = "ips", clip=None, exclude="profile",
+                    entropy_coef: float = 0.0, graphed: bool = False, sharded: bool = False,
+                    undrawn: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One optimizer step on a bandit log.  log_batch = (profile, context, ids [B, k],
+    logged_log_probs [B, k], rewards [B] or [B, k]), the tuple train.off_policy_value reads.  Only the first logged column
+    is used, the one position whose logged value is a true softmax marginal (a Plackett-Luce list objective is not
+    built): ids[:, 0] becomes the action of the row after the last profile slot (catalogue.off_policy_rows),
+    model.log_prob_rows gives its log-probability under `temperature` and `exclude`, catalogue.policy_objective(kind,
+    clip, entropy_coef) the loss.  Only slot L - 1 has an action, so the op runs over B rows (last_slot_only).  The context
+    is not read: it cancels in the dot decoders' softmax.  Like the softmax
+    step it does not call optim.mark_rows (every row of the item table has a gradient).  No host sync: a logged -inf on a
+    valid row is OR-ed into `undrawn` (a 0-d bool tensor) for the caller to test when it syncs.  -> the (device) loss."""
+    from . import catalogue
+
+    if graphed or sharded:
+        raise CarcaHipError("off_policy_step: graphed and sharded steps are not built")
+    profile, _context, ids, logged, rewards = log_batch
+    items, lg, rew = catalogue.off_policy_rows(tuple(profile[0].shape), ids, logged, rewards)
+    optim.zero_grad(set_to_none=True)
+    lp, valid, ent = model.log_prob_rows(profile, items, temperature=temperature, exclude=exclude,
+                                         with_entropy=entropy_coef != 0.0, last_slot_only=True)
+    loss, bad = catalogue._policy_objective(lp, valid, lg, rew, kind, clip, ent, entropy_coef)
+    loss.backward()
+    optim.step()
+    if undrawn is not None:
+        undrawn |= bad
+    return loss.detach()
+
+
 _SAMPLERS: dict = {}
 
 

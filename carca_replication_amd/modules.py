@@ -1320,6 +1320,27 @@ class CARCA(_PackedModule, Model):
 
         return catalogue_softmax_loss(self, profile, pos)
 
+    def log_prob_rows(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], items: Tensor, temperature: float = 1.0,
+                      exclude=None, with_entropy: bool = False,
+                      last_slot_only: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+        """The policy's log-probabilities as a differentiable quantity: what training on a bandit
+        log needs.  -> (log_probs [B, L] float32, valid [B, L] bool, entropy [B, L] float32 or None); log_probs and entropy
+        are differentiable in every parameter.
+
+        items has p_x's shape: row (b, t) is the policy "after slot t", softmax(logit / temperature) over its eligible
+        items, and log_probs[b, t] the log-probability of items[b, t] under it.  exclude: None, "profile" (row (b, t)
+        excludes the non-zero ids of p_x[b, :t + 1]; at t = L - 1 recommend(exclude="profile")'s rule) or an int
+        [B, L, E] tensor of ids (0 = padding).  Item i is eligible iff 1 <= i < n_items and not excluded; a row is valid
+        iff its own slot is not padding and its action is eligible; log_probs and entropy are exactly 0 on the other rows,
+        which get no gradient.  The context cancels in the softmax (section 13), so the value at t = L - 1 is what
+        log_prob_items reports for that policy under any request context.  last_slot_only=True reads column L - 1 of
+        items (and of an exclude tensor) alone and calls every other row not valid: the bandit shape, one action per user
+        after the whole profile, at the cost of B rows instead of B L.  Dot decoders only, as catalogue_softmax_loss;
+        dropout follows self.training."""
+        from .catalogue_xent import log_prob_rows
+
+        return log_prob_rows(self, profile, items, temperature, exclude, with_entropy, last_slot_only)
+
     def sampled_softmax_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor, samples: Tensor,
                              log_q: Tensor) -> Tensor:
         """Sampled softmax cross-entropy with the logQ correction: catalogue_softmax_loss with the

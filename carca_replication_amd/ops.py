@@ -1521,6 +1521,187 @@ def catalogue_xent(P: Tensor, T: Tensor, pos: Tensor) -> Tensor:
 
 
 # --------------------------------------------------------------------------------------------------
+# row log-softmax with a temperature and per-row exclusion (carca_policy_xent_fwd / _bwd)
+# --------------------------------------------------------------------------------------------------
+def policy_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_policy_xent_fwd / _bwd (pure: no device): catalogue_xent_plan's splits and backward
+    scratch; the forward's scratch holds a third partial per (split, row), the entropy's."""
+    if R < 1 or n_items < 1 or d < 1:
+        raise CarcaHipError("policy_xent_plan: R, n_items and d must be positive")
+    s_i, per, s_r, fwd, bwd = _xent_plan(R, n_items, d, n_cus, 0)
+    return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r,
+                scratch_fwd=fwd + (s_i * R + 63) // 64 * 64, scratch_bwd=bwd)
+
+
+def policy_temperature(what: str, temperature) -> float:
+    """The temperature as the fp32 value the kernels divide by: a finite number > 0 whose fp32 reciprocal is finite."""
+    ok = isinstance(temperature, (int, float)) and not isinstance(temperature, bool)
+    t32 = C.c_float(float(temperature)).value if ok else 0.0
+    if not (ok and math.isfinite(t32) and t32 > 0 and math.isfinite(C.c_float(1.0 / t32).value)):
+        raise CarcaHipError(f"{what}: temperature must be a finite float > 0, got {temperature!r}")
+    return t32
+
+
+def _ids32_clamped(t: Tensor, n_items: int) -> Tensor:
+    """Ids as int32 with everything outside [0, n_items) sent to -1 or n_items first: no int64 id wraps into range."""
+    return _ids32(t.clamp(min=-1, max=n_items))
+
+
+def policy_exclusion(excl: Optional[Tensor], R: int, n_items: int) -> Optional[Tensor]:
+    """excl [R, E] integer (0 = padding; duplicates and ids outside [1, n_items) allowed) -> the rows ascending, int32, as
+    the kernels walk them; None for no list (or E = 0).  A device-side sort, no host wait."""
+    if excl is None:
+        return None
+    if excl.dim() != 2 or excl.shape[0] != R or excl.is_floating_point() or excl.dtype == torch.bool:
+        raise CarcaHipError(f"policy_xent: excl must be an int [R = {R}, E] tensor, got {tuple(excl.shape)} {excl.dtype}")
+    if excl.shape[1] == 0:
+        return None
+    if R * excl.shape[1] >= 2 ** 31:
+        raise CarcaHipError("policy_xent: R x E must stay below 2^31")
+    return torch.sort(_ids32_clamped(excl, n_items), dim=1).values.contiguous()
+
+
+def policy_valid_rows(items: Tensor, excl_sorted: Optional[Tensor], n_items: int) -> Tensor:
+    """valid [R] bool: items[r] in [1, n_items) and not in its row's list (what the kernels' compact pass finds)."""
+    valid = (items >= 1) & (items < n_items)
+    if excl_sorted is not None:
+        valid &= ~(excl_sorted == items.view(-1, 1)).any(1)
+    return valid
+
+
+def policy_transposed_lists(excl_sorted: Tensor, valid: Tensor, n_items: int) -> Tuple[Tensor, Tensor]:
+    """The exclusion lists by item, for the backward's dT tile (whose own entry is an item and whose stream is 64
+    consecutive valid rows): (t_off [n_items + 1] int32, t_rows [R E] int32) with t_rows[t_off[i] : t_off[i + 1]] the
+    ascending valid-row indices (a row's rank among the valid rows) of the valid rows that list item i.  Device-side
+    torch ops of fixed shapes: one sort of R E keys, one searchsorted; no host wait."""
+    R, E = excl_sorted.shape
+    v = torch.cumsum(valid.to(torch.int64), 0) - 1
+    ids = excl_sorted.to(torch.int64)
+    ok = (ids >= 1) & (ids < n_items) & valid.view(R, 1)
+    key = torch.where(ok, ids * R + v.view(R, 1), torch.full_like(ids, n_items * R)).reshape(-1)
+    key = torch.sort(key).values
+    bounds = torch.arange(n_items + 1, dtype=torch.int64, device=key.device) * R
+    t_off = torch.searchsorted(key, bounds).to(torch.int32)
+    return t_off, (key % R).to(torch.int32)
+
+
+def _policy_desc(P: Tensor, T: Tensor, items: Tensor, d: int, t32: float, excl_sorted: Optional[Tensor], scratch_key: str,
+                 keep: list):
+    plan = policy_xent_plan(P.shape[0], T.shape[0], d, num_cus())
+    D = _lib.PolicyXentDesc()
+    D.R, D.n_items, D.d = P.shape[0], T.shape[0], d
+    D.P, D.ld_p, D.T, D.ld_t, D.items = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0), items.data_ptr()
+    D.temperature = t32
+    if excl_sorted is not None:
+        if excl_sorted.dtype != torch.int32 or not excl_sorted.is_contiguous() or excl_sorted.shape[0] != P.shape[0]:
+            raise CarcaHipError("policy_xent: the exclusion list must be policy_exclusion's (int32 [R, E], contiguous)")
+        D.excl, D.n_excl = excl_sorted.data_ptr(), excl_sorted.shape[1]
+    return _xent_splits(D, plan, ("splits_items", "items_per_split", "splits_rows"), scratch_key, P.device, keep)
+
+
+def policy_xent_fwd(P: Tensor, T: Tensor, items: Tensor, d: int, temperature: float, excl_sorted: Optional[Tensor] = None,
+                    with_entropy: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor], Tensor]:
+    """Rows P [R, ld_p] against items T [n_items, ld_t] (first d columns, strides multiples of 4), actions items [R] int32,
+    excl_sorted policy_exclusion's lists or None: -> (log_prob [R], valid [R] bool, entropy [R] or None, lse [R]) of
+    include/carca_hip.h's carca_policy_xent_fwd; no host wait."""
+    _need_cuda(P, T, items, excl_sorted)
+    t32 = policy_temperature("policy_xent_fwd", temperature)
+    keep: list = []
+    D = _policy_desc(P, T, items, d, t32, excl_sorted, "scratch_fwd", keep)
+    R = P.shape[0]
+    lse = torch.empty(R, dtype=torch.float32, device=P.device)
+    log_prob = torch.empty_like(lse)
+    entropy = torch.empty_like(lse) if with_entropy else None
+    valid = torch.empty(R, dtype=torch.bool, device=P.device)
+    D.lse, D.log_prob, D.valid = lse.data_ptr(), log_prob.data_ptr(), valid.data_ptr()
+    D.entropy = entropy.data_ptr() if with_entropy else None
+    _lib.check(_lib.load().carca_policy_xent_fwd(C.byref(D), _stream()), "policy_xent_fwd")
+    return log_prob, valid, entropy, lse
+
+
+def policy_xent_bwd(P: Tensor, T: Tensor, items: Tensor, d: int, temperature: float, excl_sorted: Optional[Tensor],
+                    lse: Tensor, c: Tensor, h: Optional[Tensor] = None, entropy: Optional[Tensor] = None,
+                    valid: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(dP [R, ld_p], dT [n_items, ld_t]) of policy_xent_fwd's outputs under the row gradients c = dL/dlog_prob and h =
+    dL/dentropy (None: none; else with the forward's entropy); zeros past d and on rows that are not valid.  valid: the
+    forward's, when at hand (else recomputed) -- the transposed lists are built from it."""
+    _need_cuda(P, T, items, excl_sorted, lse, c, h, entropy)
+    t32 = policy_temperature("policy_xent_bwd", temperature)
+    if (h is None) != (entropy is None):
+        raise CarcaHipError("policy_xent_bwd: h and the forward's entropy come together")
+    keep: list = []
+    D = _policy_desc(P, T, items, d, t32, excl_sorted, "scratch_bwd", keep)
+    R = P.shape[0]
+    if excl_sorted is not None:
+        if valid is None:
+            valid = policy_valid_rows(items, excl_sorted, T.shape[0])
+        t_off, t_rows = policy_transposed_lists(excl_sorted, valid, T.shape[0])
+        keep += [t_off, t_rows]
+        D.t_off, D.t_rows = t_off.data_ptr(), t_rows.data_ptr()
+    c32 = _f32(c.reshape(R))
+    dP = torch.empty(R, P.stride(0), dtype=torch.float32, device=P.device)
+    dT = torch.empty(T.shape[0], T.stride(0), dtype=torch.float32, device=P.device)
+    D.lse, D.c, D.dP, D.dT = lse.data_ptr(), c32.data_ptr(), dP.data_ptr(), dT.data_ptr()
+    if h is not None:
+        h32 = _f32(h.reshape(R))
+        keep.append(h32)
+        D.h, D.entropy = h32.data_ptr(), entropy.data_ptr()
+    _lib.check(_lib.load().carca_policy_xent_bwd(C.byref(D), _stream()), "policy_xent_bwd")
+    return dP, dT
+
+
+class _PolicyXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, T, items32, t32, excl_sorted, with_entropy):
+        d = P.shape[1]
+        P2, T2 = _xent_operand(P.detach(), d, "policy_xent"), _xent_operand(T.detach(), d, "policy_xent")
+        log_prob, valid, entropy, lse = policy_xent_fwd(P2, T2, items32, d, t32, excl_sorted, with_entropy)
+        ctx.save_for_backward(P2, T2, items32, excl_sorted, lse, valid, entropy)
+        ctx.d, ctx.t32 = d, t32
+        ctx.mark_non_differentiable(valid)
+        if with_entropy:
+            return log_prob, valid, entropy
+        return log_prob, valid
+
+    @staticmethod
+    def backward(ctx, g_lp, g_valid, g_ent=None):
+        P2, T2, items32, excl_sorted, lse, valid, entropy = ctx.saved_tensors
+        d = ctx.d
+        c = g_lp.detach() if g_lp is not None else torch.zeros_like(lse)
+        h = None
+        if entropy is not None:
+            h = g_ent.detach() if g_ent is not None else torch.zeros_like(lse)
+        dP, dT = policy_xent_bwd(P2, T2, items32, d, ctx.t32, excl_sorted, lse, c, h, entropy, valid)
+        return dP[:, :d], dT[:, :d], None, None, None, None
+
+
+def policy_xent(P: Tensor, T: Tensor, items: Tensor, temperature: float, excl: Optional[Tensor] = None,
+                with_entropy: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """The log-probability of action items[r] under softmax(P[r] . T[i] / temperature) over row r's eligible classes,
+    differentiable in P and T: -> (log_prob [R] float32, valid [R] bool, entropy [R] float32 or
+    None).
+
+    P [R, d] fp32, T [n_items, d] fp32, items [R] integer, temperature a finite float > 0, excl None or an int [R, E]
+    tensor of ids that are no classes of that row (0 = padding; duplicates and ids outside [1, n_items) are ignored).
+    Class i is eligible for row r iff 1 <= i < n_items and i is not in excl[r]; row r is valid iff items[r] is an
+    eligible class of r; log_prob and entropy (-sum p log p over the eligible classes, computed only with with_entropy)
+    are exactly 0 on the other rows, which get no gradient.  Fused HIP kernels: no [R, n_items] buffer in either pass, no
+    float atomics, the same call gives the same bits."""
+    _need_cuda(P, T, items, excl)
+    if P.dim() != 2 or T.dim() != 2 or P.shape[1] != T.shape[1] or items.numel() != P.shape[0]:
+        raise CarcaHipError(f"policy_xent: expected P [R, d], T [n_items, d], items [R]; got {tuple(P.shape)}, "
+                            f"{tuple(T.shape)}, {tuple(items.shape)}")
+    if items.is_floating_point() or items.dtype == torch.bool:
+        raise CarcaHipError("policy_xent: items must be an integer tensor")
+    t32 = policy_temperature("policy_xent", temperature)
+    n_items = T.shape[0]
+    items32 = _ids32_clamped(items.reshape(-1), n_items)
+    excl_sorted = policy_exclusion(excl, P.shape[0], n_items)
+    out = _PolicyXentFn.apply(P, T, items32, t32, excl_sorted, bool(with_entropy))
+    return (out[0], out[1], out[2]) if with_entropy else (out[0], out[1], None)
+
+
+# --------------------------------------------------------------------------------------------------
 # sampled softmax cross-entropy with the logQ correction (carca_sampled_xent_fwd / _bwd; DESIGN.md section 14)
 # --------------------------------------------------------------------------------------------------
 def _sampled_plan(op: str, R: int, K: int, d: int, n_cus: int, share_partials: bool) -> dict:

@@ -373,6 +373,34 @@ def off_policy_value(model: Model, logs, device: str, temperature: float = 1.0, 
     return vals
 
 
+def train_off_policy(model: Model, logs, device: str, optim: Optimizer, epochs: int, temperature: float = 1.0,
+                     kind: str = "ips", clip=None, exclude="profile", entropy_coef: float = 0.0) -> list:
+    """Train `model` on a log that recommend_sampled wrote: engine.off_policy_step over every
+    batch of `logs` (off_policy_value's tuples; a re-iterable) for `epochs` epochs.  The model's mode is the caller's
+    (dropout follows model.training).  One host sync per epoch, where a logged -inf on a valid row raises.  -> the mean
+    objective of each epoch, as Python floats."""
+    from . import catalogue
+    from .engine import off_policy_step
+
+    model = model.to(device)
+    out = []
+    for _ in range(epochs):
+        total = torch.zeros((), dtype=torch.float64, device=device)
+        bad = torch.zeros((), dtype=torch.bool, device=device)
+        n = 0
+        for profile, context, ids, logged, rewards in logs:
+            profile = to(*profile, device=device)
+            context, ids, logged, rewards = to(context, ids, logged, rewards, device=device)
+            total = total + off_policy_step(model, optim, (profile, context, ids, logged, rewards), temperature, kind, clip,
+                                            exclude, entropy_coef, undrawn=bad)
+            n += 1
+        host = torch.stack([total, bad.to(torch.float64)]).cpu()  # (the host sync)
+        if bool(host[1]):
+            raise CarcaHipError(catalogue._OBJECTIVE_UNDRAWN.replace("policy_objective", "train_off_policy", 1))
+        out.append(float(host[0]) / max(n, 1))
+    return out
+
+
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,

@@ -1465,6 +1465,54 @@ typedef struct CarcaCatalogueXentDesc {
 int carca_catalogue_xent_fwd(const CarcaCatalogueXentDesc* desc, void* stream);
 int carca_catalogue_xent_bwd(const CarcaCatalogueXentDesc* desc, void* stream);
 
+/* ---- row log-softmax with a temperature and per-row exclusion, forward and backward ---------
+ * The differentiable log-probability of a served policy.  P, T, the strides, the splits and the scratch's first part as
+ * for carca_catalogue_xent (ops.policy_xent_plan gives the sizes).  items [R] int32; excl [R, n_excl] int32, each row
+ * ASCENDING (any values: entries outside [1, n_items) exclude nothing; duplicates allowed), null with n_excl = 0.
+ * With z[r, i] = P[r] . T[i] / temperature: class i of row r is eligible iff 1 <= i < n_items and i is not in excl[r];
+ * row r is VALID iff items[r] is an eligible class of r.
+ *   carca_policy_xent_fwd: lse[r] = logsumexp of z[r, .] over the eligible classes, log_prob[r] = z[r, items[r]] - lse[r],
+ *     entropy[r] = -sum p log p over the eligible classes (only when the pointer is given), valid[r] = 1 / 0; lse,
+ *     log_prob and entropy are exactly 0 on rows that are not valid.  The forward's scratch holds one more
+ *     ceil64(splits_items R) words when entropy is given.
+ *   carca_policy_xent_bwd: with lse (and entropy, when h is given) from the forward, c[r] = dL/dlog_prob[r] and
+ *     h[r] = dL/dentropy[r] (null: none):
+ *     dz[r, i] = (c[r] (1[i = items[r]] - p[r, i]) - h[r] p[r, i] (log p[r, i] + entropy[r])) / temperature on the eligible
+ *     (r, i) of valid rows, 0 elsewhere;  dP = dz T (rows that are not valid and columns past d: 0), dT = dz^T P (row 0 and
+ *     columns past d: 0).  No division by n_valid and no scalar scale: c and h carry all of it.  With n_excl > 0 the
+ *     backward also takes the lists transposed: t_off [n_items + 1] offsets into t_rows, which holds for each item the
+ *     ascending VALID-ROW indices (the rank of a row among the valid rows, in row order) of the valid rows whose list names
+ *     it; only items in [1, n_items) are read.
+ * Products in exact-fp32 MFMA; the logit tiles are recomputed, never stored; no float atomics: the same call gives the
+ * same bits.  CARCA_ERR_UNSUPPORTED: d > 256, R n_excl >= 2^31.  CARCA_ERR_BADARG: as carca_catalogue_xent, a temperature
+ * that is not a finite number > 0, h without entropy, n_excl > 0 without the lists. */
+typedef struct CarcaPolicyXentDesc {
+  int R, n_items, d;
+  const float* P;
+  int ld_p;
+  const float* T;
+  int ld_t;
+  const int32_t* items;
+  float temperature;
+  const int32_t* excl; /* [R, n_excl] ascending rows, or null */
+  int n_excl;
+  const int32_t* t_off;  /* backward with n_excl > 0: [n_items + 1] */
+  const int32_t* t_rows; /* backward with n_excl > 0 */
+  int splits_items, items_per_split, splits_rows;
+  float* scratch;
+  int64_t scratch_floats;
+  float* lse;      /* [R]: forward output, backward input */
+  float* log_prob; /* [R] forward */
+  float* entropy;  /* [R] or null: forward output, backward input with h */
+  uint8_t* valid;  /* [R] forward */
+  const float* c;  /* [R] backward */
+  const float* h;  /* [R] or null, backward */
+  float* dP;       /* [R, ld_p] backward */
+  float* dT;       /* [n_items, ld_t] backward */
+} CarcaPolicyXentDesc;
+int carca_policy_xent_fwd(const CarcaPolicyXentDesc* desc, void* stream);
+int carca_policy_xent_bwd(const CarcaPolicyXentDesc* desc, void* stream);
+
 /* ---- sampled softmax cross-entropy with the logQ correction for the dot decoders ------------
  * P [R, ld_p] profile rows, Tp [R, ld_tp] the rows of their positives, S [K, ld_s] the rows of K samples shared by every
  * row (d features; ld_p, ld_tp, ld_s multiples of 4; P and S 16-byte aligned), pos [R] and s_ids [K] int32, bp [R] and
