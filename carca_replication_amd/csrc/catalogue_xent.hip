@@ -23,108 +23,49 @@
 //      grad / n_valid; padding rows get dP = 0, item 0 and the columns past d get 0.
 // No float atomics: every sum has one fixed order, so two calls give the same bits.
 // The tile skeleton (split range, both MFMA products, the running (max, sum-exp), the lane merge, the epilogue, the
-// launch sequences) is xent_tile.h's, shared with sampled_xent.hip; this file keeps its staging (straight into LDS behind
-// the barrier), its mask / G rule and its merge kernel.
-#include "xent_tile.h"
+// helper kernels, the launch sequences) is xent_tile.h's and the tile kernel xent_direct.h's, shared with policy_xent.hip;
+// this file keeps its rule (the own row's lse and pos, G = softmax - onehot), its merge kernel and its entry points.
+#include "xent_direct.h"
 
 namespace {
 
-// ---- 2. logit tiles ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cx_stage(const XentTile& A, float* dst, int first, int end, bool rows, int kpad, int tid) {
-  // rows: entries first .. end-1 are valid-row indices (P[ridx[v]]); else item ids (T[i]).  Zero past `end` and past d.
-  const int nc4 = kpad / 4;
-  for (int idx = tid; idx < XT_TILE * nc4; idx += XT_THREADS) {
-    const int row = idx / nc4, c = 4 * (idx - row * nc4);
-    const int e = first + row;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (e < end && c < A.d) {
-      const float* src = rows ? A.P + (size_t)A.ridx[e] * A.ld_p : A.T + (size_t)e * A.ld_t;
-      v = *reinterpret_cast<const f32x4*>(src + c);  // (ld % 4 == 0 and c < d <= ld: the 16 bytes lie in the row)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (c + j >= A.d) v[j] = 0.f;
-    }
-    *reinterpret_cast<f32x4*>(dst + row * A.pitch + c) = v;
-  }
-}
+// ---- 2. logit tiles: the rule for xd_tile_kernel ---------------------------------------------------------------------
+struct CatalogueRule {
+  struct Args {};
+  static constexpr int ROW_WORDS = 2;  // DT: lse and pos of each stream row
+  static constexpr bool SCALED = true, LISTS = false;
 
-// NCB: 16-column blocks the kernel is built for (d <= 16 NCB)
-template <int MODE, int NCB>
-__global__ __launch_bounds__(XT_THREADS) void cx_tile_kernel(XentTile A) {
-  extern __shared__ float cx_lds[];
-  float* own = cx_lds;
-  float* str = cx_lds + XT_TILE * A.pitch;
-  float* s_lse = str + XT_TILE * A.pitch;                       // DT: lse of the stream rows
-  int* s_pos = reinterpret_cast<int*>(s_lse + XT_TILE);         // DT: pos of the stream rows
-  const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, q = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nv = A.nv[0];
-  const int kpad = round_up(A.d, 16);
-  const int own0 = blockIdx.x * XT_TILE, split = blockIdx.y;
-  int s_begin, s_end;
-  if (MODE != XT_DT && own0 >= nv) return;  // (grid sized for R; rows past n_valid have nothing to do)
-  xt_split_range<MODE>(A, nv, split, s_begin, s_end);
-  constexpr bool OWN_ROWS = MODE != XT_DT;
-  cx_stage(A, own, own0, OWN_ROWS ? nv : A.n, OWN_ROWS, kpad, tid);
-
-  // this lane's own entry (column r16 of the wave's Z^T tiles)
-  const int o_idx = own0 + 16 * w + r16;
-  float o_lse = 0.f;
-  int o_pos = -1;
-  if constexpr (MODE == XT_DP) {
-    if (o_idx < nv) {
-      const int r = A.ridx[o_idx];
-      o_lse = A.lse[r];
-      o_pos = A.pos[r];
-    }
-  }
-  float run_m = -INFINITY, run_s = 0.f;  // FWD
-  f32x4 acc[NCB];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float* own_row = own + (16 * w + r16) * A.pitch + 4 * q;
-
-  for (int s0 = s_begin; s0 < s_end; s0 += XT_TILE) {
-    __syncthreads();  // (the previous step's readers of `str` are done)
-    cx_stage(A, str, s0, s_end, !OWN_ROWS, kpad, tid);
-    if constexpr (MODE == XT_DT) {
-      if (tid < XT_TILE) {
-        const int v = s0 + tid;
-        const int r = v < s_end ? A.ridx[v] : 0;
-        s_lse[tid] = v < s_end ? A.lse[r] : 0.f;
-        s_pos[tid] = v < s_end ? A.pos[r] : -1;
-      }
-    }
-    __syncthreads();
-    f32x4 z[4];
-    xt_logits<NCB>(A, own_row, str, r16, q, z);
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sl = 16 * n + 4 * q + j, si = s0 + sl;
-        if constexpr (MODE == XT_FWD) {
-          // items s0 + 16n + 4q + j of own row r16: id 0 and ids past the split are not classes (-inf)
-          if (!(si >= 1 && si < s_end)) z[n][j] = -INFINITY;
-        } else {
-          // G[own r16][stream 16n + 4q + j] = softmax - onehot (0 outside the valid rows / classes)
-          float g = 0.f;
-          if constexpr (MODE == XT_DP) {
-            if (o_idx < nv && si >= 1 && si < s_end) g = __expf(z[n][j] - o_lse) - (si == o_pos ? 1.f : 0.f);
-          } else {
-            if (si < s_end && o_idx >= 1 && o_idx < A.n)
-              g = __expf(z[n][j] - s_lse[sl]) - (s_pos[sl] == o_idx ? 1.f : 0.f);
-          }
-          z[n][j] = g;
-        }
-      }
-    if constexpr (MODE == XT_FWD) xt_running_update(z, run_m, run_s);
-    else xt_accumulate<NCB>(A, z, str, r16, q, acc);
+  struct Lane {};  // (no lane state beside the kernel's own lse and pos: own() is not called)
+  static __device__ __forceinline__ void stage_row(const XentTile& A, const Args&, float* s_row, int v, bool in, int tid) {
+    const int r = in ? A.ridx[v] : 0;
+    s_row[tid] = in ? A.lse[r] : 0.f;
+    reinterpret_cast<int*>(s_row + XT_TILE)[tid] = in ? A.pos[r] : -1;
   }
 
-  if constexpr (MODE == XT_FWD) xt_store_partial(A, run_m, run_s, split, o_idx, q, nv);
-  else xt_epilogue<MODE, NCB>(A, acc, nv, own0, split, w, lane);
-}
+  static __device__ __forceinline__ float logit(const Args&, float z) { return z; }
+
+  // G = softmax - onehot
+  static __device__ __forceinline__ float g_own(const f32x4 (&z)[4], int n, int j, float, int si, float o_lse,
+                                               int o_pos, const Lane&) {
+    return __expf(z[n][j] - o_lse) - (si == o_pos ? 1.f : 0.f);
+  }
+  static __device__ __forceinline__ float g_stream(const f32x4 (&z)[4], int n, int j, float, const float* s_row,
+                                                  int sl, int o_idx) {
+    return __expf(z[n][j] - s_row[sl]) - (reinterpret_cast<const int*>(s_row + XT_TILE)[sl] == o_idx ? 1.f : 0.f);
+  }
+
+  // FWD: -inf where masked; the lane's running (max, sum-exp)
+  static __device__ __forceinline__ void fwd_logit(f32x4 (&z)[4], int n, int j, float, bool ok) {
+    if (!ok) z[n][j] = -INFINITY;
+  }
+  static __device__ __forceinline__ void fwd_tile(const f32x4 (&z)[4], float& m, float& s, Lane&) {
+    xt_running_update(z, m, s);
+  }
+  static __device__ __forceinline__ void fwd_store(const XentTile& A, const Args&, float m, float s, const Lane&, int split,
+                                                   int o_idx, int q, int nv) {
+    xt_store_partial(A, m, s, split, o_idx, q, nv);
+  }
+};
 
 // ---- 3. merges (cx_mean_kernel and cx_reduce_kernel: xent_tile.h) ----------------------------------------------------
 
@@ -176,17 +117,18 @@ extern "C" int carca_catalogue_xent_fwd(const CarcaCatalogueXentDesc* desc, void
   CARCA_CHECK_ARG(desc, "catalogue_xent_fwd: null descriptor");
   const CarcaCatalogueXentDesc& D = *desc;
   XentCall C = cx_call(D);
-  return xt_forward(C, XT_KERNELS(cx_tile_kernel, XT_FWD), stream,
-                    [&](const int32_t* rpos, const float* part_m, const float* part_s) {
-                      hipLaunchKernelGGL(cx_merge_kernel, dim3((D.R + 255) / 256), dim3(256), 0, stream, D, rpos, part_m,
-                                         part_s);
-                    });
+  return xt_forward(
+      C, xd_kernels<CatalogueRule, XT_FWD>(), stream,
+      [&](const int32_t* rpos, const float* part_m, const float* part_s) {
+        hipLaunchKernelGGL(cx_merge_kernel, dim3((D.R + 255) / 256), dim3(256), 0, stream, D, rpos, part_m, part_s);
+      },
+      CatalogueRule::Args{});
 }
 
 extern "C" int carca_catalogue_xent_bwd(const CarcaCatalogueXentDesc* desc, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   CARCA_CHECK_ARG(desc, "catalogue_xent_bwd: null descriptor");
   XentCall C = cx_call(*desc);
-  return xt_backward(C, XT_KERNELS(cx_tile_kernel, XT_DP), XT_KERNELS(cx_tile_kernel, XT_DT), stream,
-                     [](const int32_t*, const int32_t*, float*, int) {});
+  return xt_backward(C, xd_kernels<CatalogueRule, XT_DP>(), xd_kernels<CatalogueRule, XT_DT>(), stream,
+                     [](const int32_t*, const int32_t*, float*, int) {}, CatalogueRule::Args{});
 }

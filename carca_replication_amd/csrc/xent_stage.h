@@ -202,7 +202,7 @@ __global__ __launch_bounds__(XT_THREADS) void xs_tile_kernel(XentTile A) {
   else xt_epilogue<MODE, NCB>(A, acc, nv, own0, split, w, lane);
 }
 
-// the tile kernels of one rule and mode, as xent_tile.h's XT_KERNELS
+// the tile kernels of one rule and mode, as xent_direct.h's xd_kernels
 #define XS_KERNELS(RULE, MODE) \
   (XentKernels{xs_tile_kernel<RULE, MODE, 4>, xs_tile_kernel<RULE, MODE, 8>, xs_tile_kernel<RULE, MODE, 16>})
 

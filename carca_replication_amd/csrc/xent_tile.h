@@ -1,22 +1,28 @@
-// The tile skeleton of the softmax cross-entropy kernels: catalogue_xent.hip (the classes are the whole catalogue,
-// DESIGN.md section 13) and sampled_xent.hip (the classes are K shared samples with the logQ correction, section 14).
-// sampled_bce.hip (a sigmoid loss over K shared samples, section 16) runs on it too.  Two tile kernels are built from it:
-// cx_tile_kernel (catalogue_xent.hip) and xs_tile_kernel (xent_stage.h), which both sampled losses instantiate, each with
-// its own rule struct.
+// The tile skeleton and host path of the softmax cross-entropy family.  Four ops run on it, through two tile kernels:
+//   xd_tile_kernel (xent_direct.h: tiles staged straight into LDS)   catalogue_xent.hip (the classes are the whole
+//       catalogue) and policy_xent.hip (the same classes under a temperature, per-row exclusion
+//       lists and per-row coefficients, with the entropy; section 29);
+//   xs_tile_kernel (xent_stage.h: tiles staged one step ahead in registers)   sampled_xent.hip (the classes are K shared
+//       samples with the logQ correction, section 14) and sampled_bce.hip (a sigmoid loss over them, section 16).
 //
 // A workgroup of four waves owns 64 rows of one operand (the "own" tile, staged once in LDS) and streams 64-row tiles of
 // the other through LDS.  Wave w owns own rows 16w .. 16w+15; lane l holds column r16 = l & 15 and the stream rows
 // 16n + 4q + j (q = l >> 4) of the 64 x 16 logit tile Z^T = S O^T, which is exactly the A operand of the second product
 // out += G * stream, so G never leaves the registers.  What lives here, once:
-//   device: the split range of a workgroup, the Z^T product, the running (max, sum-exp) update of masked logits, the
-//           G * stream accumulation, the four-lane merge with its partial store, the output epilogue with its zero tail;
-//           cx_compact_kernel (the valid rows, pos in [1, n_items), in row order), cx_mean_kernel (the fp64 mean of the
-//           row losses) and cx_reduce_kernel (split partials summed in split order, scaled by grad / n_valid);
-//   host:   the scratch layout, the checks both descriptors share, the LDS-size / NCB dispatch, and the launch sequences
-//           of the forward (compact, tile, merge, mean) and the backward (compact, dP tile, reduce, dT tile, reduce).
-// What each tile kernel keeps: how it stages a tile (cx_tile_kernel: straight into LDS; xs_tile_kernel: one tile ahead in
-// registers) and its mask tests with the lane's own-entry metadata.  What each loss keeps: the values around those tests
-// (catalogue: in its kernel; sampled: SxRule, SbRule) and its merge kernels.
+//   device: the split range of a workgroup, the direct staging of a tile, the Z^T product, the running (max, sum-exp)
+//           update of masked logits, the G * stream accumulation, the four-lane merge with its partial store, the output
+//           epilogue with its zero tail (scaled by grad / n_valid, or SCALED = false: by nothing);
+//           cx_compact_kernel (the valid rows, pos in [1, n_items) and, LISTS, not in the row's own sorted list, in row
+//           order), cx_mean_kernel (the fp64 mean of the row losses) and cx_reduce_kernel (split partials summed in split
+//           order, scaled like the epilogue);
+//   host:   the call description and scratch layout, the checks the descriptors share, the LDS-size / NCB dispatch, and
+//           the launch sequences of the forward (compact, tile, merge, and MEAN: mean) and the backward (compact, dP
+//           tile, reduce, dT tile, reduce), for a mean loss under a scalar grad (MEAN, the three losses) or per-row
+//           values under per-row coefficients (policy_xent).
+// What each tile kernel keeps: how it stages a tile and its mask tests around a rule struct's hooks.  What each client
+// keeps: its rule (CatalogueRule, PolicyRule<ENT, LISTS>; SxRule, SbRule), its merge kernel, the checks of its own
+// descriptor fields, and two short entry points; the sampled losses also their positive-term and pre-pass kernels, the
+// policy its three-value running update and lane merge for the entropy.
 #pragma once
 #include "carca_common.h"
 #include "../../include/carca_hip.h"
@@ -71,6 +77,36 @@ __device__ __forceinline__ void xt_split_range(const XentTile& A, int nv, int sp
     s_begin = (int)((long long)split * nb / A.splits) * XT_TILE;
     s_end = min((int)((long long)(split + 1) * nb / A.splits) * XT_TILE, nv);
   }
+}
+
+// A 64-row tile straight into LDS (the direct-staged kernel's staging; xs_tile_kernel has its own, through registers):
+// entries first .. end-1 are valid-row indices (rows: P[ridx[v]]) or class indices (T[i]).  Zero past `end` and past d.
+__device__ __forceinline__ void xt_stage_direct(const XentTile& A, float* dst, int first, int end, bool rows, int kpad,
+                                                int tid) {
+  const int nc4 = kpad / 4;
+  for (int idx = tid; idx < XT_TILE * nc4; idx += XT_THREADS) {
+    const int row = idx / nc4, c = 4 * (idx - row * nc4);
+    const int e = first + row;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (e < end && c < A.d) {
+      const float* src = rows ? A.P + (size_t)A.ridx[e] * A.ld_p : A.T + (size_t)e * A.ld_t;
+      v = *reinterpret_cast<const f32x4*>(src + c);  // (ld % 4 == 0 and c < d <= ld: the 16 bytes lie in the row)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c + j >= A.d) v[j] = 0.f;
+    }
+    *reinterpret_cast<f32x4*>(dst + row * A.pitch + c) = v;
+  }
+}
+
+// first index in [lo, hi) of the ascending list a whose entry is >= key
+__device__ __forceinline__ int xt_lower_bound(const int32_t* a, int lo, int hi, int key) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // Z^T[stream 16n + 4q + reg][own r16] for the four 16-row stream blocks n (own_row: the lane's own row, at column 4q).
@@ -153,14 +189,16 @@ __device__ __forceinline__ void xt_store_partial(const XentTile& A, float run_m,
   }
 }
 
-// DP / DT: D of acc[c] is column 16c + r16 of own rows 16w + 4q + j
-template <int MODE, int NCB>
+// DP / DT: D of acc[c] is column 16c + r16 of own rows 16w + 4q + j.  final_out (DT with one row split): out is the class
+// gradient itself, zeros up to the row stride and, SCALED, the grad / n_valid factor (not SCALED: no factor anywhere, and
+// neither nv's nor grad's read nor a multiply in the code)
+template <int MODE, int NCB, bool SCALED = true>
 __device__ __forceinline__ void xt_epilogue(const XentTile& A, const f32x4 (&acc)[NCB], int nv, int own0, int split, int w,
                                             int lane) {
   const int r16 = lane & 15, q = lane >> 4, ncb = (A.d + 15) / 16;
   float* out = A.out + (size_t)split * A.out_split_stride;
   float coef = 1.f;
-  if constexpr (MODE == XT_DT) {
+  if constexpr (SCALED && MODE == XT_DT) {
     if (A.final_out) coef = nv > 0 ? A.grad[0] / (float)nv : 0.f;
   }
   const int own_end = MODE == XT_DP ? nv : A.n;
@@ -171,7 +209,7 @@ __device__ __forceinline__ void xt_epilogue(const XentTile& A, const f32x4 (&acc
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int e = own0 + 16 * w + 4 * q + j;
-        if (e < own_end && col < A.ld_out) out[(size_t)e * A.ld_out + col] = col < A.d ? acc[c][j] * coef : 0.f;
+        if (e < own_end && col < A.ld_out) out[(size_t)e * A.ld_out + col] = col < A.d ? (SCALED ? acc[c][j] * coef : acc[c][j]) : 0.f;
       }
     }
   }
@@ -185,9 +223,12 @@ __device__ __forceinline__ void xt_epilogue(const XentTile& A, const f32x4 (&acc
 }
 
 // ---- valid rows, in row order -----------------------------------------------------------------------------------
+// LISTS: a row whose pos is in its own ascending list excl[r][0 .. E) is not valid either (policy_xent.hip)
+template <bool LISTS>
 __global__ __launch_bounds__(CX_COMPACT_THREADS) void cx_compact_kernel(const int32_t* __restrict__ pos, int R, int n_items,
                                                                          int32_t* __restrict__ ridx,
-                                                                         int32_t* __restrict__ rpos, int32_t* __restrict__ nv) {
+                                                                         int32_t* __restrict__ rpos, int32_t* __restrict__ nv,
+                                                                         const int32_t* __restrict__ excl, int E) {
   __shared__ int wsum[CX_COMPACT_THREADS / 64];
   __shared__ int base_s;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -196,7 +237,14 @@ __global__ __launch_bounds__(CX_COMPACT_THREADS) void cx_compact_kernel(const in
   for (int r0 = 0; r0 < R; r0 += CX_COMPACT_THREADS) {
     const int r = r0 + tid;
     const int p = r < R ? pos[r] : 0;
-    const bool ok = r < R && p >= 1 && p < n_items;
+    bool ok = r < R && p >= 1 && p < n_items;
+    if constexpr (LISTS) {
+      if (ok) {
+        const int32_t* l = excl + (size_t)r * E;
+        const int at = xt_lower_bound(l, 0, E, p);
+        ok = !(at < E && l[at] == p);
+      }
+    }
     const unsigned long long m = __ballot(ok);
     const int before = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) wsum[w] = __popcll(m);
@@ -234,7 +282,9 @@ __global__ __launch_bounds__(1024) void cx_mean_kernel(const float* __restrict__
   if (tid == 0) loss[0] = nv[0] > 0 ? (float)(red[0] / (double)nv[0]) : 0.f;
 }
 
-// dst[e][col] (col < ld_dst) = coef * sum over splits of part[s][map(e)][col] for col < d, else 0
+// dst[e][col] (col < ld_dst) = coef * sum over splits of part[s][map(e)][col] for col < d, else 0; coef = grad / n_valid,
+// or, not SCALED, no factor (nv and grad are not read)
+template <bool SCALED>
 __global__ __launch_bounds__(256) void cx_reduce_kernel(const float* __restrict__ part, int64_t split_stride, int splits,
                                                         int ld_part, const int32_t* __restrict__ rpos, int rows, int d,
                                                         float* __restrict__ dst, int ld_dst, const int32_t* __restrict__ nv,
@@ -246,8 +296,10 @@ __global__ __launch_bounds__(256) void cx_reduce_kernel(const float* __restrict_
   float v = 0.f;
   if (src >= 0 && col < d) {
     for (int s = 0; s < splits; ++s) v += part[(size_t)s * split_stride + (size_t)src * ld_part + col];
-    const int n = nv[0];
-    v *= n > 0 ? grad[0] / (float)n : 0.f;
+    if constexpr (SCALED) {
+      const int n = nv[0];
+      v *= n > 0 ? grad[0] / (float)n : 0.f;
+    }
   }
   dst[(size_t)e * ld_dst + col] = v;
 }
@@ -255,9 +307,15 @@ __global__ __launch_bounds__(256) void cx_reduce_kernel(const float* __restrict_
 // ---- host side -----------------------------------------------------------------------------------------------------
 // One call under one set of names, filled from either descriptor.  A carries the operands (R, n, n_items, d, P, T, pos,
 // ids, bias, lse, grad, per_split); the rest is what the launch sequences need beside them.
+//
+// MEAN, the host path's one compile-time switch (a template argument, so that an op's code object holds only the helper
+// kernels it launches): true for the three mean losses, whose backward scales by the scalar grad / n_valid and whose
+// forward ends with cx_mean_kernel over row_loss.  false for policy_xent: per-row outputs under per-row coefficients that
+// its tile kernel reads itself, so nothing scales (no grad, no row_loss / loss, no mean launch), and a row may carry an
+// exclusion list that the compact pass consults.
 struct XentCall {
   XentTile A;
-  const char* op;       // "catalogue_xent" / "sampled_xent" / "sampled_bce"
+  const char* op;       // "catalogue_xent" / "sampled_xent" / "sampled_bce" / "policy_xent"
   const char* classes;  // what a class is called in messages
   float* scratch;
   int64_t scratch_floats;
@@ -268,15 +326,18 @@ struct XentCall {
   float* loss;
   float* dP;  // [R, ld_p]
   float* dT;  // [n, ld_t]
+  int fwd_parts = 2;    // forward partials per (split, valid row): (max, sum-exp), and with 3 the entropy's sum
+  const int32_t* excl;  // not MEAN: [R][n_excl] by original row, each row ascending; null: no lists
+  int n_excl;
 };
 
-// scratch layout in 4-byte words (mirrored by ops._xent_plan): the row lists, nv, then the forward's (max, sum-exp) per
-// split and valid row, or the backward's dP partials [splits_n + extra_dp][R][ldo] and, with more than one row split,
+// scratch layout in 4-byte words (mirrored by ops._xent_plan): the row lists, nv, then the forward's fwd_parts partials
+// per split and valid row, or the backward's dP partials [splits_n + extra_dp][R][ldo] and, with more than one row split,
 // the class operand's partials [splits_rows][n][ldo].  The dP partials are summed into dP before the class operand's tile
 // launches (one stream), so with share_partials the second set starts where the first does and the scratch is the larger
 // of the two, not their sum.
 struct XentLayout {
-  int64_t ridx, rpos, nv, part, part2, total;
+  int64_t ridx, rpos, nv, part, part2, part3, total;  // part3: the forward's third partial (fwd_parts = 3)
 };
 inline XentLayout xt_layout(const XentCall& C, bool bwd) {
   XentLayout L;
@@ -285,9 +346,12 @@ inline XentLayout xt_layout(const XentCall& C, bool bwd) {
   L.rpos = cx_r64(R);
   L.nv = 2 * cx_r64(R);
   L.part = L.nv + 64;
+  L.part3 = 0;
   if (!bwd) {
-    L.part2 = L.part + cx_r64((int64_t)C.splits_n * R);
-    L.total = L.part2 + cx_r64((int64_t)C.splits_n * R);
+    const int64_t one = cx_r64((int64_t)C.splits_n * R);
+    L.part2 = L.part + one;
+    L.part3 = L.part2 + one;
+    L.total = L.part + C.fwd_parts * one;
   } else {
     const int64_t dp = cx_r64((int64_t)(C.splits_n + C.extra_dp) * R * ldo);
     const int64_t dt = C.splits_rows > 1 ? cx_r64((int64_t)C.splits_rows * C.A.n * ldo) : 0;
@@ -297,8 +361,9 @@ inline XentLayout xt_layout(const XentCall& C, bool bwd) {
   return L;
 }
 
-// the checks both descriptors share (each entry point checks its own operands and outputs beside these)
-inline int xt_check(const XentCall& C, const char* pass, bool bwd) {
+// the checks the descriptors share (each entry point checks its own operands and outputs beside these)
+template <bool MEAN = true>
+int xt_check(const XentCall& C, const char* pass, bool bwd) {
   const XentTile& A = C.A;
   CARCA_CHECK_ARG(A.R >= 1 && A.n >= 1 && A.n_items >= 1 && A.d >= 1, "%s_%s: the row, %s and item counts and d must be positive",
                   C.op, pass, C.classes);
@@ -320,90 +385,107 @@ inline int xt_check(const XentCall& C, const char* pass, bool bwd) {
                   (long long)C.scratch_floats, (long long)L.total);
   CARCA_CHECK_ARG(A.lse, "%s_%s: null lse", C.op, pass);
   if (!bwd) {
-    CARCA_CHECK_ARG(C.row_loss && C.loss, "%s_%s: null row_loss or loss", C.op, pass);
+    CARCA_CHECK_ARG(!MEAN || (C.row_loss && C.loss), "%s_%s: null row_loss or loss", C.op, pass);
   } else {
-    CARCA_CHECK_ARG(A.grad && C.dP && C.dT, "%s_%s: null grad or gradient output", C.op, pass);
+    CARCA_CHECK_ARG((!MEAN || A.grad) && C.dP && C.dT, "%s_%s: null grad or gradient output", C.op, pass);
   }
   return CARCA_OK;
 }
 
-// the tile kernels of one mode, built for d <= 64, 128, 256 (NCB = 4, 8, 16)
-using XentKernel = void (*)(XentTile);
-struct XentKernels {
-  XentKernel k4, k8, k16;
+// the tile kernels of one mode, built for d <= 64, 128, 256 (NCB = 4, 8, 16).  X: what the kernel takes by value after
+// XentTile (the sampled kernels: nothing; the direct-staged kernel: its rule's Args); row_words: the 4-byte words of LDS
+// the kernel keeps per stream row beside the tile
+template <class... X>
+struct XentKernelsT {
+  void (*k4)(XentTile, X...);
+  void (*k8)(XentTile, X...);
+  void (*k16)(XentTile, X...);
+  int row_words = 2;
 };
-#define XT_KERNELS(kernel, MODE) (XentKernels{kernel<MODE, 4>, kernel<MODE, 8>, kernel<MODE, 16>})
+using XentKernels = XentKernelsT<>;
 
-inline int xt_launch_tile(const XentCall& C, const XentKernels& K, const XentTile& A, int own_entries, hipStream_t stream) {
-  const size_t lds = (size_t)2 * XT_TILE * A.pitch * sizeof(float) + XT_TILE * (sizeof(float) + sizeof(int));
-  const XentKernel kern = A.d <= 64 ? K.k4 : A.d <= 128 ? K.k8 : K.k16;
+template <class... X>
+int xt_launch_tile(const XentCall& C, const XentKernelsT<X...>& K, const XentTile& A, int own_entries, hipStream_t stream,
+                   const X&... x) {
+  const size_t lds = (size_t)2 * XT_TILE * A.pitch * sizeof(float) + XT_TILE * K.row_words * sizeof(float);
+  const auto kern = A.d <= 64 ? K.k4 : A.d <= 128 ? K.k8 : K.k16;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
     carca_set_error("%s: cannot reserve %zu B of LDS: %s", C.op, lds, hipGetErrorString(e));
     return (int)e;
   }
-  hipLaunchKernelGGL(kern, dim3((own_entries + XT_TILE - 1) / XT_TILE, A.splits), dim3(XT_THREADS), lds, stream, A);
+  hipLaunchKernelGGL(kern, dim3((own_entries + XT_TILE - 1) / XT_TILE, A.splits), dim3(XT_THREADS), lds, stream, A, x...);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
 
 // the scratch pointers of a call's tile arguments, the LDS pitch, and the compact launch every call starts with
-inline int xt_begin(XentCall& C, const XentLayout& L, hipStream_t stream) {
+template <bool MEAN>
+int xt_begin(XentCall& C, const XentLayout& L, hipStream_t stream) {
   int32_t* base = reinterpret_cast<int32_t*>(C.scratch);
   C.A.ridx = base + L.ridx, C.A.nv = base + L.nv;
   C.A.pitch = round_up(C.A.d, 16) + 4;  // (+4 floats: the 16 rows of a 16-byte LDS read start 4 banks apart)
-  hipLaunchKernelGGL(cx_compact_kernel, dim3(1), dim3(CX_COMPACT_THREADS), 0, stream, C.A.pos, C.A.R, C.A.n_items,
-                     base + L.ridx, base + L.rpos, base + L.nv);
+  auto compact = cx_compact_kernel<false>;
+  if constexpr (!MEAN) {
+    if (C.excl) compact = cx_compact_kernel<true>;
+  }
+  hipLaunchKernelGGL(compact, dim3(1), dim3(CX_COMPACT_THREADS), 0, stream, C.A.pos, C.A.R, C.A.n_items, base + L.ridx,
+                     base + L.rpos, base + L.nv, C.excl, C.n_excl);
   CARCA_LAUNCH_CHECK();
   return CARCA_OK;
 }
 
-// forward: compact, FWD tile, merge(rpos, part_m, part_s) (the caller's launch: lse and row_loss), the fp64 mean
-template <class Merge>
-int xt_forward(XentCall& C, const XentKernels& fwd, hipStream_t stream, Merge merge) {
-  int rc = xt_check(C, "fwd", false);
+// forward: compact, FWD tile, merge(rpos, part_m, part_s) (the caller's launch: lse and the row's value), and, MEAN, the
+// fp64 mean.  x: the tile kernel's arguments after XentTile
+template <bool MEAN = true, class Merge, class... X>
+int xt_forward(XentCall& C, const XentKernelsT<X...>& fwd, hipStream_t stream, Merge merge, const X&... x) {
+  int rc = xt_check<MEAN>(C, "fwd", false);
   if (rc != CARCA_OK) return rc;
   const XentLayout L = xt_layout(C, false);
-  if ((rc = xt_begin(C, L, stream)) != CARCA_OK) return rc;
+  if ((rc = xt_begin<MEAN>(C, L, stream)) != CARCA_OK) return rc;
   XentTile A = C.A;
   A.splits = C.splits_n;
   A.part_m = C.scratch + L.part;
   A.part_s = C.scratch + L.part2;
-  if ((rc = xt_launch_tile(C, fwd, A, A.R, stream)) != CARCA_OK) return rc;
+  if ((rc = xt_launch_tile(C, fwd, A, A.R, stream, x...)) != CARCA_OK) return rc;
   merge(reinterpret_cast<const int32_t*>(C.scratch) + L.rpos, A.part_m, A.part_s);
   CARCA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cx_mean_kernel, dim3(1), dim3(1024), 0, stream, C.row_loss, A.R, C.loss, A.nv);
-  CARCA_LAUNCH_CHECK();
+  if constexpr (MEAN) {
+    hipLaunchKernelGGL(cx_mean_kernel, dim3(1), dim3(1024), 0, stream, C.row_loss, A.R, C.loss, A.nv);
+    CARCA_LAUNCH_CHECK();
+  }
   return CARCA_OK;
 }
 
 // a tile launch whose `splits` partials (A.out) cx_reduce_kernel then sums into dst [rows, ld_dst] with `extra` more
-inline void xt_reduce(const XentTile& A, int extra, const int32_t* rpos, int rows, float* dst, int ld_dst, hipStream_t stream) {
+template <bool MEAN>
+void xt_reduce(const XentTile& A, int extra, const int32_t* rpos, int rows, float* dst, int ld_dst, hipStream_t stream) {
   const int64_t n = (int64_t)rows * ld_dst;
-  hipLaunchKernelGGL(cx_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A.out, A.out_split_stride,
-                     A.splits + extra, A.ld_out, rpos, rows, A.d, dst, ld_dst, A.nv, A.grad);
+  hipLaunchKernelGGL(cx_reduce_kernel<MEAN>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, A.out,
+                     A.out_split_stride, A.splits + extra, A.ld_out, rpos, rows, A.d, dst, ld_dst, A.nv, A.grad);
 }
 
 // backward: compact; the dP tile, extra(rpos, nv, part, ldo) (the caller's launch writing the extra_dp partials; unused
 // with none), the partials summed per original row (padding rows: 0); the dT tile, where one row split writes dT itself
-// and more write partials summed per class
-template <class Extra>
-int xt_backward(XentCall& C, const XentKernels& dp, const XentKernels& dt, hipStream_t stream, Extra extra) {
-  int rc = xt_check(C, "bwd", true);
+// and more write partials summed per class.  x: the tile kernels' arguments after XentTile
+template <bool MEAN = true, class Extra, class... X>
+int xt_backward(XentCall& C, const XentKernelsT<X...>& dp, const XentKernelsT<X...>& dt, hipStream_t stream, Extra extra,
+                const X&... x) {
+  int rc = xt_check<MEAN>(C, "bwd", true);
   if (rc != CARCA_OK) return rc;
   const XentLayout L = xt_layout(C, true);
-  if ((rc = xt_begin(C, L, stream)) != CARCA_OK) return rc;
+  if ((rc = xt_begin<MEAN>(C, L, stream)) != CARCA_OK) return rc;
   const int ldo = (C.A.d + 3) / 4 * 4;
   const int32_t* rpos = reinterpret_cast<const int32_t*>(C.scratch) + L.rpos;
   XentTile A = C.A;
   A.splits = C.splits_n;
   A.out = C.scratch + L.part, A.out_split_stride = (int64_t)A.R * ldo, A.ld_out = ldo;
-  if ((rc = xt_launch_tile(C, dp, A, A.R, stream)) != CARCA_OK) return rc;
+  if ((rc = xt_launch_tile(C, dp, A, A.R, stream, x...)) != CARCA_OK) return rc;
   if (C.extra_dp) {
     extra(rpos, A.nv, A.out + (size_t)C.splits_n * A.out_split_stride, ldo);
     CARCA_LAUNCH_CHECK();
   }
-  xt_reduce(A, C.extra_dp, rpos, A.R, C.dP, A.ld_p, stream);
+  xt_reduce<MEAN>(A, C.extra_dp, rpos, A.R, C.dP, A.ld_p, stream);
   CARCA_LAUNCH_CHECK();
   XentTile B = C.A;
   B.splits = C.splits_rows;
@@ -412,9 +494,9 @@ int xt_backward(XentCall& C, const XentKernels& dp, const XentKernels& dt, hipSt
   } else {
     B.out = C.scratch + L.part2, B.out_split_stride = (int64_t)B.n * ldo, B.ld_out = ldo;
   }
-  if ((rc = xt_launch_tile(C, dt, B, B.n, stream)) != CARCA_OK) return rc;
+  if ((rc = xt_launch_tile(C, dt, B, B.n, stream, x...)) != CARCA_OK) return rc;
   if (C.splits_rows > 1) {
-    xt_reduce(B, 0, nullptr, B.n, C.dT, B.ld_t, stream);
+    xt_reduce<MEAN>(B, 0, nullptr, B.n, C.dT, B.ld_t, stream);
     CARCA_LAUNCH_CHECK();
   }
   return CARCA_OK;

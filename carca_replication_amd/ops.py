@@ -1390,11 +1390,12 @@ CX_WAVES_PER_CU = 4  # the split counts aim at this many workgroups per CU
 
 
 def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: int,
-               share_partials: bool = False) -> Tuple[int, int, int, int, int]:
+               share_partials: bool = False, fwd_parts: int = 2) -> Tuple[int, int, int, int, int]:
     """(class splits, classes per split, row splits, forward scratch, backward scratch) of either loss, the layout
     csrc/xent_tile.h checks.  The classes are split so that the forward's and dP's (row block x class split) grid has about
     CX_WAVES_PER_CU workgroups per CU, the rows of the class gradient's (class block x row split) grid likewise.  Scratch in
-    4-byte words: 2 ceil64(R) + 64 of row lists, then the forward's (max, sum-exp) partials, or the backward's dP partials
+    4-byte words: 2 ceil64(R) + 64 of row lists, then the forward's fwd_parts partials per (split, row) ((max, sum-exp);
+    policy_xent: and the entropy's sum; XentCall::fwd_parts), or the backward's dP partials
     [class splits + extra_dp_partials, R, ld] and, with more than one row split, the class gradient's
     [row splits, n_classes, ld], ld = round_up(d, 4); with share_partials the two sets share their words (the larger
     of the two, not the sum: XentCall::share_partials)."""
@@ -1408,7 +1409,7 @@ def _xent_plan(R: int, n_classes: int, d: int, n_cus: int, extra_dp_partials: in
     s_c = -(-n_classes // per)  # (no empty split)
     s_r = max(1, min(n_row_blocks, CX_MAX_SPLITS, -(-target // n_class_blocks)))
     head = 2 * r64(R) + 64
-    fwd = head + 2 * r64(s_c * R)
+    fwd = head + fwd_parts * r64(s_c * R)
     dp, dt = r64((s_c + extra_dp_partials) * R * ldo), (r64(s_r * n_classes * ldo) if s_r > 1 else 0)
     bwd = head + (max(dp, dt) if share_partials else dp + dt)
     return s_c, per, s_r, fwd, bwd
@@ -1448,11 +1449,18 @@ def _xent_splits(D, plan: dict, split_fields, scratch_key: str, device, keep: li
     return D
 
 
-def _xent_desc(P: Tensor, T: Tensor, pos: Tensor, d: int, scratch_key: str, plan: dict, keep: list):
-    D = _lib.CatalogueXentDesc()
+def _xent_operands(D, P: Tensor, T: Tensor, d: int, scratch_key: str, plan: dict, keep: list):
+    """The fields the catalogue's and the policy's descriptors share: R, n_items, d, P, T with their strides, and plan's
+    splits and scratch."""
     D.R, D.n_items, D.d = P.shape[0], T.shape[0], d
-    D.P, D.ld_p, D.T, D.ld_t, D.pos = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0), pos.data_ptr()
+    D.P, D.ld_p, D.T, D.ld_t = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0)
     return _xent_splits(D, plan, ("splits_items", "items_per_split", "splits_rows"), scratch_key, P.device, keep)
+
+
+def _xent_desc(P: Tensor, T: Tensor, pos: Tensor, d: int, scratch_key: str, plan: dict, keep: list):
+    D = _xent_operands(_lib.CatalogueXentDesc(), P, T, d, scratch_key, plan, keep)
+    D.pos = pos.data_ptr()
+    return D
 
 
 def catalogue_xent_fwd(P: Tensor, T: Tensor, pos: Tensor, d: int) -> Tuple[Tensor, Tensor]:
@@ -1528,9 +1536,8 @@ def policy_xent_plan(R: int, n_items: int, d: int, n_cus: int = 256) -> dict:
     scratch; the forward's scratch holds a third partial per (split, row), the entropy's."""
     if R < 1 or n_items < 1 or d < 1:
         raise CarcaHipError("policy_xent_plan: R, n_items and d must be positive")
-    s_i, per, s_r, fwd, bwd = _xent_plan(R, n_items, d, n_cus, 0)
-    return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r,
-                scratch_fwd=fwd + (s_i * R + 63) // 64 * 64, scratch_bwd=bwd)
+    s_i, per, s_r, fwd, bwd = _xent_plan(R, n_items, d, n_cus, 0, fwd_parts=3)
+    return dict(splits_items=s_i, items_per_split=per, splits_rows=s_r, scratch_fwd=fwd, scratch_bwd=bwd)
 
 
 def policy_temperature(what: str, temperature) -> float:
@@ -1588,15 +1595,13 @@ def policy_transposed_lists(excl_sorted: Tensor, valid: Tensor, n_items: int) ->
 def _policy_desc(P: Tensor, T: Tensor, items: Tensor, d: int, t32: float, excl_sorted: Optional[Tensor], scratch_key: str,
                  keep: list):
     plan = policy_xent_plan(P.shape[0], T.shape[0], d, num_cus())
-    D = _lib.PolicyXentDesc()
-    D.R, D.n_items, D.d = P.shape[0], T.shape[0], d
-    D.P, D.ld_p, D.T, D.ld_t, D.items = P.data_ptr(), P.stride(0), T.data_ptr(), T.stride(0), items.data_ptr()
-    D.temperature = t32
+    D = _xent_operands(_lib.PolicyXentDesc(), P, T, d, scratch_key, plan, keep)
+    D.items, D.temperature = items.data_ptr(), t32
     if excl_sorted is not None:
         if excl_sorted.dtype != torch.int32 or not excl_sorted.is_contiguous() or excl_sorted.shape[0] != P.shape[0]:
             raise CarcaHipError("policy_xent: the exclusion list must be policy_exclusion's (int32 [R, E], contiguous)")
         D.excl, D.n_excl = excl_sorted.data_ptr(), excl_sorted.shape[1]
-    return _xent_splits(D, plan, ("splits_items", "items_per_split", "splits_rows"), scratch_key, P.device, keep)
+    return D
 
 
 def policy_xent_fwd(P: Tensor, T: Tensor, items: Tensor, d: int, temperature: float, excl_sorted: Optional[Tensor] = None,

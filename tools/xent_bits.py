@@ -1,13 +1,18 @@
-"""Bit fingerprints of the tile-kernel losses (csrc/catalogue_xent.hip, csrc/sampled_xent.hip, csrc/sampled_bce.hip over
-csrc/xent_tile.h and csrc/xent_stage.h; DESIGN.md sections 13, 14 and 16): for a fixed list of seeded cases, one sha256
-per output tensor of ops.catalogue_xent_fwd / _bwd, ops.sampled_xent_fwd / _bwd and ops.sampled_bce_fwd / _bwd, over the
-bytes of the whole strided buffer (so the zero columns past d count).  Every sum in these kernels has one fixed order,
+"""Bit fingerprints of the tile-kernel losses (csrc/catalogue_xent.hip, csrc/sampled_xent.hip, csrc/sampled_bce.hip and
+csrc/policy_xent.hip over csrc/xent_tile.h, csrc/xent_stage.h and csrc/xent_direct.h; DESIGN.md sections 13, 14, 16 and
+29): for a fixed list of seeded cases, one sha256 per output tensor of ops.catalogue_xent_fwd / _bwd, ops.sampled_xent_fwd
+/ _bwd, ops.sampled_bce_fwd / _bwd and ops.policy_xent_fwd / _bwd, over the bytes of the whole strided buffer (so the zero
+columns past d count).  Every sum in these kernels has one fixed order,
 so a change that only moves code must leave every line as it was: run the script once per build (a fresh process each,
 --package-root naming the tree whose package is imported) on the same machine and compare the listings line for line.
 The hashes depend on the CU count through the split plan (first line).  The cases: d in {64, 90, 128, 192, 256} with row strides past d; padding rows (pos 0, pos >=
 n_items, negative); R = 1; one and several row splits, several class splits with a short last one; sample ids that are
 invalid, repeated, or equal to a row's positive; a batch without a valid row; the two benchmark shapes.  gBCE runs the
 sampled shapes twice, with the context rows C and without, after the softmax losses' lines (which keep their seeds).
+The policy lines come last, over the catalogue's shapes at temperature 0.5 with row gradients c and h of mixed sign:
+without lists and entropy (policy/), with the entropy (policy_ent/), with lists of 7 ids holding a duplicate, a 0, a
+negative id, an id past the end and, on every fifth row, the row's own item (policy_e7/), with lists of 70 (policy_e70/),
+and with every row's own item in its list, so that no row is valid (policy_none/); the list cases compute the entropy.
 usage: python tools/xent_bits.py [--package-root DIR] [--out listing.txt]"""
 import argparse
 import hashlib
@@ -117,6 +122,27 @@ def bce_case(seed, with_c, name, R, K, d, ld, valid):
     return [(f"{tag}/{name}/{k}", _sha(v)) for k, v in outs if v is not None]
 
 
+def policy_case(seed, kind, name, R, n_items, d, ld, valid):
+    g = torch.Generator().manual_seed(seed)
+    P, T = _operand(g, R, d, ld), _operand(g, n_items, d, ld)
+    items = _pos(g, R, n_items, valid)
+    c, h = torch.randn(R, generator=g).cuda(), (torch.randn(R, generator=g) * 0.01).cuda()
+    E = dict(policy=0, policy_ent=0, policy_e7=7, policy_e70=70, policy_none=7)[kind]
+    ent = kind != "policy"
+    ex = None
+    if E:
+        excl = torch.randint(1, n_items, (R, E), generator=g, dtype=torch.int32)
+        excl[:, 0], excl[:, 1], excl[:, 2], excl[:, 3] = 0, -5, n_items + 3, excl[:, 4]
+        own = slice(None) if kind == "policy_none" else slice(2, None, 5)
+        excl[own, 5] = items[own]
+        ex = ops.policy_exclusion(excl.cuda(), R, n_items)
+    items = items.cuda()
+    log_prob, ok, H, lse = ops.policy_xent_fwd(P, T, items, d, 0.5, ex, ent)
+    dP, dT = ops.policy_xent_bwd(P, T, items, d, 0.5, ex, lse, c, h if ent else None, H, ok)
+    outs = (("log_prob", log_prob), ("valid", ok), ("entropy", H), ("lse", lse), ("dP", dP), ("dT", dT))
+    return [(f"{kind}/{name}/{k}", _sha(v)) for k, v in outs if v is not None]
+
+
 def main():
     assert torch.cuda.is_available(), "xent_bits.py needs a GPU"
     lines = [f"# cus={ops.num_cus()}"]
@@ -127,6 +153,9 @@ def main():
     for with_c in (True, False):
         for i, shape in enumerate(SHAPES + [BENCH_SAMPLED]):
             lines += [f"{k} {h}" for k, h in bce_case(300 + i, with_c, *shape)]
+    for j, kind in enumerate(("policy", "policy_ent", "policy_e7", "policy_e70", "policy_none")):
+        for i, shape in enumerate(SHAPES + [BENCH_CATALOGUE]):
+            lines += [f"{k} {h}" for k, h in policy_case(400 + 20 * j + i, kind, *shape)]
     torch.cuda.synchronize()
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
