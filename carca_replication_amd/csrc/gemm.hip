@@ -9,6 +9,7 @@
 // Kernels in this file (gemm_rows_choose + gemm_rows_dispatch at the bottom pick one from the shape):
 //   gemm_rows_cu_kernel      ONE 384 x 96 block per CU, hand-scheduled K step: the feature GEMM (see its own comment)
 //   gemm_rows_sk_kernel, gemm_rows_skc_kernel   the same tiles with stream-K hand-over of partial tiles (their own comments)
+//                            (all three are clients of cu_tile; the tile's pieces: gemm_tile384.h)
 //   gemm_rows_n96_kernel     one 80 x 96 block per CU: narrow outputs over about one round of rows
 //   gemm_rows_kernel<128,96> block tile 128 x 96, K step 32, 4 waves, wave w owns rows 32w..32w+31 x all 96 columns
 //                            (3 accumulator tiles), 3 blocks per CU: large products whose grid does not suit the
@@ -24,6 +25,7 @@
 #include <vector>
 #include "../../include/carca_hip.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile384.h"
 #include <cstring>
 #include <string>
 
@@ -142,17 +144,11 @@ __device__ __forceinline__ void gemm_rows_body(const GemmDev& args, const int id
   __shared__ __attribute__((aligned(16))) float Bs[BN * LS];
 
   const CarcaGemmDesc& D = args.d;
-  // ---- block id -> (row block, col block): ids that are equal mod 8 land on one XCD under round-robin placement;
-  // renumber them contiguously per XCD (bijective for any grid size, no phantom blocks: a padded grid can push real
-  // blocks into a second round when the grid is sized to the chip) so that the column blocks of a row block share an L2
-  const int total = args.nrb * args.ncb;
-  const int xcd = id & 7, q8 = total >> 3, r8 = total & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+  // ---- block id -> (row block, col block), the column blocks of a row block on one XCD (no phantom blocks: a padded grid
+  // can push real blocks into a second round when the grid is sized to the chip)
+  const int wg = tile384::xcd_swizzle(id, args.nrb * args.ncb);
   const int rb = wg / args.ncb, cb = wg - rb * args.ncb;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < CARCA_MAX_SEGS; ++i)
-    if (i < D.nseg && rb >= args.rb_start[i]) s = i;
+  const int s = tile384::seg_of(D, args.rb_start, rb);
   const CarcaGemmSeg sg = D.seg[s];
   const int row0 = (rb - args.rb_start[s]) * BM;  // first row of this block inside the segment
   const int n0 = cb * BN;
@@ -175,15 +171,7 @@ __device__ __forceinline__ void gemm_rows_body(const GemmDev& args, const int id
     aoff1[i] = sg.a1_bstride ? (size_t)ub * sg.a1_bstride + (size_t)ut * D.lda1 : (size_t)gr * D.lda1;
   }
 
-  auto load4 = [](const float* p, bool full, int kk, int klen) -> f32x4 {
-    if (full) return *reinterpret_cast<const f32x4_u*>(p);
-    f32x4 v;
-    v[0] = kk + 0 < klen ? p[0] : 0.f;
-    v[1] = kk + 1 < klen ? p[1] : 0.f;
-    v[2] = kk + 2 < klen ? p[2] : 0.f;
-    v[3] = kk + 3 < klen ? p[3] : 0.f;
-    return v;
-  };
+  using tile384::load4;
   // BUF: full tiles are fetched with buffer loads (scalar resource + 32-bit lane offset + scalar k offset; see
   // gload4 in carca_common.h for why) -- the launcher sets it when every offset provably fits 32 bits
   auto load_tile = [&](int t, f32x4 (&ra_)[A_PER], f32x4 (&rb_)[B_PER]) {
@@ -333,316 +321,17 @@ __global__ __launch_bounds__((BM / 32) * 64) void gemm_rows_group_kernel(const G
 }
 
 // ---------------------------------------------------------------------------------------------------
-// gemm_rows_cu_kernel: the same product for the ONE launch that carries 97 % of the model's flops
-// (feats_embed at n_attrs = 4096: ~19k rows x 4102 x 450).  One 768-thread block per CU, tile 384 x 96:
-// 36 of the 9060 32x32 output tiles per CU (255 blocks on 256 CUs, one round) like the 128 x 96 kernel's
-// three co-resident blocks, but the B tile is staged once instead of three times (107 instead of
-// 149 bytes through L1 per MFMA).  With a single lock-stepped block nothing else covers a wave's
-// non-MFMA instructions, and the SIMD serves its three waves oldest-first (measured: barrier waits
-// 4200 / 2200 / 300 cycles per step for the 1st / 2nd / 3rd wave of a SIMD), so the step is scheduled
-// by hand: every LDS read, LDS write and global load sits in the shadow of one of the wave's own
-// MFMAs, fragments are double-buffered in registers one 8-k group ahead, LDS is double-buffered so
-// that there is ONE barrier per K step, global loads run two tiles ahead on a scalar base + constant
-// per-lane offsets (no address arithmetic in the loop), and all LDS addresses are immediates.
-// TN = 3: tile 384 x 96 (the C2 feature GEMM: 5 column blocks of N = 450).  TN = 4: tile 384 x 128 for N that 128-wide
-// blocks cover in one round where 96-wide ones need two (g = 640: 5 x 51 = 255 blocks instead of 7 x 51 = 357); its B
-// tile is 1024 staging slots for 768 threads: every thread carries two, the second one live for threads 0..255 and a
-// clamped load + a store into a dummy LDS strip for the others (the pipelined body stays branch-free).
-template <int DBG, int TN = 3>
-__global__ __launch_bounds__(768) void gemm_rows_cu_kernel(const GemmDev args) {
-  constexpr int BM = 384, BN = 32 * TN, BK = 32, NW = 12, NT = 768, LS = BK + 4, C4 = BK / 4;
-  constexpr int A_PER = BM * C4 / NT, B_PER = (BN * C4 + NT - 1) / NT;  // 4 + 1 (or 2) staged float4 per thread and tile
-  static_assert(TN == 3 || TN == 4, "column tiles per block");
-  constexpr int A_BUF = BM * LS, B_BUF = BN * LS;  // floats per LDS buffer
-  constexpr int DUMMY = (B_PER * NT > BN * C4) ? (B_PER * NT - BN * C4) * 4 : 0;  // floats: dead B slots land here
-  __shared__ __attribute__((aligned(16))) float As[2 * A_BUF];
-  __shared__ __attribute__((aligned(16))) float Bs[2 * B_BUF + DUMMY];
-
-  const CarcaGemmDesc& D = args.d;
-  const int id = blockIdx.x, total = args.nrb * args.ncb;
-  if (args.has_pas && id == total) {  // the passenger: this workgroup only copies item rows (an otherwise idle CU)
-    carca_gather_rows<16>(args.pas, (int)threadIdx.x >> 6, NW, (int)threadIdx.x & 63);
-    return;
-  }
-  const int xcd = id & 7, q8 = total >> 3, r8 = total & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-  const int rb = wg / args.ncb, cb = wg - rb * args.ncb;
-  int s = 0;
-#pragma unroll
-  for (int i = 1; i < CARCA_MAX_SEGS; ++i)
-    if (i < D.nseg && rb >= args.rb_start[i]) s = i;
-  const CarcaGemmSeg sg = D.seg[s];
-  const int row0 = (rb - args.rb_start[s]) * BM;
-  const int n0 = cb * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nfast = D.K0 / BK;  // full tiles of k-source 0: the pipelined loop
-  const int nt0 = (D.K0 + BK - 1) / BK, nt1 = (D.K1 + BK - 1) / BK;
-  const int ntiles = nt0 + nt1;
-
-  // ---- staging slots: element offsets are loop invariants; the fast loop adds them to a scalar base ----
-  size_t aoff0[A_PER], aoff1[A_PER];
-  unsigned a_byte[A_PER];  // byte offset of the slot's 16 bytes inside tile 0 of k-source 0 (host: < 4 GiB)
-  int a_lds[A_PER];        // float index inside an A buffer
-#pragma unroll
-  for (int i = 0; i < A_PER; ++i) {
-    const int slot = tid + i * NT, r = slot / C4, c4 = slot - r * C4;
-    const int gr = min(row0 + r, sg.rows - 1);
-    const int ub = gr / sg.T, ut = gr - ub * sg.T;
-    aoff0[i] = sg.a0_gather ? (size_t)sg.ids[gr] * D.lda0
-               : sg.a0_bstride ? (size_t)ub * sg.a0_bstride + (size_t)ut * D.lda0
-                               : (size_t)gr * D.lda0;
-    aoff1[i] = sg.a1_bstride ? (size_t)ub * sg.a1_bstride + (size_t)ut * D.lda1 : (size_t)gr * D.lda1;
-    a_byte[i] = (unsigned)((aoff0[i] + c4 * 4) * sizeof(float));
-    a_lds[i] = r * LS + c4 * 4;
-  }
-  int b_gn[B_PER], b_c4[B_PER];
-  int b_at[2][B_PER];  // float index inside Bs of the slot's 16 bytes, per LDS buffer (dead slots: the dummy strip)
-  unsigned b_byte[B_PER];
-#pragma unroll
-  for (int i = 0; i < B_PER; ++i) {
-    const int slot = tid + i * NT;
-    const bool live = DUMMY == 0 || slot < BN * C4;
-    const int r = live ? slot / C4 : 0;
-    b_c4[i] = slot % C4;
-    b_gn[i] = min(n0 + r, D.N - 1);
-    b_byte[i] = (unsigned)(((size_t)b_gn[i] * D.ldb0 + b_c4[i] * 4) * sizeof(float));
-    b_at[0][i] = live ? r * LS + b_c4[i] * 4 : 2 * B_BUF + (slot - BN * C4) * 4;
-    b_at[1][i] = live ? B_BUF + r * LS + b_c4[i] * 4 : 2 * B_BUF + (slot - BN * C4) * 4;
-  }
-
-  f32x4 ra[A_PER], rbv[B_PER];
-  // Buffer loads: scalar resource + 32-bit per-lane offset + scalar tile offset -- no address arithmetic in the
-  // loop and half the address data of a 64-bit global_load per instruction.
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sg.a0, 0, -1, 0x00020000);
-  const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)D.bt0, 0, -1, 0x00020000);
-  int k_byte = 0;  // scalar: byte offset of the NEXT tile to load inside a row
-  auto load_fast = [&](int i) {  // slot i of that tile (i >= A_PER: B slot i - A_PER)
-    const int ia = i < A_PER ? i : 0, ib = i < A_PER ? 0 : i - A_PER;
-    const u32x4 v = i < A_PER ? __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_byte[ia], k_byte, 0)
-                              : __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_byte[ib], k_byte, 0);
-    f32x4 f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(v[e]);
-    if (i < A_PER)
-      ra[ia] = f;
-    else
-      rbv[ib] = f;
-  };
-  auto store_slot = [&](int i, int buf) {
-    if (i < A_PER) {
-      *reinterpret_cast<f32x4*>(&As[buf * A_BUF + a_lds[i]]) = ra[i];
-    } else {
-      // (dead slots -- the second B slot of threads >= 256 at TN = 4 -- write their own 16 bytes of the dummy strip)
-      *reinterpret_cast<f32x4*>(&Bs[b_at[buf][i - A_PER]]) = rbv[i - A_PER];
-    }
-  };
-  auto load4 = [](const float* p, bool full, int kk, int klen) -> f32x4 {
-    if (full) return *reinterpret_cast<const f32x4_u*>(p);
-    f32x4 v;
-    v[0] = kk + 0 < klen ? p[0] : 0.f;
-    v[1] = kk + 1 < klen ? p[1] : 0.f;
-    v[2] = kk + 2 < klen ? p[2] : 0.f;
-    v[3] = kk + 3 < klen ? p[3] : 0.f;
-    return v;
-  };
-  auto load_tail = [&](int t) {  // any tile, either k-source, ragged K (the few tiles behind the fast loop)
-    const bool src1 = t >= nt0;
-    const int k0 = (src1 ? t - nt0 : t) * BK;
-    const int klen = src1 ? D.K1 : D.K0;
-    const float* abase = src1 ? sg.a1 : sg.a0;
-    const float* bbase = src1 ? D.bt1 : D.bt0;
-    const int ldb = src1 ? D.ldb1 : D.ldb0;
-    const bool full = k0 + BK <= klen;
-#pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-      const int c4 = (tid + i * NT) % C4;
-      ra[i] = load4(abase + (src1 ? aoff1[i] : aoff0[i]) + k0 + c4 * 4, full, k0 + c4 * 4, klen);
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i)
-      rbv[i] = load4(bbase + (size_t)b_gn[i] * ldb + k0 + b_c4[i] * 4, full, k0 + b_c4[i] * 4, klen);
-  };
-
-  f32x16 acc[TN];
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[tn][r] = 0.f;
-
-  const int lr = lane & 31, lh = lane >> 5;
-  const float* a_frag = &As[(wave * 32 + lr) * LS + 4 * lh];
-  const float* b_frag = &Bs[lr * LS + 4 * lh];
-  f32x4 fa0, fa1, fb0[TN], fb1[TN];  // fragment sets of two consecutive 8-k groups
-
-#define CARCA_PIN() __builtin_amdgcn_sched_barrier(0)
-  // fragment read j of group kg from LDS buffer `buf` into set (fa, fb): j = 0 is A, 1..3 the B tiles
-  auto read_frag = [&](int j, int buf, int kg, f32x4& fa, f32x4(&fb)[TN]) {
-    if (j == 0)
-      fa = *reinterpret_cast<const f32x4*>(a_frag + buf * A_BUF + kg * 8);
-    else
-      fb[j - 1] = *reinterpret_cast<const f32x4*>(b_frag + buf * B_BUF + (j - 1) * 32 * LS + kg * 8);
-  };
-  // 4 TN MFMAs of one 8-k group; aux(i) is issued behind MFMA i and must be independent of it
-  constexpr int NR = TN + 1;  // fragment reads per group: A, then the TN B tiles
-  auto mfma_group = [&](const f32x4& fa, const f32x4(&fb)[TN], auto&& aux) {
-#pragma unroll
-    for (int i = 0; i < 4 * TN; ++i) {
-      acc[i % TN] = mfma32(fa[i / TN], fb[i % TN][i / TN], acc[i % TN]);
-      CARCA_PIN();
-      aux(i);
-      CARCA_PIN();
-    }
-  };
-  unsigned long long w_vm = 0, w_bar = 0, t_begin = 0;
-
-  // one K step on tile t (LDS buffer CUR); tile t+1 is in registers, tile t+2 gets loaded
-  // one K step on tile t (LDS buffer CUR); tile t+1 is in registers, tile t+2 gets loaded.  Gaps 0..3 of every group
-  // carry the fragment reads of the next group; gaps 4..8 of group 1 the LDS writes of tile t+1 and gaps 4..8 of
-  // group 2 the loads of tile t+2 (behind the writes: the staging registers are reused).
-  auto step = [&](auto cur_tag, int t) {
-    constexpr int CUR = decltype(cur_tag)::value, NXT = CUR ^ 1;
-    const bool has1 = t + 1 < nfast, has2 = t + 2 < nfast;
-    mfma_group(fa0, fb0, [&](int i) {
-      if (i < NR) read_frag(i, CUR, 1, fa1, fb1);
-    });
-    if constexpr (DBG) {
-      const unsigned long long ta = __builtin_amdgcn_s_memtime();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      w_vm += __builtin_amdgcn_s_memtime() - ta;
-      CARCA_PIN();
-    }
-    static_assert(NR + A_PER + B_PER <= 4 * TN, "a group's gaps hold its reads and the tile's staging slots");
-    mfma_group(fa1, fb1, [&](int i) {
-      if (i < NR)
-        read_frag(i, CUR, 2, fa0, fb0);
-      else if (i < NR + A_PER + B_PER && has1)
-        store_slot(i - NR, NXT);
-    });
-    mfma_group(fa0, fb0, [&](int i) {
-      if (i < NR)
-        read_frag(i, CUR, 3, fa1, fb1);
-      else if (i < NR + A_PER + B_PER && has2)
-        load_fast(i - NR);
-    });
-    if (has2) k_byte += BK * sizeof(float);
-    CARCA_PIN();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own LDS writes of tile t+1 and reads of tile t retired
-    if constexpr (DBG) {
-      const unsigned long long tb = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_s_barrier();
-      w_bar += __builtin_amdgcn_s_memtime() - tb;
-    } else {
-      __builtin_amdgcn_s_barrier();  // raw: the loads of tile t+2 stay in flight across it
-    }
-    CARCA_PIN();
-    mfma_group(fa1, fb1, [&](int i) {
-      if (i < NR && has1) read_frag(i, NXT, 0, fa0, fb0);
-    });
-  };
-
-  if (nfast > 0) {
-    // prologue: tile 0 -> LDS buffer 0, tile 1 -> registers
-#pragma unroll
-    for (int i = 0; i < A_PER + B_PER; ++i) load_fast(i);
-    k_byte += BK * sizeof(float);
-#pragma unroll
-    for (int i = 0; i < A_PER + B_PER; ++i) store_slot(i, 0);
-    if (nfast > 1) {
-#pragma unroll
-      for (int i = 0; i < A_PER + B_PER; ++i) load_fast(i);
-      k_byte += BK * sizeof(float);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NR; ++j) read_frag(j, 0, 0, fa0, fb0);
-    if constexpr (DBG) t_begin = __builtin_amdgcn_s_memtime();
-    int t = 0;
-    for (; t + 1 < nfast; t += 2) {
-      step(std::integral_constant<int, 0>{}, t);
-      step(std::integral_constant<int, 1>{}, t + 1);
-    }
-    if (t < nfast) step(std::integral_constant<int, 0>{}, t);
-    if constexpr (DBG) {
-      if (args.dbg && lane == 0) {
-        unsigned long long* o = args.dbg + ((size_t)blockIdx.x * NW + wave) * 4;
-        o[0] = __builtin_amdgcn_s_memtime() - t_begin;
-        o[1] = w_vm;
-        o[2] = w_bar;
-        o[3] = 0;
-      }
-    }
-  }
-#undef CARCA_PIN
-  // ---- tail tiles (ragged end of k-source 0, all of k-source 1): plain load -> LDS -> multiply ----
-  // (the context columns as ONE 8-k group where they are all of the tail: see cu_tile)
-  const bool ctx8 = D.K1 >= 4 && D.K1 <= 8 && D.K0 % BK == 0 && !(args.diag & 64);
-  if (ctx8) {
-    const int xr = tid >> 1, xh = tid & 1;
-    const int cs = min(4 * xh, D.K1 - 4), sh = 4 * xh - cs;
-    const int gr = min(row0 + xr, sg.rows - 1);
-    const int ub = gr / sg.T, ut = gr - ub * sg.T;
-    const size_t ao = sg.a1_bstride ? (size_t)ub * sg.a1_bstride + (size_t)ut * D.lda1 : (size_t)gr * D.lda1;
-    const bool bx_live = tid < 2 * BN;
-    const f32x4 av = *reinterpret_cast<const f32x4_u*>(sg.a1 + ao + cs);
-    const f32x4 bv = *reinterpret_cast<const f32x4_u*>(D.bt1 + (size_t)min(n0 + (bx_live ? xr : 0), D.N - 1) * D.ldb1 + cs);
-    auto fix = [&](const f32x4 v) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x = sh == 0 ? v[e] : (sh == 1 ? v[(e + 1) & 3] : (sh == 2 ? v[(e + 2) & 3] : v[(e + 3) & 3]));
-        o[e] = (4 * xh + e < D.K1) ? x : 0.f;
-      }
-      return o;
-    };
-    __syncthreads();  // every wave is done with both LDS buffers
-    *reinterpret_cast<f32x4*>(&As[xr * LS + xh * 4]) = fix(av);
-    if (bx_live) *reinterpret_cast<f32x4*>(&Bs[xr * LS + xh * 4]) = fix(bv);
-    __syncthreads();
-    const f32x4 a = *reinterpret_cast<const f32x4*>(a_frag);
-    f32x4 b[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) b[tn] = *reinterpret_cast<const f32x4*>(b_frag + tn * 32 * LS);
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) acc[tn] = mfma32(a[st], b[tn][st], acc[tn]);
-  }
-  for (int t = ctx8 ? ntiles : nfast; t < ntiles; ++t) {
-    load_tail(t);
-    __syncthreads();  // every wave is done with both LDS buffers
-#pragma unroll
-    for (int i = 0; i < A_PER + B_PER; ++i) store_slot(i, 0);
-    __syncthreads();
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(a_frag + kg * 8);
-      f32x4 b[TN];
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) b[tn] = *reinterpret_cast<const f32x4*>(b_frag + tn * 32 * LS + kg * 8);
-#pragma unroll
-      for (int st = 0; st < 4; ++st)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) acc[tn] = mfma32(a[st], b[tn][st], acc[tn]);
-    }
-  }
-
-  // ---- epilogue (same as gemm_rows_kernel) ----------------------------------------------------------
-  gemm_rows_epilogue<TN>(D, sg, acc, n0, row0 + wave * 32, lr, lh);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// gemm_rows_sk_kernel: gemm_rows_cu_kernel with the PADDING of the last column block given back.
-// N = 450 is 4 x 96 + 66: the fifth column block of every row block multiplies 96 columns for 66 results, and since
-// every workgroup owns one tile the launch lasts as long as a full tile -- 6.3 % of the MFMA work is padding (DESIGN,
-// section "Next").  Here the fifth tile is CHEAP: two 32-column MFMA tiles + the last XC <= 2 columns as VALU dot
-// products on the A fragments the wave holds anyway (4 XC fused multiply-adds per 8-k group beside 8 MFMAs), and the time
-// its workgroup saves goes to the four others: it computes the LAST `don` K steps of each of their tiles first (a
-// 384 x 96 partial tile each, handed over through memory with a flag), then its own tile; the owners run `don` steps less
-// and add the partial in their epilogue -- which is ~0.75 of the kernel later, so nobody ever waits (the flag is there
-// for correctness).  A giver waits for nobody, every workgroup is resident (one round, one workgroup per CU): no cycle.
-// cu_tile is gemm_rows_cu_kernel's body over a K-step range [t_lo, t_hi) with the three endings.
-enum { SK_PLAIN = 0, SK_GIVE = 1, SK_TAKE = 2, SK_DYN = 3 };
+// cu_tile: ONE 384 x (32 TN + XC) tile on one 768-thread workgroup per CU, over the K steps [t_lo, t_hi) of k-source 0 and
+// (with_tail) the tail tiles behind them -- the body of gemm_rows_cu_kernel, gemm_rows_sk_kernel and gemm_rows_skc_kernel
+// (their own comments below).  The tile's pieces and why its K step is scheduled by hand: gemm_tile384.h.  The step here:
+// global loads run two K tiles ahead on a scalar base + constant per-lane offsets (no address arithmetic in the loop), all
+// LDS addresses are immediates.  TN = 4 (384 x 128): the B tile is 1024 staging slots for 768 threads -- every thread
+// carries two, the second one live for threads 0..255 and a clamped load + a store into the dummy strip for the others.
+// The endings (MODE): SK_WHOLE the whole tile, gemm_rows_epilogue with every term; the others the plain epilogue (alpha,
+// bias, row mask) inline, behind it SK_GIVE the partial tile handed over, SK_TAKE a partial tile added, SK_DYN either as a
+// value.  (gemm_rows_epilogue behind the stream-K modes costs them ~150 spilled VGPRs: the ending is a compile-time choice.)
+// DBG (SK_WHOLE only): per-wave stamps of the fast loop for tools/stamp_gemm.py.
+enum { SK_PLAIN = 0, SK_GIVE = 1, SK_TAKE = 2, SK_DYN = 3, SK_WHOLE = 4 };
 // What a tile of gemm_rows_skc_kernel adds to cu_tile's arguments (MODE == SK_DYN): the ending as a value, the number of
 // partial tiles a taker adds (those of the workgroups behind it: part / flag of the first, one slot further each), and the
 // kept rows of the tile's segment.
@@ -651,25 +340,19 @@ struct SkcTile {
   int seg, row0, live;
   const int* rows;
 };
-template <int TN, int XC, int MODE>
+template <int TN, int XC, int MODE, int DBG = 0>
 __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__ As, float* __restrict__ Bs, const int rb,
                                         const int n0, const int t_lo, const int t_hi, const bool with_tail,
                                         float* __restrict__ part, int* flag, const SkcTile dyn = SkcTile{}) {
+  using namespace tile384;
   constexpr bool IDX = MODE == SK_DYN;  // rows through the kept-row list
-  constexpr int BM = 384, BNS = 32 * TN + XC, BK = 32, NW = 12, NT = 768, LS = BK + 4, C4 = BK / 4;
-  constexpr int A_PER = BM * C4 / NT, B_PER = (BNS * C4 + NT - 1) / NT;
-  constexpr int A_BUF = BM * LS, B_BUF = BNS * LS;
+  constexpr int BNS = b_cols(TN, XC), B_PER = b_per(TN, XC), B_BUF = b_buf(TN, XC);
   constexpr int XCA = XC > 0 ? XC : 1;
-  static_assert(B_PER == 1 && 2 * B_BUF + (NT - BNS * C4) * 4 <= 2 * 96 * LS + 1024, "B tile: one slot per thread, inside the kernel's Bs");
+  static_assert(TN >= 2 && TN <= 4 && (MODE == SK_WHOLE || (B_PER == 1 && !DBG)) && (MODE != SK_WHOLE || XC == 0) &&
+                    2 * B_BUF + (B_PER * NT - BNS * C4) * 4 <= bs_floats(TN == 4 ? 4 : 3),
+                "B tile: inside the kernel's Bs; two slots per thread, stamps and the full epilogue for the whole tile only");
   const CarcaGemmDesc& D = args.d;
-  int s = 0;
-  if constexpr (IDX) {
-    s = dyn.seg;
-  } else {
-#pragma unroll
-    for (int i = 1; i < CARCA_MAX_SEGS; ++i)
-      if (i < D.nseg && rb >= args.rb_start[i]) s = i;
-  }
+  const int s = IDX ? dyn.seg : seg_of(D, args.rb_start, rb);
   const CarcaGemmSeg sg = D.seg[s];
   const int row0 = IDX ? dyn.row0 : (rb - args.rb_start[s]) * BM;
   const int nrows = IDX ? dyn.live : sg.rows;  // rows of the segment this kernel multiplies
@@ -679,8 +362,8 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
 
   // element offset of staging slot i's row inside k-source 0 / 1 (recomputed where the tail tiles need it: kept in registers
   // across the K loop -- sixteen VGPRs of 64-bit offsets -- they were what the 168-register kernel spilled)
-  auto a_off = [&](int i, bool src1) -> size_t {
-    const int slot = tid + i * NT, r = slot / C4;
+  auto a_off = [&](int i, bool src1, int th) -> size_t {  // (th: tid)
+    const int slot = th + i * NT, r = slot / C4;
     int gr = min(row0 + r, nrows - 1);
     if constexpr (IDX) gr = dyn.rows[gr];
     const int ub = gr / sg.T, ut = gr - ub * sg.T;
@@ -694,48 +377,47 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
 #pragma unroll
   for (int i = 0; i < A_PER; ++i) {
     const int slot = tid + i * NT, r = slot / C4, c4 = slot - r * C4;
-    a_byte[i] = (unsigned)((a_off(i, false) + c4 * 4) * sizeof(float));
+    a_byte[i] = (unsigned)((a_off(i, false, tid) + c4 * 4) * sizeof(float));
     a_lds[i] = r * LS + c4 * 4;
   }
-  const bool b_live = tid < BNS * C4;  // (threads past the B tile's slots load a clamped row and store into the dummy strip)
+  // the thread's B slot: slot tid of the tile's BNS x 8 (threads past them load a clamped row and store into the dummy strip)
+  const bool b_live = tid < BNS * C4;
   const int b_r = b_live ? tid / C4 : 0, b_c4 = tid % C4;
   const int b_gn = min(n0 + b_r, D.N - 1);
   const unsigned b_byte = (unsigned)(((size_t)b_gn * D.ldb0 + b_c4 * 4) * sizeof(float));
   const int b_at0 = b_live ? b_r * LS + b_c4 * 4 : 2 * B_BUF + (tid - BNS * C4) * 4;
   const int b_at1 = b_live ? B_BUF + b_r * LS + b_c4 * 4 : 2 * B_BUF + (tid - BNS * C4) * 4;
+  // TN = 4: 1024 slots for 768 threads -- a second one, tid + NT: live for threads 0..255 (same 16-byte group c4, 96 rows
+  // further), the others' own 16 bytes of the dummy strip
+  const bool b2_live = B_PER > 1 && tid + NT < BNS * C4;
+  const int b2_gn = min(n0 + (b2_live ? b_r + NT / C4 : 0), D.N - 1);
+  const unsigned b2_byte = (unsigned)(((size_t)b2_gn * D.ldb0 + b_c4 * 4) * sizeof(float));
+  const int b2_at = b2_live ? (b_r + NT / C4) * LS + b_c4 * 4 : 2 * B_BUF + (tid + NT - BNS * C4) * 4;  // (LDS buffer 1: + B_BUF where live)
 
-  f32x4 ra[A_PER], rbv;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  f32x4 ra[A_PER], rbv[B_PER];
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sg.a0, 0, -1, 0x00020000);
   const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)D.bt0, 0, -1, 0x00020000);
   int k_byte = t_lo * BK * (int)sizeof(float);  // scalar: byte offset of the NEXT tile to load inside a row
-  auto load_fast = [&](int i) {
-    const u32x4 v = i < A_PER ? __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_byte[i < A_PER ? i : 0], k_byte, 0)
-                              : __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_byte, k_byte, 0);
+  auto load_fast = [&](int i) {  // slot i of that tile (i >= A_PER: B slot i - A_PER)
+    const int ia = i < A_PER ? i : 0, ib = i < A_PER ? 0 : i - A_PER;
+    const u32x4 v = i < A_PER ? __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_byte[ia], k_byte, 0)
+                              : __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, ib ? b2_byte : b_byte, k_byte, 0);
     f32x4 f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(v[e]);
     if (i < A_PER)
-      ra[i < A_PER ? i : 0] = f;
+      ra[ia] = f;
     else
-      rbv = f;
+      rbv[ib] = f;
   };
   auto store_slot = [&](int i, int buf) {
+    const int ia = i < A_PER ? i : 0, ib = i < A_PER ? 0 : i - A_PER;
     if (i < A_PER)
-      *reinterpret_cast<f32x4*>(&As[buf * A_BUF + a_lds[i < A_PER ? i : 0]]) = ra[i < A_PER ? i : 0];
+      *reinterpret_cast<f32x4*>(&As[buf * A_BUF + a_lds[ia]]) = ra[ia];
     else
-      *reinterpret_cast<f32x4*>(&Bs[buf ? b_at1 : b_at0]) = rbv;
+      *reinterpret_cast<f32x4*>(&Bs[ib ? (b2_live ? buf * B_BUF + b2_at : b2_at) : (buf ? b_at1 : b_at0)]) = rbv[ib];
   };
-  auto load4 = [](const float* p, bool full, int kk, int klen) -> f32x4 {
-    if (full) return *reinterpret_cast<const f32x4_u*>(p);
-    f32x4 v;
-    v[0] = kk + 0 < klen ? p[0] : 0.f;
-    v[1] = kk + 1 < klen ? p[1] : 0.f;
-    v[2] = kk + 2 < klen ? p[2] : 0.f;
-    v[3] = kk + 3 < klen ? p[3] : 0.f;
-    return v;
-  };
-  auto load_tail = [&](int t) {
+  auto load_tail = [&](int t) {  // any tile, either k-source, ragged K (the few tiles behind the fast loop)
     const bool src1 = t >= nt0;
     const int k0 = (src1 ? t - nt0 : t) * BK;
     const int klen = src1 ? D.K1 : D.K0;
@@ -743,12 +425,16 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
     const float* bbase = src1 ? D.bt1 : D.bt0;
     const int ldb = src1 ? D.ldb1 : D.ldb0;
     const bool full = k0 + BK <= klen;
+    // (TN = 4: moved out of the tail loop, the row offsets inside both k-sources cost 47 spilled VGPRs; this keeps them in)
+    int th = tid;
+    if constexpr (B_PER > 1) asm volatile("" : "+v"(th));
 #pragma unroll
     for (int i = 0; i < A_PER; ++i) {
       const int c4 = (tid + i * NT) % C4;
-      ra[i] = load4(abase + a_off(i, src1) + k0 + c4 * 4, full, k0 + c4 * 4, klen);
+      ra[i] = load4(abase + a_off(i, src1, th) + k0 + c4 * 4, full, k0 + c4 * 4, klen);
     }
-    rbv = load4(bbase + (size_t)b_gn * ldb + k0 + b_c4 * 4, full, k0 + b_c4 * 4, klen);
+    rbv[0] = load4(bbase + (size_t)b_gn * ldb + k0 + b_c4 * 4, full, k0 + b_c4 * 4, klen);
+    if constexpr (B_PER > 1) rbv[1] = load4(bbase + (size_t)b2_gn * ldb + k0 + b_c4 * 4, full, k0 + b_c4 * 4, klen);
   };
 
   f32x16 acc[TN];
@@ -761,70 +447,55 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
   for (int c = 0; c < XCA; ++c) xacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int lr = lane & 31, lh = lane >> 5;
-  const float* a_frag = &As[(wave * 32 + lr) * LS + 4 * lh];
+  const float* a_frag = &As[(wave * 32 + lr) * LS + 4 * lh];  // (fragment addresses: gemm_tile384.h)
   const float* b_frag = &Bs[lr * LS + 4 * lh];
-  const float* x_frag = &Bs[(32 * TN) * LS + 4 * lh];  // the XC extra rows of the B tile: one k quad per half wave
-  f32x4 fa0, fa1, fb0[TN], fb1[TN], fx0[XCA], fx1[XCA];
+  const float* x_frag = &Bs[(32 * TN) * LS + 4 * lh];
+  f32x4 fa0, fa1, fb0[TN], fb1[TN], fx0[XCA], fx1[XCA];  // fragment sets of two consecutive 8-k groups
 
-#define CARCA_PIN() __builtin_amdgcn_sched_barrier(0)
-  constexpr int NR = TN + 1, NRX = NR + XC;
-  auto read_frag = [&](int j, int buf, int kg, f32x4& fa, f32x4(&fb)[TN], f32x4(&fx)[XCA]) {
-    if (j == 0)
-      fa = *reinterpret_cast<const f32x4*>(a_frag + buf * A_BUF + kg * 8);
-    else if (j < NR)
-      fb[j - 1] = *reinterpret_cast<const f32x4*>(b_frag + buf * B_BUF + (j - 1) * 32 * LS + kg * 8);
-    else
-      fx[j - NR] = *reinterpret_cast<const f32x4*>(x_frag + buf * B_BUF + (j - NR) * LS + kg * 8);
-  };
-  auto mfma_group = [&](const f32x4& fa, const f32x4(&fb)[TN], const f32x4(&fx)[XCA], auto&& aux) {
-#pragma unroll
-    for (int i = 0; i < 4 * TN; ++i) {
-      acc[i % TN] = mfma32(fa[i / TN], fb[i % TN][i / TN], acc[i % TN]);
-      CARCA_PIN();
-      if constexpr (XC > 0) {
-        if (i < XC) {
-          // two v_pk_fma_f32, written out: left to the compiler the same four FMAs cost 70 spilled VGPRs (it re-plans the
-          // fragment registers of the whole pinned step around them)
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          const int c = i < XC ? i : 0;
-          f32x2 a0 = {fa[0], fa[1]}, a1 = {fa[2], fa[3]};
-          f32x2 w0 = {fx[c][0], fx[c][1]}, w1 = {fx[c][2], fx[c][3]};
-          f32x2 x0 = {xacc[c][0], xacc[c][1]}, x1 = {xacc[c][2], xacc[c][3]};
-          asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(x0) : "v"(a0), "v"(w0));
-          asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(x1) : "v"(a1), "v"(w1));
-          xacc[c] = f32x4{x0[0], x0[1], x1[0], x1[1]};
-        }
-      }
-      aux(i);
-      CARCA_PIN();
-    }
-  };
+  constexpr int NR = TN + 1, NRX = NR + XC;  // fragment reads per group: A, the TN B tiles, the XC columns
   static_assert(NRX <= 4 * TN && NR + A_PER + B_PER <= 4 * TN, "a group's gaps hold its reads and the tile's staging slots");
+  unsigned long long w_vm = 0, w_bar = 0, t_begin = 0;  // (DBG: cycles in the wait for tile t+2's loads / in the barrier)
+  // one K step on tile t (LDS buffer CUR); tile t+1 is in registers, tile t+2 gets loaded.  Gaps 0..NRX-1 of every group
+  // carry the fragment reads of the next group; the gaps from NR on of group 1 the LDS writes of tile t+1 and those of
+  // group 2 the loads of tile t+2 (behind the writes: the staging registers are reused).
   auto step = [&](auto cur_tag, int t) {
     constexpr int CUR = decltype(cur_tag)::value, NXT = CUR ^ 1;
     const bool has1 = t + 1 < t_hi, has2 = t + 2 < t_hi;
-    mfma_group(fa0, fb0, fx0, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 1, fa1, fb1, fx1);
+    mfma_group<TN, XC>(acc, xacc, fa0, fb0, fx0, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 1, fa1, fb1, fx1);
     });
-    mfma_group(fa1, fb1, fx1, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 2, fa0, fb0, fx0);
+    if constexpr (DBG) {
+      const unsigned long long ta = __builtin_amdgcn_s_memtime();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      w_vm += __builtin_amdgcn_s_memtime() - ta;
+      CARCA_PIN();
+    }
+    mfma_group<TN, XC>(acc, xacc, fa1, fb1, fx1, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 2, fa0, fb0, fx0);
       if (i >= NR && i < NR + A_PER + B_PER && has1) store_slot(i - NR, NXT);
     });
-    mfma_group(fa0, fb0, fx0, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 3, fa1, fb1, fx1);
+    mfma_group<TN, XC>(acc, xacc, fa0, fb0, fx0, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 3, fa1, fb1, fx1);
       if (i >= NR && i < NR + A_PER + B_PER && has2) load_fast(i - NR);
     });
     if (has2) k_byte += BK * sizeof(float);
     CARCA_PIN();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // raw: the loads of tile t+2 stay in flight across it
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own LDS writes of tile t+1 and reads of tile t retired
+    if constexpr (DBG) {
+      const unsigned long long tb = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_s_barrier();
+      w_bar += __builtin_amdgcn_s_memtime() - tb;
+    } else {
+      __builtin_amdgcn_s_barrier();  // raw: the loads of tile t+2 stay in flight across it
+    }
     CARCA_PIN();
-    mfma_group(fa1, fb1, fx1, [&](int i) {
-      if (i < NRX && has1) read_frag(i, NXT, 0, fa0, fb0, fx0);
+    mfma_group<TN, XC>(acc, xacc, fa1, fb1, fx1, [&](int i) {
+      if (i < NRX && has1) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, NXT, 0, fa0, fb0, fx0);
     });
   };
 
-  __syncthreads();  // (a workgroup that runs several tiles: the previous one is done with both LDS buffers)
+  // (a workgroup that runs several tiles: the previous one is done with both LDS buffers)
+  if constexpr (MODE != SK_WHOLE) __syncthreads();
   if (t_hi > t_lo) {
 #pragma unroll
     for (int i = 0; i < A_PER + B_PER; ++i) load_fast(i);
@@ -838,19 +509,44 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < NRX; ++j) read_frag(j, 0, 0, fa0, fb0, fx0);
+    for (int j = 0; j < NRX; ++j) read_frag<TN, XC>(a_frag, b_frag, x_frag, j, 0, 0, fa0, fb0, fx0);
+    if constexpr (DBG) t_begin = __builtin_amdgcn_s_memtime();
     int t = t_lo;
     for (; t + 1 < t_hi; t += 2) {
       step(std::integral_constant<int, 0>{}, t);
       step(std::integral_constant<int, 1>{}, t + 1);
     }
     if (t < t_hi) step(std::integral_constant<int, 0>{}, t);
+    if constexpr (DBG) {
+      if (args.dbg && lane == 0) {
+        unsigned long long* o = args.dbg + ((size_t)blockIdx.x * NW + wave) * 4;
+        o[0] = __builtin_amdgcn_s_memtime() - t_begin;
+        o[1] = w_vm;
+        o[2] = w_bar;
+        o[3] = 0;
+      }
+    }
   }
-#undef CARCA_PIN
+  // one 8-k group of a tail tile in LDS buffer 0, as the compiler schedules it
+  auto tail_group = [&](int kg) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(a_frag + kg * 8);
+    f32x4 b[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) b[tn] = *reinterpret_cast<const f32x4*>(b_frag + tn * 32 * LS + kg * 8);
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) acc[tn] = mfma32(a[st], b[tn][st], acc[tn]);
+    if constexpr (XC > 0) {
+#pragma unroll
+      for (int c = 0; c < XC; ++c) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(x_frag + c * LS + kg * 8);
+        xacc[c] = __builtin_elementwise_fma(a, w, xacc[c]);
+      }
+    }
+  };
   // The context columns (k-source 1 with 4 <= K1 <= 8 behind a K0 of whole 32-steps: AllEmbedding's six) as ONE 8-k group
-  // (round 5; the scheme of gemm_rows_cus_kernel's context item, gemm_stream.hip): every thread requests one 16-byte group
-  // of its row -- thread = (row tid >> 1, half tid & 1), the second half clamped to END at K1 and shifted / zeroed when
-  // stored --, two barriers, 4 TN MFMAs.  The general tail below stages a whole 32-wide tile through element-wise
+  // (ctx_fix, gemm_tile384.h): every thread requests one 16-byte group of its row, two barriers, 4 TN MFMAs.  The general tail below stages a whole 32-wide tile through element-wise
   // conditional loads (twenty dword loads per thread) and multiplies four 8-k groups, three of them zeros: ~7 us per
   // owned tile against ~3.  Same products in the same order (the other groups added zeros): bit-identical results.
   const bool ctx8 = with_tail && D.K1 >= 4 && D.K1 <= 8 && D.K0 % BK == 0 && !(args.diag & 64);
@@ -864,34 +560,11 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
     const bool bx_live = tid < 2 * BNS;
     const f32x4 av = *reinterpret_cast<const f32x4_u*>(sg.a1 + ao + cs);
     const f32x4 bv = *reinterpret_cast<const f32x4_u*>(D.bt1 + (size_t)min(n0 + (bx_live ? xr : 0), D.N - 1) * D.ldb1 + cs);
-    auto fix = [&](const f32x4 v) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x = sh == 0 ? v[e] : (sh == 1 ? v[(e + 1) & 3] : (sh == 2 ? v[(e + 2) & 3] : v[(e + 3) & 3]));
-        o[e] = (4 * xh + e < D.K1) ? x : 0.f;
-      }
-      return o;
-    };
     __syncthreads();  // every wave is done with both LDS buffers
-    *reinterpret_cast<f32x4*>(&As[xr * LS + xh * 4]) = fix(av);
-    *reinterpret_cast<f32x4*>(&Bs[bx_live ? xr * LS + xh * 4 : 2 * B_BUF + ((tid - 2 * BNS) & 255) * 4]) = fix(bv);
+    *reinterpret_cast<f32x4*>(&As[xr * LS + xh * 4]) = ctx_fix(av, sh, xh, D.K1);
+    *reinterpret_cast<f32x4*>(&Bs[bx_live ? xr * LS + xh * 4 : 2 * B_BUF + ((tid - 2 * BNS) & 255) * 4]) = ctx_fix(bv, sh, xh, D.K1);
     __syncthreads();
-    const f32x4 a = *reinterpret_cast<const f32x4*>(a_frag);
-    f32x4 b[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) b[tn] = *reinterpret_cast<const f32x4*>(b_frag + tn * 32 * LS);
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) acc[tn] = mfma32(a[st], b[tn][st], acc[tn]);
-    if constexpr (XC > 0) {
-#pragma unroll
-      for (int c = 0; c < XC; ++c) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(x_frag + c * LS);
-        xacc[c] = __builtin_elementwise_fma(a, w, xacc[c]);
-      }
-    }
+    tail_group(0);
   } else if (with_tail) {
     for (int t = D.K0 / BK; t < ntiles; ++t) {
       load_tail(t);
@@ -900,24 +573,12 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
       for (int i = 0; i < A_PER + B_PER; ++i) store_slot(i, 0);
       __syncthreads();
 #pragma unroll
-      for (int kg = 0; kg < BK / 8; ++kg) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(a_frag + kg * 8);
-        f32x4 b[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) b[tn] = *reinterpret_cast<const f32x4*>(b_frag + tn * 32 * LS + kg * 8);
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-#pragma unroll
-          for (int tn = 0; tn < TN; ++tn) acc[tn] = mfma32(a[st], b[tn][st], acc[tn]);
-        if constexpr (XC > 0) {
-#pragma unroll
-          for (int c = 0; c < XC; ++c) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(x_frag + c * LS + kg * 8);
-            xacc[c] = __builtin_elementwise_fma(a, w, xacc[c]);
-          }
-        }
-      }
+      for (int kg = 0; kg < BK / 8; ++kg) tail_group(kg);
     }
+  }
+  if constexpr (MODE == SK_WHOLE) {
+    gemm_rows_epilogue<TN>(D, sg, acc, n0, row0 + wave * 32, lr, lh);
+    return;
   }
 
   const int mode = MODE == SK_DYN ? dyn.mode : MODE;
@@ -981,7 +642,7 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
     }
   }
 
-  // ---- epilogue (as gemm_rows_cu_kernel) ------------------------------------------------------------
+  // ---- the plain epilogue (the launchers admit no other term behind these endings) ---------------------------------
   int erow[16];  // the output row of accumulator register r (-1: past the segment's rows)
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -1018,16 +679,12 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
     }
   }
   if constexpr (XC > 0) {
-    // the VALU columns: lane (lr, lh) holds row wave * 32 + lr's sum over the k quads of its half; the launcher admits
-    // this kernel only for the plain epilogue (alpha, bias, row mask)
     int row = row0 + wave * 32 + lr;
     const bool row_ok = row < nrows;
     if constexpr (IDX) row = dyn.rows[min(row, nrows - 1)];
 #pragma unroll
     for (int c = 0; c < XC; ++c) {
-      const float mine = (xacc[c][0] + xacc[c][1]) + (xacc[c][2] + xacc[c][3]);
-      auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine), __float_as_uint(mine), false, false);
-      const float tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+      const float tot = xcol_total(xacc[c]);
       const int n = n0 + 32 * TN + c;
       if (lh == 0 && row_ok && n < D.N) {
         float v = (D.alpha != 0.f ? D.alpha * tot : tot) + (D.bias ? D.bias[n] : 0.f);
@@ -1038,14 +695,46 @@ __device__ __forceinline__ void cu_tile(const GemmDev& args, float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// gemm_rows_cu_kernel: the row product for the ONE launch that carries 97 % of the model's flops (feats_embed at
+// n_attrs = 4096: ~19k rows x 4102 x 450).  One 768-thread block per CU computes one whole tile (cu_tile, SK_WHOLE):
+// 36 of the 9060 32x32 output tiles per CU (255 blocks on 256 CUs, one round) like the 128 x 96 kernel's three
+// co-resident blocks, but the B tile is staged once instead of three times (107 instead of 149 bytes through L1 per MFMA).
+// TN = 3: tile 384 x 96 (the C2 feature GEMM: 5 column blocks of N = 450).  TN = 4: tile 384 x 128 for N that 128-wide
+// blocks cover in one round where 96-wide ones need two (g = 640: 5 x 51 = 255 blocks instead of 7 x 51 = 357).
+// Workgroup nrb * ncb (one past the tiles), where the launcher adds it, is the passenger: it only copies item rows.
+template <int DBG, int TN = 3>
+__global__ __launch_bounds__(768) void gemm_rows_cu_kernel(const GemmDev args) {
+  __shared__ __attribute__((aligned(16))) float As[tile384::AS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Bs[tile384::bs_floats(TN)];
+  const int id = blockIdx.x, total = args.nrb * args.ncb;
+  if (args.has_pas && id == total) {  // (an otherwise idle CU)
+    carca_gather_rows<16>(args.pas, (int)threadIdx.x >> 6, tile384::NW, (int)threadIdx.x & 63);
+    return;
+  }
+  const int wg = tile384::xcd_swizzle(id, total);
+  const int rb = wg / args.ncb, cb = wg - rb * args.ncb;
+  cu_tile<TN, 0, SK_WHOLE, DBG>(args, As, Bs, rb, cb * (32 * TN), 0, args.d.K0 / tile384::BK, true, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// gemm_rows_sk_kernel: gemm_rows_cu_kernel with the PADDING of the last column block given back.
+// N = 450 is 4 x 96 + 66: the fifth column block of every row block multiplies 96 columns for 66 results, and since
+// every workgroup owns one tile the launch lasts as long as a full tile -- 6.3 % of the MFMA work is padding (DESIGN,
+// section "Next").  Here the fifth tile is CHEAP: two 32-column MFMA tiles + the last XC <= 2 columns as VALU dot
+// products on the A fragments the wave holds anyway (4 XC fused multiply-adds per 8-k group beside 8 MFMAs), and the time
+// its workgroup saves goes to the four others: it computes the LAST `don` K steps of each of their tiles first (a
+// 384 x 96 partial tile each, handed over through memory with a flag), then its own tile; the owners run `don` steps less
+// and add the partial in their epilogue -- which is ~0.75 of the kernel later, so nobody ever waits (the flag is there
+// for correctness).  A giver waits for nobody, every workgroup is resident (one round, one workgroup per CU): no cycle.
 template <int XC>
 __global__ __launch_bounds__(768) void gemm_rows_sk_kernel(const GemmDev args) {
-  __shared__ __attribute__((aligned(16))) float As[2 * 384 * 36];
-  __shared__ __attribute__((aligned(16))) float Bs[2 * 96 * 36 + 1024];
+  __shared__ __attribute__((aligned(16))) float As[tile384::AS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Bs[tile384::BS_FLOATS];
   const CarcaGemmDesc& D = args.d;
   const int id = blockIdx.x, total = args.nrb * args.ncb;
   if (args.has_pas && id == total) {
-    static_assert(12 * 24 * 96 <= 2 * 384 * 36 && 12 * 18 * 128 <= 2 * 384 * 36, "the passenger's rows fit the A buffers");
+    static_assert(12 * 24 * 96 <= tile384::AS_FLOATS && 12 * 18 * 128 <= tile384::AS_FLOATS, "the passenger's rows fit the A buffers");
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if (args.pas.d <= 96)
       gather_rows_dma<24, 96>(args.pas, As, wave, 12, (int)threadIdx.x & 63);
@@ -1053,8 +742,7 @@ __global__ __launch_bounds__(768) void gemm_rows_sk_kernel(const GemmDev args) {
       gather_rows_dma<18, 128>(args.pas, As, wave, 12, (int)threadIdx.x & 63);
     return;
   }
-  const int xcd = id & 7, q8 = total >> 3, r8 = total & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+  const int wg = tile384::xcd_swizzle(id, total);
   const int rb = wg / args.ncb, j = wg - rb * args.ncb;
   const int nfast = D.K0 / 32, nfull = args.ncb - 1;
   if (j == 0) {  // the row block's cheap workgroup (first of the block's five to be dispatched)
@@ -1094,7 +782,7 @@ __global__ __launch_bounds__(768) void gemm_rows_sk_kernel(const GemmDev args) {
 // another grouping of the K range (1e-7 relative), the same bits from run to run.
 constexpr int SKC_RB = 8;       // row blocks one workgroup's stretch may touch (the launcher checks rows against it)
 constexpr int SKC_CH = 1536;    // 64-row chunks of all segments (+ one entry per segment)
-constexpr int SKC_LDS_IDS = 2 * 384 * 36;  // ids the prologue keeps in LDS (the A buffers' space: 27,648)
+constexpr int SKC_LDS_IDS = tile384::AS_FLOATS;  // ids the prologue keeps in LDS (the A buffers' space: 27,648)
 constexpr int SKC_MIN_STEPS = 64;  // K steps of k-source 0 below which the product stays on the one-tile-per-workgroup kernels
 constexpr int SKC_OV_MAX = 12;  // bound on the row-block ownership cost in K steps (a stretch holds at least 16 steps)
 // defaults (tuning keys 17 / 18 = value + 1).  MEASURED, round 5, interleaved A/B at C2 (tools/ab_eval.py): ownership cost 0 / 4
@@ -1106,8 +794,8 @@ constexpr int SKC_OV_TEAM = 0, SKC_OV_LONE = 0;
 
 template <int XC>
 __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) {
-  __shared__ __attribute__((aligned(16))) float As[2 * 384 * 36];
-  __shared__ __attribute__((aligned(16))) float Bs[2 * 96 * 36 + 1024];
+  __shared__ __attribute__((aligned(16))) float As[tile384::AS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Bs[tile384::BS_FLOATS];
   __shared__ int Rl[SKC_RB * 384];  // kept rows of this workgroup's row blocks
   __shared__ int Cp[SKC_CH];        // kept rows before each 64-row chunk of its segment (+ the segment's total)
   __shared__ int Pc[8 * SKC_RB + 4];  // this workgroup's pieces (step 5)
@@ -1351,6 +1039,9 @@ __global__ __launch_bounds__(768) void gemm_rows_skc_kernel(const GemmDev args) 
     if ((x + 1) * nfull < nblk && x + 1 <= cap && span(x + 1) < span(x)) ++x;
   }
   const int y = (int)max(1l, min(cap, (long)nblk - (long)x * nfull));
+  // (tile384::xcd_swizzle over the x nfull + y workgroup numbers, written out: the grid is one workgroup per CU, and the ids
+  // past their XCD's share `cnt` of the numbers have no stretch -- with the helper and the share beside it, this kernel's
+  // code comes out different)
   const int xcd = id & 7, nw = x * nfull + y, q8 = nw >> 3, r8 = nw & 7;
   const int cnt = xcd < r8 ? q8 + 1 : q8;
   if (nrb == 0 || (id >> 3) >= cnt) {

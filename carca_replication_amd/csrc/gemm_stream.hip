@@ -12,9 +12,9 @@
 //     MFMAs (12 instead of 48) and no barrier of its own;
 //   * the epilogue is stores only (buffer stores: one lane-offset register, the row in the scalar offset; the pad mask of
 //     a wave's 32 rows is ONE id per lane and a ballot), issued while the next tile's loads fly.
-// Tiles and the K step itself are gemm_rows_cu_kernel's (384 x 96, twelve waves, wave w owns rows 32 w .. + 31 x 96
-// columns, hand-scheduled step with LDS double buffer and one barrier); the narrow last column block (N = 450 = 4 x 96 +
-// 66) is two MFMA column tiles + up to two VALU columns as in gemm_rows_sk_kernel; its (cheaper) tiles are dealt BEHIND the
+// The tile and the pieces of its K step are gemm_tile384.h's (384 x 96, twelve waves, wave w owns rows 32 w .. + 31 x 96
+// columns, pinned MFMA groups, LDS double buffer and one barrier; the step's schedule over items is this file's); the narrow
+// last column block (N = 450 = 4 x 96 + 66) is two MFMA column tiles + up to two VALU columns; its (cheaper) tiles are dealt BEHIND the
 // full ones -- fewer to the workgroups that hold one full tile more -- so that all workgroups end together.  Same products in the same order as gemm_rows_cu_kernel per output
 // element (K steps in order, the context group last): results agree to the last bit where that kernel's tail tile adds its
 // 32-wide step in the same grouping, and to round-off otherwise (tests/test_hip_gemm_stream.py: float64 products).
@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "gemm_host.h"
 #include "../../include/carca_hip.h"
+#include "gemm_tile384.h"
 
 namespace {
 
@@ -42,25 +43,15 @@ enum { IT_FAST = 1, IT_CTX = 2 };
 template <int TN, int XC>
 __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __restrict__ As, float* __restrict__ Bs,
                                              const int n0, const int rbA, const int rbB) {
-  constexpr int BM = 384, BNS = 32 * TN + XC, BK = 32, NT = 768, LS = BK + 4, C4 = BK / 4;
-  constexpr int A_PER = BM * C4 / NT;  // 4
-  constexpr int A_BUF = BM * LS, B_BUF = BNS * LS;
+  using namespace tile384;
+  constexpr int BNS = b_cols(TN, XC), B_BUF = b_buf(TN, XC);
   constexpr int XCA = XC > 0 ? XC : 1;
-  static_assert(A_PER == 4 && BNS * C4 <= NT && 2 * B_BUF + 1024 <= 2 * 96 * LS + 1024, "one B slot per thread, inside the kernel's Bs");
+  static_assert(A_PER == 4 && b_per(TN, XC) == 1 && 2 * B_BUF + 1024 <= BS_FLOATS, "one B slot per thread, inside the kernel's Bs");
   const CarcaGemmDesc& D = args.d;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nfast = D.K0 / BK;
   const int K1 = D.K1;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-  auto seg_of = [&](int rb) {
-    int s = 0;
-#pragma unroll
-    for (int i = 1; i < CARCA_MAX_SEGS; ++i)
-      if (i < D.nseg && rb >= args.rb_start[i]) s = i;
-    return s;
-  };
 
   // ---- per-thread invariants --------------------------------------------------------------------------------------
   const int r0 = tid >> 3, c4 = tid & 7;            // fast items: slot i is row r0 + 96 i, 16-byte group c4
@@ -85,7 +76,7 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
   const float* l_a1 = D.seg[0].a1;
   unsigned a_v[A_PER], a1_v = 0;
   auto retarget = [&](int rb) {  // the cursor's tile: operand bases and this thread's row offsets (clamped into the segment)
-    const int s = seg_of(rb);
+    const int s = seg_of(D, args.rb_start, rb);
     const CarcaGemmSeg sg = D.seg[s];
     const int row0 = (rb - args.rb_start[s]) * BM, last = sg.rows - 1;
     l_a0 = sg.a0;
@@ -112,7 +103,8 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
       if (i == A_PER) rbv = to_f(__builtin_amdgcn_raw_buffer_load_b128(carca_rsrc(D.bt1), b1_v(), 0, 0));
     }
   };
-  auto ctx_fix = [&](const f32x4 v) {  // the clamped group moved to its columns; columns at or past K1 are zeros
+  // (tile384::ctx_fix, written out: called from here, the function costs this kernel ~960 instructions more per instance)
+  auto ctx_store = [&](const f32x4 v) {  // the clamped group moved to its columns; columns at or past K1 are zeros
     const int sh = 4 * xh - cs_of();
     f32x4 o;
 #pragma unroll
@@ -130,8 +122,8 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
       else
         *reinterpret_cast<f32x4*>(&Bs[buf ? b_at1 : b_at0]) = rbv;
     } else {
-      if (i == 0) *reinterpret_cast<f32x4*>(&As[buf * A_BUF + xr * LS + xh * 4]) = ctx_fix(ra[0]);
-      if (i == A_PER) *reinterpret_cast<f32x4*>(&Bs[bx_at(buf)]) = ctx_fix(rbv);
+      if (i == 0) *reinterpret_cast<f32x4*>(&As[buf * A_BUF + xr * LS + xh * 4]) = ctx_store(ra[0]);
+      if (i == A_PER) *reinterpret_cast<f32x4*>(&Bs[bx_at(buf)]) = ctx_store(rbv);
     }
   };
 
@@ -147,64 +139,34 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
     for (int c = 0; c < XCA; ++c) xacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
   const int lr = lane & 31, lh = lane >> 5;
-  const float* a_frag = &As[(wave * 32 + lr) * LS + 4 * lh];
+  const float* a_frag = &As[(wave * 32 + lr) * LS + 4 * lh];  // (fragment addresses: gemm_tile384.h)
   const float* b_frag = &Bs[lr * LS + 4 * lh];
   const float* x_frag = &Bs[(32 * TN) * LS + 4 * lh];
   f32x4 fa0, fa1, fb0[TN], fb1[TN], fx0[XCA], fx1[XCA];
-#define CARCA_PIN() __builtin_amdgcn_sched_barrier(0)
   constexpr int NR = TN + 1, NRX = NR + XC, NSL = A_PER + 1;
   static_assert(NRX <= 4 * TN && NR + NSL <= 4 * TN, "a group's gaps hold its reads and the item's staging slots");
-  auto read_frag = [&](int j, int buf, int kg, f32x4& fa, f32x4(&fb)[TN], f32x4(&fx)[XCA]) {
-    if (j == 0)
-      fa = *reinterpret_cast<const f32x4*>(a_frag + buf * A_BUF + kg * 8);
-    else if (j < NR)
-      fb[j - 1] = *reinterpret_cast<const f32x4*>(b_frag + buf * B_BUF + (j - 1) * 32 * LS + kg * 8);
-    else
-      fx[j - NR] = *reinterpret_cast<const f32x4*>(x_frag + buf * B_BUF + (j - NR) * LS + kg * 8);
-  };
-  auto mfma_group = [&](const f32x4& fa, const f32x4(&fb)[TN], const f32x4(&fx)[XCA], auto&& aux) {
-#pragma unroll
-    for (int i = 0; i < 4 * TN; ++i) {
-      acc[i % TN] = mfma32(fa[i / TN], fb[i % TN][i / TN], acc[i % TN]);
-      CARCA_PIN();
-      if constexpr (XC > 0) {
-        if (i < XC) {  // (two v_pk_fma_f32, written out: gemm.hip, cu_tile)
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          const int c = i < XC ? i : 0;
-          f32x2 a0 = {fa[0], fa[1]}, a1 = {fa[2], fa[3]};
-          f32x2 w0 = {fx[c][0], fx[c][1]}, w1 = {fx[c][2], fx[c][3]};
-          f32x2 x0 = {xacc[c][0], xacc[c][1]}, x1 = {xacc[c][2], xacc[c][3]};
-          asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(x0) : "v"(a0), "v"(w0));
-          asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(x1) : "v"(a1), "v"(w1));
-          xacc[c] = f32x4{x0[0], x0[1], x1[0], x1[1]};
-        }
-      }
-      aux(i);
-      CARCA_PIN();
-    }
-  };
   // one fast item in LDS buffer CUR: four 8-k groups; the item in registers (kind RK) goes to buffer NXT, the cursor's item
   // (kind LK) is requested, the next item's first fragments are read behind the barrier.  The kinds are COMPILE-TIME (a
   // branch per staging slot between the pinned MFMAs cut the groups into pieces and cost ~200 spilled registers).
   auto fast_step = [&](auto cur_tag, auto rk_tag, auto lk_tag, const int so) {
     constexpr int CUR = decltype(cur_tag)::value, NXT = CUR ^ 1;
-    mfma_group(fa0, fb0, fx0, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 1, fa1, fb1, fx1);
+    mfma_group<TN, XC>(acc, xacc, fa0, fb0, fx0, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 1, fa1, fb1, fx1);
     });
-    mfma_group(fa1, fb1, fx1, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 2, fa0, fb0, fx0);
+    mfma_group<TN, XC>(acc, xacc, fa1, fb1, fx1, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 2, fa0, fb0, fx0);
       if (i >= NR && i < NR + NSL) store_slot(rk_tag, i - NR, NXT);
     });
-    mfma_group(fa0, fb0, fx0, [&](int i) {
-      if (i < NRX) read_frag(i, CUR, 3, fa1, fb1, fx1);
+    mfma_group<TN, XC>(acc, xacc, fa0, fb0, fx0, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, CUR, 3, fa1, fb1, fx1);
       if (i >= NR && i < NR + NSL) request_slot(lk_tag, i - NR, so);
     });
     CARCA_PIN();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // raw: the requested item stays in flight across it
     CARCA_PIN();
-    mfma_group(fa1, fb1, fx1, [&](int i) {
-      if (i < NRX) read_frag(i, NXT, 0, fa0, fb0, fx0);
+    mfma_group<TN, XC>(acc, xacc, fa1, fb1, fx1, [&](int i) {
+      if (i < NRX) read_frag<TN, XC>(a_frag, b_frag, x_frag, i, NXT, 0, fa0, fb0, fx0);
     });
   };
   // the context item in LDS buffer CUR, a tile's last: one 8-k group (its fragments were read behind the previous barrier);
@@ -213,7 +175,7 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
     constexpr int CUR = decltype(cur_tag)::value, NXT = CUR ^ 1;
     (void)CUR;
     constexpr std::integral_constant<int, IT_FAST> kf{};
-    mfma_group(fa0, fb0, fx0, [&](int i) {
+    mfma_group<TN, XC>(acc, xacc, fa0, fb0, fx0, [&](int i) {
       if (i < NSL) store_slot(kf, i, NXT);
       if (i >= NSL && i < 2 * NSL) request_slot(kf, i - NSL, BK * 4);
     });
@@ -224,12 +186,11 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
     __builtin_amdgcn_s_barrier();
     CARCA_PIN();
   };
-#undef CARCA_PIN
 
   // ---- the epilogue of row block rb (the plain one: alpha, bias, rows with id 0 as zeros) -----------------------------
   auto epilogue = [&](int rb) {
     const unsigned c_v = (unsigned)((((size_t)wave * 32 + 4 * lh) * D.ldc + n0 + lr) * sizeof(float));
-    const int s = seg_of(rb);
+    const int s = seg_of(D, args.rb_start, rb);
     const CarcaGemmSeg sg = D.seg[s];
     const int row0 = (rb - args.rb_start[s]) * BM, nrows = sg.rows;
     unsigned keep = 0xffffffffu;  // bit j: row row0 + 32 wave + j is kept
@@ -260,9 +221,7 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
       const int row = row0 + wave * 32 + lr;
 #pragma unroll
       for (int c = 0; c < XC; ++c) {
-        const float mine = (xacc[c][0] + xacc[c][1]) + (xacc[c][2] + xacc[c][3]);
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine), __float_as_uint(mine), false, false);
-        const float tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+        const float tot = xcol_total(xacc[c]);
         const int n = n0 + 32 * TN + c;
         if (lh == 0 && row < nrows && n < D.N) {
           float v = alpha * tot + (D.bias ? D.bias[n] : 0.f);
@@ -290,7 +249,7 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
   for (int i = 0; i < NSL; ++i) request_slot(kF, i, BK * 4);
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < NRX; ++j) read_frag(j, 0, 0, fa0, fb0, fx0);
+  for (int j = 0; j < NRX; ++j) read_frag<TN, XC>(a_frag, b_frag, x_frag, j, 0, 0, fa0, fb0, fx0);
   // tile rb: its item 0 in LDS buffer P (first fragments read), item 1 in registers
   auto tile_body = [&](auto p_tag, const int rb) {
     constexpr int P = decltype(p_tag)::value;
@@ -311,7 +270,7 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
     epilogue(rb);
     if (rb + 1 < rbB) {  // the next tile starts in buffer P ^ 1
 #pragma unroll
-      for (int j = 0; j < NRX; ++j) read_frag(j, P ^ 1, 0, fa0, fb0, fx0);
+      for (int j = 0; j < NRX; ++j) read_frag<TN, XC>(a_frag, b_frag, x_frag, j, P ^ 1, 0, fa0, fb0, fx0);
     }
   };
   for (int rb = rbA; rb < rbB; rb += 2) {
@@ -323,13 +282,11 @@ __device__ __forceinline__ void stream_tiles(const StreamDev& args, float* __res
 
 template <int XC>
 __global__ __launch_bounds__(768) void gemm_rows_cus_kernel(const StreamDev args) {
-  __shared__ __attribute__((aligned(16))) float As[2 * 384 * 36];
-  __shared__ __attribute__((aligned(16))) float Bs[2 * 96 * 36 + 1024];
+  __shared__ __attribute__((aligned(16))) float As[tile384::AS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Bs[tile384::BS_FLOATS];
   carca_warm_kernargs<sizeof(StreamDev)>();
   // consecutive workgroup numbers w on ONE XCD: the nfull workgroups of a team stream the same A rows through one L2
-  const int id = blockIdx.x, nw = gridDim.x;
-  const int xcd = id & 7, q8 = nw >> 3, r8 = nw & 7;
-  const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+  const int w = tile384::xcd_swizzle(blockIdx.x, gridDim.x);
   const int nfull = args.nfull, x = args.x, rem = args.rem;
   if (w < x * nfull) {
     const int j = w / nfull, cb = w - j * nfull;
