@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libcarca_hip.so")
 _STAMP = LIB_PATH + ".srchash"
 SOURCES = ["api.hip", "gemm.hip", "gemm_wgrad.hip", "gemm_split.hip", "gemm_stream.hip", "wgrad_cu.hip", "decoders.hip", "batch_build.hip", "embed.hip", "sa_block.hip", "sa_eval.hip", "cross_score.hip", "cross_stream.hip", "loss_metrics.hip", "backward.hip", "block_bwd.hip", "row_chain.hip", "optim.hip", "recommend.hip", "rank.hip", "knn_catalogue.hip",
            "catalogue_xent.hip", "feat_dedup.hip", "sampled_xent.hip", "sampled_bce.hip", "similar_items.hip", "mmr_rerank.hip", "recommend_lists.hip", "explain_lists.hip",
-           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip", "policy_items.hip", "policy_xent.hip"]
+           "recommend_users.hip", "recommend_contexts.hip", "retrieve.hip", "recommend_sampled.hip", "policy_items.hip", "policy_xent.hip", "listed_xent.hip"]
 HEADERS = ["carca_common.h", "gemm_host.h", "attn_common.h", "gemm_epilogue.h", "gemm_tile384.h", "cross_fold.h", "recommend_common.h", "catalogue_select.h",
            "catalogue_sweep.h", "xent_tile.h", "xent_stage.h", "xent_direct.h", "row_stream.h", "group_select.h", "recommend_score.h", "deep_select.h",
            "sampled_select.h", "policy_items.h"]
@@ -344,6 +344,15 @@ class SampledXentDesc(C.Structure):
                 ("dP", _fp), ("dTp", _fp), ("dS", _fp)]
 
 
+class ListedXentDesc(C.Structure):
+    """CarcaListedXentDesc (carca_listed_xent_fwd / _bwd)."""
+    _fields_ = [(n, C.c_int32) for n in ("R", "G", "rows_per_list", "N", "U", "n_items", "d")] + [
+        ("P", _fp), ("ld_p", C.c_int32), ("Tp", _fp), ("ld_tp", C.c_int32), ("pos_bias", _fp), ("pos", _fp), ("S", _fp),
+        ("ld_s", C.c_int32), ("lists", _fp), ("index", _fp), ("bias", _fp), ("csr_off", _fp), ("csr_ent", _fp),
+        ("splits", C.c_int32), ("entries_per_split", C.c_int32), ("scratch", _fp), ("scratch_floats", C.c_int64),
+        ("lse", _fp), ("row_loss", _fp), ("loss", _fp), ("grad", _fp), ("dP", _fp), ("dTp", _fp), ("dS", _fp)]
+
+
 class SampledBceDesc(C.Structure):
     """CarcaSampledBceDesc (carca_sampled_bce_fwd / _bwd)."""
     _fields_ = [("R", C.c_int32), ("K", C.c_int32), ("n_items", C.c_int32), ("d", C.c_int32), ("P", _fp),
@@ -493,6 +502,8 @@ SIGNATURES = {
     "carca_policy_xent_bwd": (_i, [C.POINTER(PolicyXentDesc), _fp]),
     "carca_sampled_xent_fwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
     "carca_sampled_xent_bwd": (_i, [C.POINTER(SampledXentDesc), _fp]),
+    "carca_listed_xent_fwd": (_i, [C.POINTER(ListedXentDesc), _fp]),
+    "carca_listed_xent_bwd": (_i, [C.POINTER(ListedXentDesc), _fp]),
     "carca_sampled_bce_fwd": (_i, [C.POINTER(SampledBceDesc), _fp]),
     "carca_sampled_bce_bwd": (_i, [C.POINTER(SampledBceDesc), _fp]),
     "carca_build_train_batch": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _fp, _fp, _fp, _fp, _fp,

@@ -105,6 +105,69 @@ def _candidates(what: str, candidates, D, keep: list, device):
     return _lib.Candidates(ids.data_ptr() if ids.shape[0] else None, ids.shape[0])
 
 
+class NegativeLists:
+    """A list of negative item ids per group of rows, for ops.listed_xent / CARCA.listed_softmax_loss (DESIGN.md section
+    30): hard negatives from CARCA.retrieve, logged impressions, any per-user candidate list.
+
+    lists: an integer tensor [G, N], N >= 1, G N < 2^31; ids outside [1, n_items) -- 0 and negatives included -- are padding
+    (no class), duplicates inside a list and across lists are allowed and each counts.  bias: None or a float [G, N]
+    tensor added to the entries' logits (a logQ-style correction; no gradient).  The constructor builds once, on the
+    lists' device (CPU tensors too), what the loss needs at every call; the read of U is its one host sync, so build it
+    once per set of lists, not inside a captured step.  The fields: `lists` [G, N] int32 (ids outside [0, n_items) sent
+    to -1 or n_items), `ids` [U] int32, the distinct live ids ascending (the rows of S the caller embeds), `index` [G, N]
+    int32, the position in `ids` of each entry or -1 for padding, `csr_off` [U + 1] and `csr_ent` [G N] int32, the lists
+    by item: csr_ent[csr_off[u] : csr_off[u + 1]] are the flat positions g N + j of the entries of ids[u], ascending (the
+    fixed order in which the backward sums an item's gradient; ops.listed_csr), `bias` float32 [G, N] or None; n_items,
+    G and N are ints.  An all-padding object is legal: U = 0."""
+
+    def __init__(self, lists: Tensor, n_items: int, bias: Optional[Tensor] = None):
+        n_items = int(n_items)
+        if n_items < 1:
+            raise CarcaHipError(f"NegativeLists: n_items = {n_items} must be positive")
+        if not isinstance(lists, Tensor) or lists.dim() != 2 or lists.shape[0] < 1 or lists.shape[1] < 1 or \
+                lists.is_floating_point() or lists.is_complex() or lists.dtype == torch.bool:
+            raise CarcaHipError("NegativeLists: lists must be an integer tensor [G, N] with G, N >= 1")
+        G, N = lists.shape
+        if G * N >= 2 ** 31:
+            raise CarcaHipError(f"NegativeLists: G x N = {G * N} must stay below 2^31")
+        if bias is not None:
+            if not isinstance(bias, Tensor) or tuple(bias.shape) != (G, N) or not bias.is_floating_point():
+                raise CarcaHipError(f"NegativeLists: bias must be a float tensor [G, N] = [{G}, {N}]")
+            bias = bias.detach().to(device=lists.device, dtype=torch.float32).contiguous()
+        flat = lists.detach().reshape(-1).to(torch.int64)
+        live = (flat >= 1) & (flat < n_items)
+        safe = torch.where(live, flat, torch.zeros_like(flat))
+        present = torch.zeros(n_items, dtype=torch.bool, device=lists.device)
+        present[safe] = True
+        present[0] = False
+        ids = torch.nonzero(present, as_tuple=False).reshape(-1)  # (ascending; the one host sync: U)
+        rank = torch.cumsum(present.to(torch.int64), 0) - 1
+        index = torch.where(live, rank[safe], torch.full_like(flat, -1)).to(torch.int32).reshape(G, N).contiguous()
+        self.n_items, self.G, self.N = n_items, G, N
+        self.lists = flat.clamp(min=-1, max=n_items).to(torch.int32).reshape(G, N).contiguous()
+        self.ids = ids.to(torch.int32).contiguous()
+        self.index = index
+        self.csr_off, self.csr_ent = ops.listed_csr(index, self.ids.shape[0])
+        self.bias = bias
+
+    def __len__(self) -> int:
+        return self.ids.shape[0]
+
+    _FIELDS = ("lists", "ids", "index", "csr_off", "csr_ent")
+
+    def to(self, device) -> "NegativeLists":
+        """The lists on `device`: itself when they are there already, else a copy of the built fields (no host sync)."""
+        ids = self.ids.to(device)
+        if ids is self.ids:
+            return self
+        out = object.__new__(NegativeLists)
+        out.n_items, out.G, out.N = self.n_items, self.G, self.N
+        for f in self._FIELDS:
+            setattr(out, f, getattr(self, f).to(device))
+        out.bias = None if self.bias is None else self.bias.to(device)
+        return out
+
+
 GROUPS_MAX = 65535  # most groups of an ItemGroups (csrc: RG_MAX_GROUPS, a grid dimension)
 CAPPED_SCRATCH_MAX = 1 << 30  # bytes of recommend_capped's [B, G, m] key scratch (csrc: RG_MAX_KEY_BYTES)
 

@@ -418,6 +418,87 @@ def sampled_softmax_loss(model, profile, pos: Tensor, samples: Tensor, log_q: Te
     return _SampledFn.apply(model, tuple(profile), pos, samples, log_q, *cached_parameters(model))
 
 
+# ---- softmax over per-user negative lists ------------------------------------------------------
+def _listed_operands(negatives):
+    """(the ids of the [1, U] target segment, the CSR for them): NegativeLists' own, or, for an all-padding object, one
+    padding id (a segment needs a row; no entry points to it) with the CSR of that one row."""
+    if len(negatives) > 0:
+        return negatives.ids, (negatives.csr_off, negatives.csr_ent)
+    return torch.zeros(1, dtype=torch.int32, device=negatives.ids.device), ops.listed_csr(negatives.index, 1)
+
+
+class _ListedFn(torch.autograd.Function):
+    """The fused route of the listed loss: _SampledFn's, with the lists' distinct items as the [1, U] target segment."""
+
+    @staticmethod
+    def forward(ctx, model, profile, pos, negatives, *params):
+        ids, csr = _listed_operands(negatives)
+        segs, n_items = _sampled_segments(model, profile, pos, ids)
+        rows, (es_s, es_p), st = _profile_forward(model, segs)
+        dpi, U, L = st["dpi"], segs[1][0].shape[1], st["L"]
+        S, Tp = es_s.view(U, dpi), es_p.view(-1, dpi)
+        pos32 = ops._ids32_clamped(pos.reshape(-1), n_items)
+        d = model.embeds.d
+        lx = (pos32, negatives.lists, negatives.index, L, negatives.bias, None, n_items)
+        loss, lse, row_loss = ops.listed_xent_fwd(rows, Tp, pos32, S, negatives.lists, negatives.index, L, negatives.bias,
+                                                  None, n_items, d)
+        ctx.model, ctx.params = model, params
+        ctx.st = dict(st, S=S, Tp=Tp, lx=lx, csr=csr, lse=lse, row_loss=row_loss)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        st, d = ctx.st, ctx.model.embeds.d
+
+        def loss_bwd():
+            pos32, lists, index, L, bias, pos_bias, n_items = st["lx"]
+            dP, dTp, dS = ops.listed_xent_bwd(st["rows"], st["Tp"], pos32, st["S"], lists, index, L, bias, pos_bias,
+                                              n_items, st["csr"], st["lse"], st["row_loss"], g.detach(), d)
+            return dP, [dS, dTp]
+
+        grads = _profile_backward(ctx.model, ctx.params, st, loss_bwd)
+        ctx.st = None
+        return (None, None, None, None) + grads
+
+
+def _listed_composed_loss(model, profile, pos, negatives) -> Tensor:
+    ids, csr = _listed_operands(negatives)
+    segs, n_items = _sampled_segments(model, profile, pos, ids)
+    p_n, (S, Tp) = _composed_rows(model, profile, segs, "listed_softmax_loss")
+    d, L = model.embeds.d, profile[0].shape[1]
+    return ops.listed_xent(p_n.reshape(-1, d), Tp.reshape(-1, d), pos.reshape(-1), S.reshape(-1, d), negatives.lists,
+                           negatives.index, L, negatives.bias, n_items=n_items, csr=csr)
+
+
+def listed_softmax_loss(model, profile, pos: Tensor, negatives) -> Tensor:
+    from .catalogue import NegativeLists
+    from .modules import cached_parameters, note_training_forward
+
+    what = "listed_softmax_loss"
+    _check(model, profile, pos, what)
+    emb = model.embeds
+    n_items = emb.items_embed.num_embeddings if hasattr(emb, "items_embed") else emb.attr_table().shape[0]
+    B, L = profile[0].shape
+    if not isinstance(negatives, NegativeLists):
+        if not isinstance(negatives, Tensor):
+            raise CarcaHipError(f"{what}: negatives must be a NegativeLists or an integer tensor [B, N]")
+        ops._need_cuda(negatives)
+        negatives = NegativeLists(negatives, n_items)
+    if negatives.n_items != n_items:
+        raise CarcaHipError(f"{what}: the negative lists were built for n_items = {negatives.n_items}, the model has "
+                            f"{n_items}")
+    if negatives.G != B:
+        raise CarcaHipError(f"{what}: one list per user is needed, [B = {B}, N]; got {negatives.G} lists")
+    if L > ops.LISTED_MAX_ROWS_PER_LIST:
+        raise CarcaHipError(f"{what}: L={L} > {ops.LISTED_MAX_ROWS_PER_LIST} profile slots")
+    negatives = negatives.to(profile[0].device)
+    ops._need_cuda(negatives.ids)
+    note_training_forward()  # packed-weight caches: see modules._WEIGHT_EPOCH
+    if model._composed(profile, [profile]):
+        return _listed_composed_loss(model, profile, pos, negatives)
+    return _ListedFn.apply(model, tuple(profile), pos, negatives, *cached_parameters(model))
+
+
 # ---- BCE against K shared negatives, gBCE (DESIGN.md section 16) ------------------------------------------------------
 def _context_rows(model, pos_ctx: Tensor):
     """C [B L, d] = M c_r, the context's share of e(i, c) = T[i] + M c, as a differentiable function of the embedding's

@@ -297,6 +297,26 @@ def _sampled_softmax_step(model, optim, batch, sampler) -> torch.Tensor:
     return loss.detach()
 
 
+def hard_negative_step(model, optim, batch, miner, graphed: bool = False, sharded: bool = False) -> torch.Tensor:
+    """One optimizer step of the softmax over mined per-user negatives: miner.mine (a
+    sampling.HardNegativeMiner: the current model's top items per user, in eval mode under no_grad), then
+    CARCA.listed_softmax_loss over the positive half against those lists, backward, the touched rows announced as the
+    sampled steps do (the profile's, the positives' and the lists' distinct items), the step.  Mining reads the item-side
+    tables, which are rebuilt once per weight version -- here every step; it also costs the step's one host sync (the
+    lists' U).  Graph-captured and sharded steps are not built.  -> the (device) loss."""
+    if graphed or sharded:
+        raise CarcaHipError("hard_negative_step: graphed and sharded steps are not built")
+    p_x, p_a, p_c, o_x = as_batch7(batch)[:4]
+    pos = o_x[:, : o_x.shape[1] // 2]  # train.py:86-88: the positive half
+    negatives = miner.mine(model, (p_x, p_a, p_c), pos)
+    optim.zero_grad(set_to_none=True)
+    loss = model.listed_softmax_loss((p_x, p_a, p_c), pos, negatives)
+    loss.backward()
+    _mark_sampled_rows(model, optim, p_x, pos, negatives.ids)
+    optim.step()
+    return loss.detach()
+
+
 def _forward_backward(model, optim, batch, denom: Optional[torch.Tensor]) -> torch.Tensor:
     """denom: the loss normaliser (device float[1]: the all-reduced mask count of a sharded step), None = this batch's own."""
     p_x, p_a, p_c, o_x, o_a, o_c, y_true = batch

@@ -1353,6 +1353,20 @@ class CARCA(_PackedModule, Model):
 
         return sampled_softmax_loss(self, profile, pos, samples, log_q)
 
+    def listed_softmax_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor, negatives) -> Tensor:
+        """Softmax cross-entropy against a different list of negatives per user: hard negatives
+        mined with retrieve (sampling.HardNegativeMiner), logged impressions, any per-user candidate list.  negatives: a
+        catalogue.NegativeLists of [B, N] built for this model's n_items -- one list per user, shared by the user's L
+        slots -- or a raw integer tensor [B, N], which builds one for this call and so costs a host sync per call.  Each
+        valid slot's logsumexp runs over its positive and the entries of its user's list that are items and not its
+        positive (duplicates each count), an entry's logit plus negatives.bias where one was given; ids outside
+        [1, n_items) are padding, a slot whose list has no such entry pays 0.  With every list arange(1, n_items) it
+        equals catalogue_softmax_loss.  No float atomics: the same call gives the same bits.  Same decoders, embeddings,
+        dropout and errors as catalogue_softmax_loss."""
+        from .catalogue_xent import listed_softmax_loss
+
+        return listed_softmax_loss(self, profile, pos, negatives)
+
     def sampled_bce_loss(self, profile: Tuple[Tensor, Optional[Tensor], Tensor], pos: Tensor, pos_ctx: Tensor,
                          samples: Tensor, t: float = 0.75) -> Tensor:
         """Binary cross-entropy against K negatives shared by every slot, gBCE (Petrov & Macdonald, gSASRec; DESIGN.md

@@ -1981,6 +1981,180 @@ def sampled_bce(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, s_ids: Tensor, n_
     return _SampledBceFn.apply(P, Tp, S, C, _ids32(pos.reshape(-1)), _ids32(s_ids.reshape(-1)), int(n_items), float(beta))
 
 
+# --------------------------------------------------------------------------------------------------
+# softmax cross-entropy over per-list negatives (carca_listed_xent_fwd / _bwd)
+# --------------------------------------------------------------------------------------------------
+LISTED_MAX_ROWS_PER_LIST = 1024
+
+
+def listed_xent_plan(G: int, rows_per_list: int, N: int, U: int, d: int, n_cus: int = 256) -> dict:
+    """Host-side sizing of carca_listed_xent_fwd / _bwd (pure: no device).  A list's N entries are split so that the
+    forward's and dP's (group x row block x split) grid has about CX_WAVES_PER_CU workgroups per CU.  Returns splits,
+    entries_per_split and the scratch each call needs, in 4-byte words: 2 ceil64(R) + 64 + ceil64(G + 1) of row lists and
+    group offsets (R = G rows_per_list), then the forward's 2 ceil64(splits R) (max, sum-exp) partials, or the backward's
+    dP partials [splits + 1, R, ld] (the last: the positive term) and the entry partials [G N, ld], ld = round_up(d, 4):
+    scratch_bwd <= (G N + (splits + 1) R) ld + O(R).  U (the rows of S) does not enter the sizes."""
+    if G < 1 or N < 1 or d < 1 or U < 0 or not 1 <= rows_per_list <= LISTED_MAX_ROWS_PER_LIST:
+        raise CarcaHipError("listed_xent_plan: G, N and d must be positive, U >= 0 and rows_per_list in 1..1024")
+    if G * N >= 2 ** 31:
+        raise CarcaHipError("listed_xent_plan: G x N must stay below 2^31")
+    r64 = lambda n: (n + 63) // 64 * 64  # noqa: E731
+    R, ldo = G * rows_per_list, (d + 3) // 4 * 4
+    target = CX_WAVES_PER_CU * max(1, int(n_cus))
+    n_row_blocks = G * -(-rows_per_list // CX_TILE)
+    n_entry_blocks = -(-N // CX_TILE)
+    splits = max(1, min(n_entry_blocks, CX_MAX_SPLITS, -(-target // n_row_blocks)))
+    per = -(-n_entry_blocks // splits) * CX_TILE
+    splits = -(-N // per)  # (no empty split)
+    head = 2 * r64(R) + 64 + r64(G + 1)
+    return dict(splits=splits, entries_per_split=per, scratch_fwd=head + 2 * r64(splits * R),
+                scratch_bwd=head + r64((splits + 1) * R * ldo) + r64(G * N * ldo))
+
+
+def listed_csr(index: Tensor, U: int) -> Tuple[Tensor, Tensor]:
+    """The lists by item, for the backward's dS: (csr_off [U + 1] int32, csr_ent [G N] int32) with
+    csr_ent[csr_off[u] : csr_off[u + 1]] the flat positions g N + j of the entries with index[g, j] == u, ascending
+    (entries with a negative index sort to the end, past csr_off[U]).  One stable sort and one searchsorted of fixed
+    shapes, on index's device (CPU tensors too); no host wait."""
+    flat = index.reshape(-1).to(torch.int64)
+    key = torch.where(flat >= 0, flat, torch.full_like(flat, U))
+    vals, perm = torch.sort(key, stable=True)
+    bounds = torch.arange(U + 1, dtype=torch.int64, device=index.device)
+    return torch.searchsorted(vals, bounds).to(torch.int32), perm.to(torch.int32)
+
+
+def _lx_desc(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, lists: Tensor, index: Tensor, rows_per_list: int,
+             bias: Optional[Tensor], pos_bias: Optional[Tensor], n_items: int, d: int, scratch_key: str, keep: list):
+    """The descriptor of either pass: pos [R], lists and index [G, N] int32 contiguous, bias [G, N] and pos_bias [R]
+    float32 or None."""
+    R, (G, N), U = P.shape[0], lists.shape, S.shape[0]
+    if R != G * int(rows_per_list) or tuple(index.shape) != (G, N) or pos.numel() != R:
+        raise CarcaHipError(f"listed_xent: expected R = G rows_per_list rows, pos [R] and index [G, N]; got R = {R}, "
+                            f"G = {G}, rows_per_list = {rows_per_list}, index {tuple(index.shape)}, pos {tuple(pos.shape)}")
+    for t, name in ((pos, "pos"), (lists, "lists"), (index, "index")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise CarcaHipError(f"listed_xent: {name} must be int32 and contiguous")
+    plan = listed_xent_plan(G, int(rows_per_list), N, U, d, num_cus())
+    D = _lib.ListedXentDesc()
+    D.R, D.G, D.rows_per_list, D.N, D.U, D.n_items, D.d = R, G, int(rows_per_list), N, U, int(n_items), d
+    D.P, D.ld_p, D.Tp, D.ld_tp = P.data_ptr(), P.stride(0), Tp.data_ptr(), Tp.stride(0)
+    D.S, D.ld_s = (S.data_ptr(), S.stride(0)) if U > 0 else (None, (d + 3) // 4 * 4)
+    D.pos, D.lists, D.index = pos.data_ptr(), lists.data_ptr(), index.data_ptr()
+    if bias is not None:
+        bias = _f32(bias.reshape(G, N))
+        keep.append(bias)
+        D.bias = bias.data_ptr()
+    if pos_bias is not None:
+        pos_bias = _f32(pos_bias.reshape(R))
+        keep.append(pos_bias)
+        D.pos_bias = pos_bias.data_ptr()
+    return _xent_splits(D, plan, ("splits", "entries_per_split"), scratch_key, P.device, keep)
+
+
+def listed_xent_fwd(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, lists: Tensor, index: Tensor, rows_per_list: int,
+                    bias: Optional[Tensor], pos_bias: Optional[Tensor], n_items: int, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Mean softmax cross-entropy over per-list negatives (include/carca_hip.h: carca_listed_xent_fwd) of rows P [R, ld_p]
+    with positives Tp [R, ld_tp] against the entries of lists [G, N] (int32), whose rows are S[index] (S [U, ld_s], index
+    [G, N] int32, negative: no class); first d columns, strides multiples of 4.  Returns (loss [1], lse [R], row_loss
+    [R]); no host wait."""
+    _need_cuda(P, Tp, pos, S, lists, index, bias, pos_bias)
+    keep: list = []
+    D = _lx_desc(P, Tp, pos, S, lists, index, rows_per_list, bias, pos_bias, n_items, d, "scratch_fwd", keep)
+    lse = torch.empty(P.shape[0], dtype=torch.float32, device=P.device)
+    row_loss = torch.empty_like(lse)
+    loss = torch.empty(1, dtype=torch.float32, device=P.device)
+    D.lse, D.row_loss, D.loss = lse.data_ptr(), row_loss.data_ptr(), loss.data_ptr()
+    _lib.check(_lib.load().carca_listed_xent_fwd(C.byref(D), _stream()), "listed_xent_fwd")
+    return loss, lse, row_loss
+
+
+def listed_xent_bwd(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, lists: Tensor, index: Tensor, rows_per_list: int,
+                    bias: Optional[Tensor], pos_bias: Optional[Tensor], n_items: int, csr: Tuple[Tensor, Tensor],
+                    lse: Tensor, row_loss: Tensor, grad: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dP [R, ld_p], dTp [R, ld_tp], dS [U, ld_s]) of listed_xent_fwd's loss scaled by grad [1] (device); zeros past d.
+    csr: listed_csr(index, U), the order in which an item's entry partials are summed."""
+    csr_off, csr_ent = csr
+    _need_cuda(P, Tp, pos, S, lists, index, bias, pos_bias, lse, row_loss, grad, csr_off, csr_ent)
+    U = S.shape[0]
+    if (csr_off.dtype != torch.int32 or csr_ent.dtype != torch.int32 or csr_off.numel() != U + 1
+            or csr_ent.numel() != lists.numel() or not csr_off.is_contiguous() or not csr_ent.is_contiguous()):
+        raise CarcaHipError("listed_xent_bwd: csr must be listed_csr's (int32 [U + 1] and [G N], contiguous)")
+    keep: list = []
+    D = _lx_desc(P, Tp, pos, S, lists, index, rows_per_list, bias, pos_bias, n_items, d, "scratch_bwd", keep)
+    g = _f32(grad.reshape(1))
+    dP, dTp, dS = (torch.empty(x.shape[0], x.stride(0) if x.shape[0] else (d + 3) // 4 * 4, dtype=torch.float32,
+                               device=P.device) for x in (P, Tp, S))
+    D.dP, D.dTp, D.dS = dP.data_ptr(), dTp.data_ptr(), dS.data_ptr() if U > 0 else None
+    D.csr_off, D.csr_ent = csr_off.data_ptr(), csr_ent.data_ptr()
+    D.lse, D.row_loss, D.grad = lse.data_ptr(), row_loss.data_ptr(), g.data_ptr()
+    _lib.check(_lib.load().carca_listed_xent_bwd(C.byref(D), _stream()), "listed_xent_bwd")
+    return dP, dTp, dS
+
+
+class _ListedXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, Tp, S, pos32, lists32, index32, rows_per_list, bias, pos_bias, n_items, csr_off, csr_ent):
+        d = P.shape[1]
+        P2, Tp2, S2 = (_xent_operand(x.detach(), d, "listed_xent") for x in (P, Tp, S))
+        loss, lse, row_loss = listed_xent_fwd(P2, Tp2, pos32, S2, lists32, index32, rows_per_list, bias, pos_bias,
+                                              n_items, d)
+        ctx.save_for_backward(P2, Tp2, S2, pos32, lists32, index32, bias, pos_bias, csr_off, csr_ent, lse, row_loss)
+        ctx.d, ctx.n_items, ctx.rows_per_list = d, n_items, rows_per_list
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        P2, Tp2, S2, pos32, lists32, index32, bias, pos_bias, csr_off, csr_ent, lse, row_loss = ctx.saved_tensors
+        d = ctx.d
+        dP, dTp, dS = listed_xent_bwd(P2, Tp2, pos32, S2, lists32, index32, ctx.rows_per_list, bias, pos_bias,
+                                      ctx.n_items, (csr_off, csr_ent), lse, row_loss, g.detach(), d)
+        return (dP[:, :d], dTp[:, :d], dS[:, :d]) + (None,) * 9
+
+
+def listed_xent(P: Tensor, Tp: Tensor, pos: Tensor, S: Tensor, lists: Tensor, index: Tensor, rows_per_list: int,
+                bias: Optional[Tensor] = None, pos_bias: Optional[Tensor] = None, *, n_items: int,
+                csr: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+    """Mean softmax cross-entropy of each row against its own list of negatives, differentiable in P, Tp and S (DESIGN.md
+    section 30).  Row r reads list g = r // rows_per_list; with z(r, +) = P[r] . Tp[r] + pos_bias[r] and
+    z(r, j) = P[r] . S[index[g, j]] + bias[g, j]:
+
+        sum over valid r of ( logsumexp( {z(r, +)} U {z(r, j) : j in N_r} ) - z(r, +) ) / n_valid
+        N_r = {j : index[g, j] >= 0, lists[g, j] in [1, n_items), lists[g, j] != pos[r]}      (duplicates each count)
+
+    P [R, d], Tp [R, d] (the rows of the positives), S [U, d] (the embedded rows of the U distinct items of the lists)
+    fp32; pos [R] and lists [G, N] integer, index [G, N] integer: the row of S of each entry, negative for an entry that
+    is no class; R = G rows_per_list, 1 <= rows_per_list <= 1024; bias [G, N] and pos_bias [R] fp32 or None (logQ-style
+    corrections; no gradient).  Row r is valid iff pos[r] lies in [1, n_items); a batch without a valid row gives 0, a
+    valid row without a negative has row loss 0; U = 0 is legal.  dS is 0 for a row of S no live entry points to.  csr:
+    listed_csr(index, U) when the caller holds it (catalogue.NegativeLists does), else built here, on the device.
+    Fused HIP kernels: no [R, N] buffer, no float atomics, the same call gives the same bits, no host wait."""
+    _need_cuda(P, Tp, pos, S, lists, index, bias, pos_bias)
+    if P.dim() != 2 or Tp.dim() != 2 or S.dim() != 2 or Tp.shape != P.shape or S.shape[1] != P.shape[1]:
+        raise CarcaHipError(f"listed_xent: expected P [R, d], Tp [R, d], S [U, d]; got {tuple(P.shape)}, "
+                            f"{tuple(Tp.shape)}, {tuple(S.shape)}")
+    if lists.dim() != 2 or lists.shape[1] < 1 or tuple(index.shape) != tuple(lists.shape):
+        raise CarcaHipError(f"listed_xent: lists and index must be [G, N] with N >= 1; got {tuple(lists.shape)} and "
+                            f"{tuple(index.shape)}")
+    if any(t.is_floating_point() or t.dtype == torch.bool for t in (pos, lists, index)):
+        raise CarcaHipError("listed_xent: pos, lists and index must be integer tensors")
+    if any(t.dtype != torch.float32 for t in (P, Tp, S)):
+        raise CarcaHipError(f"listed_xent: P, Tp and S must be float32, got {P.dtype}, {Tp.dtype}, {S.dtype}")
+    rows_per_list = int(rows_per_list)
+    if not 1 <= rows_per_list <= LISTED_MAX_ROWS_PER_LIST or lists.shape[0] * rows_per_list != P.shape[0]:
+        raise CarcaHipError(f"listed_xent: rows_per_list must lie in 1..{LISTED_MAX_ROWS_PER_LIST} with R = G "
+                            f"rows_per_list; got {rows_per_list} for R = {P.shape[0]}, G = {lists.shape[0]}")
+    if pos.numel() != P.shape[0]:
+        raise CarcaHipError(f"listed_xent: pos must have R = {P.shape[0]} entries, got {pos.numel()}")
+    if lists.numel() >= 2 ** 31:
+        raise CarcaHipError("listed_xent: G x N must stay below 2^31")
+    n_items, U = int(n_items), S.shape[0]
+    index32 = _ids32(index.clamp(min=-1, max=max(U - 1, -1)))
+    if csr is None:
+        csr = listed_csr(index32, U)
+    return _ListedXentFn.apply(P, Tp, S, _ids32_clamped(pos.reshape(-1), n_items), _ids32_clamped(lists, n_items), index32,
+                               rows_per_list, bias, pos_bias, n_items, csr[0], csr[1])
+
+
 def similar_rows(table: Tensor, n_cols: int, items: Optional[Tensor], k: int = 10, metric: str = "cosine",
                  exclude_self: bool = True, candidates=None, max_scratch_bytes: int = 1 << 30) -> Tuple[Tensor, Tensor]:
     """Item-to-item top-k over any fp32 row table on the device (carca_similar_items): for each id

@@ -401,6 +401,25 @@ def train_off_policy(model: Model, logs, device: str, optim: Optimizer, epochs: 
     return out
 
 
+def train_hard_negatives(model: Model, train_loader, device: str, optim: Optimizer, epochs: int, miner) -> list:
+    """Train `model` with the softmax over mined per-user negatives: engine.hard_negative_step over
+    every batch of `train_loader` (the training loader's 7- or 5-tuples; a re-iterable) for `epochs` epochs, `miner` a
+    sampling.HardNegativeMiner.  The model's mode is the caller's (dropout follows model.training; mining switches to
+    eval for its own call).  Every step mines with the current weights, so it rebuilds the item-side tables and syncs
+    once; the loss is read once per epoch.  -> the mean loss of each epoch, as Python floats."""
+    model = model.to(device)
+    out = []
+    for _ in range(epochs):
+        total = torch.zeros((), dtype=torch.float64, device=device)
+        n = 0
+        for batch in train_loader:
+            dev_batch = to(*engine.as_batch7(batch), device=device)
+            total = total + engine.hard_negative_step(model, optim, dev_batch, miner)
+            n += 1
+        out.append(float(total) / max(n, 1))  # (the epoch's host sync)
+    return out
+
+
 def train(model: Model, train_loader: DataLoader, val_loader: DataLoader, test_loader: DataLoader, device: str,
           optim: Optimizer, epochs: int, top_k: int = 10, verbose: int = 1, early_stop: int = 10,
           datadir: str = "model", scheduler: Union[_LRScheduler, None] = None, graphed: bool = False,

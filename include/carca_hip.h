@@ -1559,6 +1559,63 @@ typedef struct CarcaSampledXentDesc {
 int carca_sampled_xent_fwd(const CarcaSampledXentDesc* desc, void* stream);
 int carca_sampled_xent_bwd(const CarcaSampledXentDesc* desc, void* stream);
 
+/* ---- softmax cross-entropy over per-list negatives for the dot decoders ----------------------
+ * P [R, ld_p] profile rows, Tp [R, ld_tp] the rows of their positives, S [U, ld_s] the embedded rows of the U distinct
+ * items of the lists (d features; ld_p, ld_tp, ld_s multiples of 4; P, S and dS 16-byte aligned), pos [R] int32, lists
+ * [G, N] int32 item ids, index [G, N] int32 the row of S of each entry (< 0: the entry is no class; any other value is
+ * clamped into [0, U) before it is used as an address), bias [G, N] and pos_bias [R] additive corrections or NULL.
+ * R = G rows_per_list, rows_per_list in 1..1024: row r reads list g = r / rows_per_list.  Row r is VALID iff pos[r] lies
+ * in [1, n_items).  Entry (g, j) is a negative of row r iff index[g][j] >= 0, lists[g][j] lies in [1, n_items) and
+ * differs from pos[r] (duplicates each count).
+ *   carca_listed_xent_fwd: with z(r, +) = P[r] . Tp[r] + pos_bias[r] and z(r, j) = P[r] . S[index[g][j]] + bias[g][j],
+ *     lse[r] = log( exp z(r, +) + sum over the negatives j of r of exp z(r, j) ), row_loss[r] = lse[r] - z(r, +)
+ *     (both 0 for a row that is not valid; row_loss 0 for a valid row without a negative), loss[0] = sum of row_loss /
+ *     n_valid (0 when no row is valid);
+ *   carca_listed_xent_bwd: with lse and row_loss from the forward and the upstream scale grad[0],
+ *     G[r, j] = exp(z(r, j) - lse[r]) on the negatives (else 0), p_pos = exp(-row_loss[r]):
+ *     dP  = grad / n_valid (sum_j G[r, j] S[index[g][j]] + (p_pos - 1) Tp), dTp = grad / n_valid (p_pos - 1) P  (0 for
+ *     rows that are not valid), dS[u] = grad / n_valid sum over the entries (g, j) of item u of E[g][j], E[g][j] = sum
+ *     over the rows r of group g of G[r, j] P[r], summed in the order of the by-item CSR: csr_off [U + 1] int32 and
+ *     csr_ent int32, csr_ent[csr_off[u] .. csr_off[u + 1]) the flat positions g N + j of the live entries with index
+ *     u, ascending; a row of S without an entry gets 0; every output 0 past d.
+ * Products in exact-fp32 MFMA; the logit tiles are recomputed, never stored.  A list is split over `splits` workgroup
+ * columns of entries_per_split (a multiple of 64).  Scratch (scratch_floats 4-byte words, 16-byte aligned,
+ * caller-allocated; ops.listed_xent_plan gives the size): 2 ceil64(R) + 64 + ceil64(G + 1) words of row lists and group
+ * offsets, then the forward's 2 ceil64(splits R) (max, sum-exp) partials, or the backward's ceil64((splits + 1) R ld) dP
+ * partials and the ceil64(G N ld) entry partials E, ld = round_up(d, 4).  No float atomics: the same call gives the same
+ * bits.  U = 0 is legal (S, dS, csr_* unused): every valid row's loss is 0.
+ * CARCA_ERR_UNSUPPORTED: d > 256, G N >= 2^31, R >= 2^25 - 64.  CARCA_ERR_BADARG: null pointers, strides, alignment,
+ * rows_per_list outside 1..1024 or R != G rows_per_list, splits outside 1..256, entries_per_split * splits < N,
+ * scratch too small. */
+typedef struct CarcaListedXentDesc {
+  int R, G, rows_per_list, N, U, n_items, d;
+  const float* P;
+  int ld_p;
+  const float* Tp;
+  int ld_tp;
+  const float* pos_bias;   /* [R] or NULL */
+  const int32_t* pos;      /* [R] */
+  const float* S;          /* [U, ld_s] */
+  int ld_s;
+  const int32_t* lists;    /* [G, N] */
+  const int32_t* index;    /* [G, N] */
+  const float* bias;       /* [G, N] or NULL */
+  const int32_t* csr_off;  /* [U + 1] backward */
+  const int32_t* csr_ent;  /* [>= csr_off[U]] backward */
+  int splits, entries_per_split;
+  float* scratch;
+  int64_t scratch_floats;
+  float* lse;        /* [R]: forward output, backward input */
+  float* row_loss;   /* [R]: forward output, backward input */
+  float* loss;       /* [1] forward */
+  const float* grad; /* [1] backward: upstream scale of loss */
+  float* dP;         /* [R, ld_p] backward */
+  float* dTp;        /* [R, ld_tp] backward */
+  float* dS;         /* [U, ld_s] backward */
+} CarcaListedXentDesc;
+int carca_listed_xent_fwd(const CarcaListedXentDesc* desc, void* stream);
+int carca_listed_xent_bwd(const CarcaListedXentDesc* desc, void* stream);
+
 /* ---- binary cross-entropy against K shared negatives (gBCE) for the dot decoders -------------
  * P [R, ld_p] profile rows, Tp [R, ld_tp] the rows of their positives (context included), S [K, ld_s] the rows of K
  * samples shared by every row (zero context), C [R, ld_c] the rows' context share M c_r, or NULL (d features; ld_p, ld_tp,
